@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mvoxels/s of a float SDF extraction (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--dist spheres]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--dist spheres] [--dump-outputs DIR] [--full]
 
 One "step" = one full ExtractSignedDistanceField<float> pass (pass 1 to class records, Y pass, X pass +
 finalize + min/max) over a synthetic occupancy grid that is already resident in HBM; the
@@ -12,6 +12,17 @@ one process per GPU, with one RCCL exchange of 4-byte per-line boundary summarie
 (voxelized_geometry_tools_amd/multi_gpu.py).  `--gpus 1 --workload c5` runs config 5 on one GPU
 (the reference point of the scaling series: an N > 1 line names it in `same_workload_one_gpu`).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes the outputs of the last step when --dump-outputs is given, and
+prints the line (value, ms_per_step, the roofline from the library's kernel events of the timed steps).  Everything
+else -- the CPU baseline, the secondary SDF workloads, the raycast section, the host-pointer paths, the C++ host layer
+and, at N > 1 or with --force-slab, the in-run check of the slabs -- runs only with --full (each leg can still be left
+out there with its --no-* option).
+
+--dump-outputs DIR writes what the timed path computed in its last step, as float32 .npy files: sdf.npy (the whole
+field, when it is at most 32 MiB) or sdf_sample.npy + sdf_sample_index.npy (a fixed, seeded sample of 2^22 voxels and
+their flat C-order indices, float64), and sdf_min_max.npy; at N > 1 every rank writes its slab's files with a _rank<r>
+suffix.  The inputs are seeded: two builds run with the same arguments can be compared file by file.
 
 Launching: `python bench.py --gpus N` starts the N ranks itself (a `torch.distributed.run`
 child, started before this process touches the GPU) unless it already runs under a launcher
@@ -54,7 +65,31 @@ def parse_args():
     ap.add_argument("--no-raycast", action="store_true", help="skip the raycast voxelizer section (BASELINE config 3)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary SDF workloads (salt, unknown mix, 512^3, 64^3, batches)")
     ap.add_argument("--cpu-seconds", type=float, default=30.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baseline, secondary workloads, raycast "
+                         "section, host paths, C++ host layer, the in-run slab check (each still off with its --no-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (SDF or a seeded sample of it, min / max) as .npy to DIR")
     return ap.parse_args()
+
+
+DUMP_FULL_BYTES = 32 << 20     # fields up to this size are written whole
+DUMP_SAMPLES = 1 << 22         # else: this many voxels (before removing repeats) at seeded positions
+DUMP_SEED = 20240917
+
+
+def dump_outputs(torch, out_dir, sdf, minmax, suffix=""):
+    """The arrays a caller of the timed path receives (the SDF and its min / max), from the last timed step."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = sdf.numel()
+    if n * 4 <= DUMP_FULL_BYTES:
+        np.save(os.path.join(out_dir, "sdf%s.npy" % suffix), sdf.cpu().numpy().astype(np.float32))
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLES, dtype=np.int64))
+        vals = sdf.reshape(-1)[torch.from_numpy(idx).to(sdf.device)].cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, "sdf_sample%s.npy" % suffix), vals)
+        np.save(os.path.join(out_dir, "sdf_sample_index%s.npy" % suffix), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "sdf_min_max%s.npy" % suffix), minmax.cpu().numpy().astype(np.float32))
 
 
 def device_occupancy(torch, shape, dist, seed, device, z_offset=0, full_shape=None, salt_p=0.01):
@@ -673,8 +708,11 @@ def main():
         dist.all_reduce(pt, op=dist.ReduceOp.MAX)
         phase_ms = {k: round(float(v), 4) for k, v in zip(multi_gpu.SlabSdf.PHASES, pt.cpu().numpy())}
 
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, sdf, minmax, "" if world == 1 else "_rank%d" % rank)
+
     run_check = None
-    if dist_on:
+    if dist_on and args.full:
         run_check = slab_run_check(torch, dist, capi, ctx, runner, sdf, minmax, full_shape, local_shape, z_offset, rank,
                                    world, device, args.dist, args.salt_p, res)
 
@@ -718,18 +756,18 @@ def main():
                                 "ranks": world, "in_run_check": run_check}
             if not args.size:
                 line["same_workload_one_gpu"] = one_gpu_reference(workload_key)
-        if headline and not args.no_secondary:
+        if headline and args.full and not args.no_secondary:
             del occ, sdf, ws  # (8 + 7.4 GB: the secondary workloads allocate their own)
             occ = sdf = ws = None
             torch.cuda.empty_cache()
             line["secondary"] = secondary_workloads(ctx, torch, capi, device, res)
             occ = device_occupancy(torch, local_shape, args.dist, 42, device, z_offset, full_shape, args.salt_p)
-        if headline and not args.no_raycast:
+        if headline and args.full and not args.no_raycast:
             try:
                 line["raycast"] = raycast_section()
             except Exception as exc:
                 line["raycast"] = {"error": repr(exc)}
-        if not dist_on and not args.no_end_to_end and workload_key == "c4":
+        if args.full and not dist_on and not args.no_end_to_end and workload_key == "c4":
             try:
                 line["host_path"] = end_to_end(ctx, torch, occ, local_shape, res)
             except Exception as exc:  # the headline number must not depend on host RAM for pinned buffers
@@ -744,7 +782,7 @@ def main():
                     line["multi_host_path"] = {"error": repr(exc)}
             if headline:
                 line["cpp_host_layer"] = cpp_host_layer()
-        if not args.no_cpu_baseline and not dist_on:
+        if args.full and not args.no_cpu_baseline and not dist_on:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         else:
             line["cpu_baseline"] = None

@@ -17,6 +17,8 @@ Outputs
   voxelization_scene.npz   the scene of the reference's test/pointcloud_voxelization_test.cpp:166-246
                            (static grid, two 129x129 lattice clouds, grid<-cloud transforms).
   raycast_rays.npy         the 1000 seeded (origin, point) pairs of test/voxel_raycasting_test.cpp.
+plugin_boundary_symbols.json (not written here) is recorded by
+`python tests/test_cpp_host.py --record-plugin-symbols <reference checkout>/include`: a list of symbol names.
 None of these contain reference source text; they are inputs and expected outputs only.
 """
 import os
