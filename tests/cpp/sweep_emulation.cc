@@ -160,7 +160,7 @@ void CheckYRecords(const Case& c, std::mt19937& rng)
 }
 
 // X-pass shaped run: lines along x, int32 input (signed squared YZ distance), float output + extrema.
-void CheckX(const Case& c, std::mt19937& rng)
+void CheckX(const Case& c, const std::vector<double>& resolutions, std::mt19937& rng)
 {
   const int nx = c.nx, ny = c.ny, nz = c.nz;
   const int64_t total = static_cast<int64_t>(nx) * ny * nz;
@@ -202,56 +202,118 @@ void CheckX(const Case& c, std::mt19937& rng)
             static_cast<int32_t>(static_cast<uint32_t>(v) | (cls ? 0x80000000u : 0u));
       }
     }
-  std::vector<float> out(total, 12345.0f);
-  vgt::SdfParams p{};
-  p.nx = nx; p.ny = ny; p.nz = nz;
-  p.resolution = 0.37;
-  p.add_virtual_border = c.border ? 1 : 0;
-  std::vector<unsigned char> scratch(vgt::SweepPassScratchBytes(nx, ny, nz));
-  uint32_t minmax[2] = {0xffffffffu, 0u};
-  vgt::LaunchPassXSweepFinalize(in.data(), out.data(), minmax, vgt::SweepScratch{scratch.data(), scratch.size()}, p, nullptr);
-  std::vector<int64_t> f(nx);
-  std::vector<uint8_t> neg(nx);
-  float lo = INFINITY, hi = -INFINITY;
-  for (int y = 0; y < ny; y++)
-    for (int z = 0; z < nz; z++)
-    {
-      for (int x = 0; x < nx; x++)
+  // the brute-force squared distances (after the border clamp; INT64_MAX = no voxel of the other class) and classes, once
+  std::vector<int64_t> want_d2(total);
+  std::vector<uint8_t> want_neg(total);
+  {
+    std::vector<int64_t> f(nx);
+    std::vector<uint8_t> neg(nx);
+    for (int y = 0; y < ny; y++)
+      for (int z = 0; z < nz; z++)
       {
-        const int32_t v = in[(static_cast<int64_t>(x) * ny + y) * nz + z];
-        neg[x] = v < 0;
-        const int64_t a = v & 0x7fffffff;
-        f[x] = (a == vgt::kInf32) ? -1 : a;
-      }
-      for (int x = 0; x < nx; x++)
-      {
-        int64_t d2 = BruteRow(f, neg, nx, x);
-        if (c.border)
+        for (int x = 0; x < nx; x++)
         {
-          int64_t b = INT64_MAX;
-          if (nx > 1) b = std::min<int64_t>(b, std::min(x + 1, nx - x));
-          if (ny > 1) b = std::min<int64_t>(b, std::min(y + 1, ny - y));
-          if (nz > 1) b = std::min<int64_t>(b, std::min(z + 1, nz - z));
-          if (b != INT64_MAX) d2 = std::min(d2, b * b);
+          const int32_t v = in[(static_cast<int64_t>(x) * ny + y) * nz + z];
+          neg[x] = v < 0;
+          const int64_t a = v & 0x7fffffff;
+          f[x] = (a == vgt::kInf32) ? -1 : a;
         }
-        float want = (d2 == INT64_MAX) ? INFINITY : static_cast<float>(std::sqrt(static_cast<double>(d2)) * p.resolution);
-        if (neg[x]) want = -want;
-        lo = std::min(lo, want);
-        hi = std::max(hi, want);
-        const float got = out[(static_cast<int64_t>(x) * ny + y) * nz + z];
-        if (std::memcmp(&got, &want, 4) != 0)
+        for (int x = 0; x < nx; x++)
         {
-          if (failures++ < 10)
-            std::printf("X MISMATCH shape %dx%dx%d mode %d border %d line (y=%d,z=%d) row %d: got %g want %g\n", nx, ny, nz,
-                        c.mode, c.border, y, z, x, got, want);
+          int64_t d2 = BruteRow(f, neg, nx, x);
+          if (c.border)
+          {
+            int64_t b = INT64_MAX;
+            if (nx > 1) b = std::min<int64_t>(b, std::min(x + 1, nx - x));
+            if (ny > 1) b = std::min<int64_t>(b, std::min(y + 1, ny - y));
+            if (nz > 1) b = std::min<int64_t>(b, std::min(z + 1, nz - z));
+            if (b != INT64_MAX) d2 = std::min(d2, b * b);
+          }
+          const int64_t i = (static_cast<int64_t>(x) * ny + y) * nz + z;
+          want_d2[i] = d2;
+          want_neg[i] = neg[x];
+        }
+      }
+  }
+  std::vector<unsigned char> scratch(vgt::SweepPassScratchBytes(nx, ny, nz));
+  std::vector<float> out(total);
+  for (const double resolution : resolutions)
+  {
+    std::fill(out.begin(), out.end(), 12345.0f);
+    vgt::SdfParams p{};
+    p.nx = nx; p.ny = ny; p.nz = nz;
+    p.resolution = resolution;
+    p.add_virtual_border = c.border ? 1 : 0;
+    uint32_t minmax[2] = {0xffffffffu, 0u};
+    vgt::LaunchPassXSweepFinalize(in.data(), out.data(), minmax, vgt::SweepScratch{scratch.data(), scratch.size()}, p, nullptr);
+    float lo = INFINITY, hi = -INFINITY;
+    for (int64_t i = 0; i < total; i++)
+    {
+      const int64_t d2 = want_d2[i];
+      float want = (d2 == INT64_MAX) ? INFINITY : static_cast<float>(std::sqrt(static_cast<double>(d2)) * resolution);
+      if (want_neg[i]) want = -want;
+      lo = std::min(lo, want);
+      hi = std::max(hi, want);
+      const float got = out[i];
+      if (std::memcmp(&got, &want, 4) != 0)
+      {
+        if (failures++ < 10)
+        {
+          const int x = static_cast<int>(i / (static_cast<int64_t>(ny) * nz)), y = static_cast<int>(i / nz % ny), z = static_cast<int>(i % nz);
+          std::printf("X MISMATCH shape %dx%dx%d mode %d border %d resolution %.17g line (y=%d,z=%d) row %d d2 %lld: got %.9g want %.9g\n",
+                      nx, ny, nz, c.mode, c.border, resolution, y, z, x, static_cast<long long>(d2), got, want);
         }
       }
     }
-  const float got_lo = vgt::DecodeOrdered(minmax[0]), got_hi = vgt::DecodeOrdered(minmax[1]);
-  if (got_lo != lo || got_hi != hi)
-  {
-    if (failures++ < 10) std::printf("X EXTREMA shape %dx%dx%d: got (%g, %g) want (%g, %g)\n", nx, ny, nz, got_lo, got_hi, lo, hi);
+    const float got_lo = vgt::DecodeOrdered(minmax[0]), got_hi = vgt::DecodeOrdered(minmax[1]);
+    if (got_lo != lo || got_hi != hi)
+    {
+      if (failures++ < 10)
+        std::printf("X EXTREMA shape %dx%dx%d resolution %.17g: got (%g, %g) want (%g, %g)\n", nx, ny, nz, resolution, got_lo,
+                    got_hi, lo, hi);
+    }
   }
+}
+
+// Resolutions of the X-pass check: the ordinary 0.37, the edges of the fast conversion's range (1e-30 and 1e30 take the exact
+// conversion, the values just inside them the fast one), subnormal, underflowing and overflowing outputs, near ties of
+// sqrt(d2) * res to a float32 rounding midpoint for small d2 (the fast conversion's re-do), and subnormal near ties on which
+// the fast conversion, run outside its range, rounds differently from the exact one.
+std::vector<double> XResolutions()
+{
+  std::vector<double> out = {0.37, 1.0e-30, std::nextafter(1.0e-30, INFINITY), std::nextafter(1.0e30, 0.0), 1.0e30,
+                             1.0e-42, 1.0e-46, 5.0e-324, 1.7e308};
+  const double overflow = std::ldexp(1.0, 128) - std::ldexp(1.0, 103);  // FLT_MAX + half an ulp: the first value rounded to inf
+  out.push_back(std::nextafter(overflow / 2.0, 0.0));
+  out.push_back(overflow / 2.0);
+  for (const int d2 : {2, 5})
+  {
+    const float f = 7.7f;
+    const double mid = static_cast<double>(f) + static_cast<double>(std::nextafter(f, INFINITY) - f) / 2.0;
+    const double res = mid / std::sqrt(static_cast<double>(d2));
+    out.push_back(std::nextafter(res, 0.0));
+    out.push_back(std::nextafter(res, INFINITY));
+  }
+  int found = 0;
+  for (int d2 = 2; d2 < 64 && found < 4; d2++)
+  {
+    const double mid = 1.5 * std::ldexp(1.0, -149);
+    double res = mid / std::sqrt(static_cast<double>(d2));
+    for (int step = 0; step < 3; step++) res = std::nextafter(res, 0.0);
+    for (int step = 0; step < 7 && found < 4; step++, res = std::nextafter(res, INFINITY))
+    {
+      bool unsure;
+      const float fast = vgt::FastSqrtTimesResolution(static_cast<uint32_t>(d2), res, unsure);
+      if (fast != static_cast<float>(std::sqrt(static_cast<double>(d2)) * res))
+      {
+        out.push_back(res);
+        found++;
+        break;
+      }
+    }
+  }
+  if (found < 4) std::printf("only %d subnormal near ties found\n", found);
+  return out;
 }
 }  // namespace
 
@@ -259,6 +321,7 @@ int main(int argc, char** argv)
 {
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 1;
   std::mt19937 rng(4242);
+  const std::vector<double> x_resolutions = XResolutions();
   int cases = 0;
   for (int round = 0; round < rounds; round++)
   {
@@ -289,8 +352,11 @@ int main(int argc, char** argv)
     };
     for (const Case& c : x_cases)
     {
-      CheckX(c, rng);
-      cases++;
+      // (every resolution in the first round; the later rounds vary the lines at the ordinary one)
+      const std::vector<double> just_one = {x_resolutions[0]};
+      const std::vector<double>& resolutions = (round == 0) ? x_resolutions : just_one;
+      CheckX(c, resolutions, rng);
+      cases += static_cast<int>(resolutions.size());
     }
   }
   std::printf("%d cases, %d mismatches (band %d; 32-bit entries: ring %d, chunk %d; 64-bit entries: ring %d, chunk %d)\n", cases,

@@ -444,7 +444,17 @@ def test_longest_axis(ctx, oracle, shape):
         assert (lo, hi) == (wlo, whi)
 
 
-@pytest.mark.parametrize("resolution", [0.01, 0.25, 1.0, 1.0 / 3.0, 0.1, 0.05, 2.5e-3, 7.0, 1.0e-20, 3.0e25, 1.0e-42])
+def _finalize_edge_resolutions():
+    """The edges of the fast conversion's range and near ties of sqrt(d2) * res to a float32 midpoint (tests/sdf_conversion_ref.py)."""
+    import sdf_conversion_ref as R
+    out = [r.value for r in R.range_edges()]
+    out += [R.near_tie(d2, 7.7, nudge).value for d2 in (2, 1000, (1 << 20) + 3) for nudge in (-1, 1)]
+    out += [R.square_tie(3, True).value, R.subnormal_near_tie(2, 1).value]
+    return out
+
+
+@pytest.mark.parametrize("resolution", [0.01, 0.25, 1.0, 1.0 / 3.0, 0.1, 0.05, 2.5e-3, 7.0, 1.0e-20, 3.0e25, 1.0e-42]
+                         + _finalize_edge_resolutions())
 def test_fast_finalize_matches_exact_for_every_d2(vctx, resolution):
     """The final conversion float(sqrt(double(d2)) * res) (signed_distance_field_generation.hpp:98-105) has a
     fast evaluation with an exact fallback; both are run on the device for EVERY d2 in [0, 2^31)."""
