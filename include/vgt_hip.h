@@ -389,6 +389,52 @@ int vgt_hip_sdf_local_extrema_map(vgt_hip_ctx* ctx, const float* sdf_host, int64
 int vgt_hip_sdf_local_extrema_map_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
                                       double resolution, const double* rotation, double* extrema_dev);
 
+/* ---- connected components, spatial segments and component surfaces of the component map types ----
+ *   OccupancyComponentMap::UpdateConnectedComponents()                        S/occupancy_component_map.cpp:447-509
+ *   TaggedObjectOccupancyComponentMap::UpdateConnectedComponents(across)      S/tagged_object_occupancy_component_map.cpp:689-773
+ *   TaggedObjectOccupancyComponentMap::UpdateSpatialSegments(threshold, p)    same file :775-868
+ * all of which are topology_computation::ComputeConnectedComponents (I/topology_computation.hpp:59-196), a flood fill
+ * over the six face neighbours started from every still-unlabelled cell in X-major / Z-fastest order.  The result is
+ * therefore fully determined: a cell outside the labelling gets 0, every other cell the number of its component, and
+ * components are numbered 1, 2, 3 ... in ascending order of the smallest linear index they contain.  The device
+ * labelling (a union-find whose roots are the smallest index of their set, csrc/component_kernels.hip) returns exactly
+ * these numbers, one uint32 per voxel; *num_components / *num_segments receive the largest label.  Grids below 2^31
+ * cells.  Blocking (the count is read back).  Two face-adjacent cells are connected when
+ *   vgt_hip_connected_components[_dev]   both occupancies are > 0.5, or both < 0.5, or both == 0.5 as floats (a NaN cell
+ *                                        is a component of its own);
+ *   vgt_hip_cells_connected_components   the same and, unless connect_across_objects, their object ids are equal
+ *                                        (cells without object ids: connect_across_objects is ignored);
+ *   vgt_hip_cells_spatial_segments[_dev] only cells with (occupancy < 0.5 or object id > 0) and no infinite component in
+ *                                        their entry of the local-extrema map (vgt_hip_sdf_local_extrema_map, 3 doubles
+ *                                        per voxel) are labelled; two of them are connected when their object ids are
+ *                                        equal and the distance of their entries, evaluated in double as
+ *                                        sqrt((dx*dx + dy*dy) + dz*dz), is < connected_threshold.  Cells with object ids
+ *                                        only.
+ * vgt_hip_cells_update_spatial_segments is UpdateSpatialSegments as one call: with add_virtual_border the field of
+ * vgt_hip_cells_sdf without an object list, otherwise the one of vgt_hip_cells_free_and_named_objects_sdf; its local-
+ * extrema map under `rotation` (9 doubles row-major or NULL); the segments.  Field and map never leave the device. */
+int vgt_hip_connected_components(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx, int64_t ny, int64_t nz,
+                                 uint32_t* labels_host, uint32_t* num_components);
+int vgt_hip_connected_components_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t nx, int64_t ny, int64_t nz,
+                                     uint32_t* labels_dev, uint32_t* num_components);
+int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
+                                       uint32_t* labels_host, uint32_t* num_components);
+int vgt_hip_cells_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const double* extrema_host,
+                                   double connected_threshold, uint32_t* labels_host, uint32_t* num_segments);
+int vgt_hip_cells_spatial_segments_dev(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const double* extrema_dev,
+                                       double connected_threshold, uint32_t* labels_dev, uint32_t* num_segments);
+int vgt_hip_cells_update_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double connected_threshold,
+                                          double resolution, int unknown_is_filled, int add_virtual_border,
+                                          const double* rotation, uint32_t* labels_host, uint32_t* num_segments);
+/* The dense form of ExtractComponentSurfaces (S/occupancy_component_map.cpp:290-350,531-567; the tagged variant
+ * S/tagged_object_occupancy_component_map.cpp:485-541): mask[i] = 1 when the class of cell i is selected by
+ * component_types -- 0x01 filled (> 0.5) | 0x02 empty (< 0.5) | 0x04 unknown (everything else, NaN included) -- and the
+ * cell lies on a face of the grid or one of its six face neighbours has another label; else 0. */
+int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host, const uint32_t* labels_host,
+                                   int64_t nx, int64_t ny, int64_t nz, int component_types, uint8_t* mask_host);
+int vgt_hip_component_surface_mask_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, const uint32_t* labels_dev,
+                                       int64_t nx, int64_t ny, int64_t nz, int component_types, uint8_t* mask_dev);
+
 /* ---- multi-GPU: the grid is cut into Z slabs, one device per slab (BASELINE.json config 5).
  * Lines along Y and X are local to a slab; only the first pass (nearest voxel of the other class
  * along Z) crosses slabs, and all it needs from the other slabs is, per (x, y) line, the nearest

@@ -8,6 +8,7 @@
 //                              (occupancy_map.hpp:174-210).
 #pragma once
 
+#include <array>
 #include <functional>
 #include <map>
 #include <memory>
@@ -128,6 +129,17 @@ Gradients GetIndexCoarseGradients(const SignedDistanceField& sdf, bool enable_ed
 // SignedDistanceField::ComputeLocalExtremaMap (:1205-1231): 3 doubles per voxel.
 std::vector<double> ComputeLocalExtremaMap(const SignedDistanceField& sdf, int hip_device = 0);
 
+// ---- connected components, spatial segments, component surfaces ----
+struct ComponentLabels
+{
+  std::vector<uint32_t> labels;  // one per voxel, X-major / Z fastest; 0 = not labelled
+  uint32_t count = 0;            // the largest label
+};
+// ExtractComponentSurfaces' component_types_to_extract (occupancy_component_map.hpp)
+enum COMPONENT_TYPES : uint8_t { FILLED_COMPONENTS = 0x01, EMPTY_COMPONENTS = 0x02, UNKNOWN_COMPONENTS = 0x04 };
+// component number -> grid indices (x, y, z) of its surface cells, in ascending linear order
+using ComponentSurfaces = std::map<uint32_t, std::vector<std::array<int64_t, 3>>>;
+
 // ---- the other three map types ----
 // OccupancyComponentMap::ExtractSignedDistanceField<float> (occupancy_component_map.hpp:270-306).
 SignedDistanceField ExtractSignedDistanceField(
@@ -157,6 +169,12 @@ public:
       const SignedDistanceFieldGenerationParameters& parameters) const;
   // distinct object ids > 0, ascending
   std::vector<uint32_t> ObjectIds() const;
+  // The labels of UpdateConnectedComponents / UpdateSpatialSegments for the uploaded cells (one uint32 per voxel,
+  // X-major / Z fastest) and their number: the same upload serves fields and labels.  The map itself is not written;
+  // the free functions below do that.  `rotation`: of the map's origin transform (what the extrema map follows).
+  ComponentLabels ConnectedComponents(bool connect_across_objects) const;
+  ComponentLabels SpatialSegments(double connected_threshold,
+                                  const SignedDistanceFieldGenerationParameters& parameters) const;
 
 private:
   void Upload(const void* cells, int cell_bytes, int object_id_offset, int hip_device);
@@ -165,4 +183,24 @@ private:
   ::vgt_hip_cells* cells_ = nullptr;
   DenseGrid shape_;  // origin / frame / sizes of the map, for the fields handed back
 };
+
+// OccupancyComponentMap::UpdateConnectedComponents (occupancy_component_map.cpp:447-509) and
+// TaggedObjectOccupancyComponentMap::UpdateConnectedComponents (tagged_object_occupancy_component_map.cpp:689-773): the
+// cells' `component` members receive the reference's numbers (1, 2, 3 ... in ascending order of the components' smallest
+// linear index); returns their number.  std::invalid_argument for an uninitialised map or one of 2^31 cells and more.
+uint32_t UpdateConnectedComponents(OccupancyComponentMap& map, int hip_device = 0);
+uint32_t UpdateConnectedComponents(TaggedObjectOccupancyComponentMap& map, bool connect_across_objects,
+                                   int hip_device = 0);
+// TaggedObjectOccupancyComponentMap::UpdateSpatialSegments (:775-868) as one device chain (SDF -> local extrema map,
+// rotated by the map's origin transform -> segments); writes the cells' `spatial_segment` members.  Runs on
+// sdf_parameters.hip_device.
+uint32_t UpdateSpatialSegments(TaggedObjectOccupancyComponentMap& map, double connected_threshold,
+                               const SignedDistanceFieldGenerationParameters& sdf_parameters);
+// ExtractComponentSurfaces (occupancy_component_map.cpp:511-571, tagged variant :485-541) from the cells' current
+// `component` members: the device computes the dense mask (vgt_hip_component_surface_mask), the host sorts it into
+// per-component index lists.
+ComponentSurfaces ExtractComponentSurfaces(const OccupancyComponentMap& map, uint8_t component_types,
+                                           int hip_device = 0);
+ComponentSurfaces ExtractComponentSurfaces(const TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
+                                           int hip_device = 0);
 }  // namespace vgt_hip

@@ -395,6 +395,8 @@ public:
     data_[static_cast<size_t>((x * ny_ + y) * nz_ + z)] = value;
   }
   const std::vector<Cell>& GetImmutableRawData() const { return data_; }
+  // (UpdateConnectedComponents / UpdateSpatialSegments write the cells' component / spatial_segment members)
+  std::vector<Cell>& GetMutableRawData() { return data_; }
 
 private:
   Isometry3 origin_;

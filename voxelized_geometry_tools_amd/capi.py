@@ -73,6 +73,14 @@ SIGNATURES = {
     "vgt_hip_sdf_fine_gradient": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _i64, _f64, _p, _p]),
     "vgt_hip_sdf_local_extrema_map": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_sdf_local_extrema_map_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
+    "vgt_hip_connected_components": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    "vgt_hip_connected_components_dev": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    "vgt_hip_cells_connected_components": (_int, [_p, _p, _int, _p, _p]),
+    "vgt_hip_cells_spatial_segments": (_int, [_p, _p, _p, _f64, _p, _p]),
+    "vgt_hip_cells_spatial_segments_dev": (_int, [_p, _p, _p, _f64, _p, _p]),
+    "vgt_hip_cells_update_spatial_segments": (_int, [_p, _p, _f64, _f64, _int, _int, _p, _p, _p]),
+    "vgt_hip_component_surface_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
+    "vgt_hip_component_surface_mask_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
     "vgt_hipx_sdf_multi": (_int, [_p, _int, _p, _i64, _i64, _i64, _f64, _int, _int, _p, _p, _p]),
     "vgt_hipx_release": (None, []),
     "vgt_hipx_last_timing": (_int, [_p]),
@@ -279,6 +287,42 @@ class Context:
         check(self._lib.vgt_hip_sdf_local_extrema_map(self.handle, _ptr(field), *field.shape, float(resolution),
                                                       _ptr(rot), _ptr(out)))
         return out
+
+    def connected_components(self, occupancy):
+        """UpdateConnectedComponents of an occupancy grid: (uint32 labels of the grid's shape, number of components).
+        Components are numbered from 1 in ascending order of the smallest linear index they contain."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.float32)
+        if occ.ndim != 3:
+            raise ValueError("occupancy must be (nx, ny, nz)")
+        labels = np.empty(occ.shape, dtype=np.uint32)
+        count = ctypes.c_uint32(0)
+        check(self._lib.vgt_hip_connected_components(self.handle, _ptr(occ), *occ.shape, _ptr(labels),
+                                                     ctypes.byref(count)))
+        return labels, int(count.value)
+
+    def connected_components_dev(self, occ_ptr, shape, labels_ptr):
+        """vgt_hip_connected_components_dev: device buffers in and out -> number of components."""
+        count = ctypes.c_uint32(0)
+        check(self._lib.vgt_hip_connected_components_dev(self.handle, _ptr(occ_ptr), *[int(v) for v in shape],
+                                                         _ptr(labels_ptr), ctypes.byref(count)))
+        return int(count.value)
+
+    def component_surface_mask(self, occupancy, labels, component_types):
+        """Dense ExtractComponentSurfaces: bool array, True where the cell's class is selected by component_types
+        (1 filled | 2 empty | 4 unknown) and the cell is a surface cell of its component."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.float32)
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if occ.ndim != 3 or lab.shape != occ.shape:
+            raise ValueError("occupancy and labels must be (nx, ny, nz) grids of one shape")
+        mask = np.empty(occ.shape, dtype=np.uint8)
+        check(self._lib.vgt_hip_component_surface_mask(self.handle, _ptr(occ), _ptr(lab), *occ.shape,
+                                                       int(component_types), _ptr(mask)))
+        return mask.astype(bool)
+
+    def component_surface_mask_dev(self, occ_ptr, labels_ptr, shape, component_types, mask_ptr):
+        check(self._lib.vgt_hip_component_surface_mask_dev(self.handle, _ptr(occ_ptr), _ptr(labels_ptr),
+                                                           *[int(v) for v in shape], int(component_types),
+                                                           _ptr(mask_ptr)))
 
     def trim(self):
         """Frees the device buffers the context caches between host-pointer calls."""
@@ -723,3 +767,42 @@ class Cells:
             self.ctx.handle, self.handle, float(resolution), int(bool(unknown_is_filled)),
             int(bool(add_virtual_border)), _ptr(out), ctypes.byref(lo), ctypes.byref(hi)))
         return out, float(lo.value), float(hi.value)
+
+    def connected_components(self, connect_across_objects=False):
+        """UpdateConnectedComponents: (uint32 labels, number of components)."""
+        labels = np.empty(self.shape, dtype=np.uint32)
+        count = ctypes.c_uint32(0)
+        check(self._lib.vgt_hip_cells_connected_components(self.ctx.handle, self.handle,
+                                                           int(bool(connect_across_objects)), _ptr(labels),
+                                                           ctypes.byref(count)))
+        return labels, int(count.value)
+
+    def spatial_segments(self, extrema, threshold):
+        """The labelling step of UpdateSpatialSegments on a given local-extrema map [nx, ny, nz, 3] float64:
+        (uint32 labels, number of segments)."""
+        ext = np.ascontiguousarray(extrema, dtype=np.float64)
+        if ext.shape != self.shape + (3,):
+            raise ValueError("the extrema map must be (nx, ny, nz, 3)")
+        labels = np.empty(self.shape, dtype=np.uint32)
+        count = ctypes.c_uint32(0)
+        check(self._lib.vgt_hip_cells_spatial_segments(self.ctx.handle, self.handle, _ptr(ext), float(threshold),
+                                                       _ptr(labels), ctypes.byref(count)))
+        return labels, int(count.value)
+
+    def spatial_segments_dev(self, extrema_ptr, threshold, labels_ptr):
+        count = ctypes.c_uint32(0)
+        check(self._lib.vgt_hip_cells_spatial_segments_dev(self.ctx.handle, self.handle, _ptr(extrema_ptr),
+                                                           float(threshold), _ptr(labels_ptr), ctypes.byref(count)))
+        return int(count.value)
+
+    def update_spatial_segments(self, threshold, resolution, unknown_is_filled=True, add_virtual_border=False,
+                                rotation=None):
+        """UpdateSpatialSegments in one call (SDF -> local extrema -> segments on the device):
+        (uint32 labels, number of segments)."""
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        labels = np.empty(self.shape, dtype=np.uint32)
+        count = ctypes.c_uint32(0)
+        check(self._lib.vgt_hip_cells_update_spatial_segments(
+            self.ctx.handle, self.handle, float(threshold), float(resolution), int(bool(unknown_is_filled)),
+            int(bool(add_virtual_border)), _ptr(rot), _ptr(labels), ctypes.byref(count)))
+        return labels, int(count.value)

@@ -1,0 +1,430 @@
+// Connected components and spatial segments of voxel maps (the reference's one generic routine,
+// topology_computation::ComputeConnectedComponents, I/topology_computation.hpp:59-196, under the three predicates of
+//   OccupancyComponentMap::UpdateConnectedComponents                  S/occupancy_component_map.cpp:447-509
+//   TaggedObjectOccupancyComponentMap::UpdateConnectedComponents      S/tagged_object_occupancy_component_map.cpp:689-773
+//   TaggedObjectOccupancyComponentMap::UpdateSpatialSegments          same file :775-868)
+// and the dense component-surface mask (S/occupancy_component_map.cpp:290-350,531-567).
+//
+// The reference floods from every still-unlabelled cell in X-major / Z-fastest order, so its components are numbered
+// 1, 2, 3 ... in ascending order of the smallest linear index they contain.  Here the labelling is a union-find over
+// int32 labels in which a parent is ALWAYS SMALLER than its child -- the root of a set is its smallest linear index --
+// so that numbering is the rank of the root among all roots, whatever order the atomics land in:
+//   1. InitRuns    one lane per cell, a wave holds 64 consecutive cells of the linear order (Z is the fastest axis).
+//                  Each lane evaluates connected(i - 1, i) with the data of the lane below (shuffles, no second load);
+//                  one ballot gives the wave its run boundaries, and a lane's first label is the start of its run.
+//                  Inactive cells (spatial segments only) get -1 and never take part in a union.
+//   2. MergeEdges  one lane per cell: the run that continues across the wave's first lane, the -Y and the -X edge.
+//                  Lock-free union on roots: atomicMin(&label[larger root], smaller root), retried with what the atomic
+//                  returned while someone else moved the root first; every retry strictly lowers an index, so the loop
+//                  is bounded.  A lane whose edge joins the same two runs as the edge one cell below it skips.
+//   3. FlattenCount every cell -> its root (in place), roots counted per block of kScanBlockCells cells.
+//   4. ScanBlocks  exclusive scan of the block counts by one workgroup; the total is the number of components.
+//   5. RankRoots   rank of every root inside its block + the block's offset -> out[root] = rank + 1.
+//   6. Relabel     out[i] = out[root(i)], 0 for inactive cells.
+// (The issue that asked for this suggested an LDS tile merge between 1 and 2; it is not here: see DESIGN.md.)
+#include "vgt_internal.hpp"
+
+namespace vgt
+{
+namespace
+{
+constexpr int kBlock = 256;
+constexpr int kCellsPerThread = 4;
+constexpr int kScanBlockCells = kBlock * kCellsPerThread;  // cells per block count of the scan
+constexpr int kScanThreads = 1024;
+
+// What a predicate needs to know of one cell.
+//  occupancy classes (kClasses / kClassesAndIds): cls 0 = > 0.5, 1 = < 0.5, 2 = == 0.5, 3 = none of them (NaN: connects
+//  to nothing); id = the object id (0 when the predicate ignores ids)
+//  spatial segments: cls 1 = active, 0 = not; id = object id; e = the cell's entry of the local-extrema map
+struct CellKey
+{
+  uint32_t cls, id;
+};
+
+__device__ __forceinline__ uint32_t OccupancyClass(float occupancy)
+{
+  return occupancy > 0.5f ? 0u : (occupancy < 0.5f ? 1u : (occupancy == 0.5f ? 2u : 3u));
+}
+
+struct View
+{
+  const uint8_t* cells;  // records of cell_bytes bytes, float occupancy first
+  int cell_bytes;
+  int id_offset;         // < 0: ids are not looked at
+  const double* extrema; // spatial segments only: 3 doubles per cell
+  double threshold;
+};
+
+template <int kMode>
+__device__ __forceinline__ CellKey LoadKey(const View& v, int64_t i, double e[3])
+{
+  const uint8_t* rec = v.cells + i * v.cell_bytes;
+  const float occupancy = *reinterpret_cast<const float*>(rec);
+  CellKey k;
+  k.id = v.id_offset >= 0 ? *reinterpret_cast<const uint32_t*>(rec + v.id_offset) : 0u;
+  if (kMode == kComponentSegments)
+  {
+    e[0] = v.extrema[3 * i];
+    e[1] = v.extrema[3 * i + 1];
+    e[2] = v.extrema[3 * i + 2];
+    // S/tagged_object_occupancy_component_map.cpp:828-841
+    k.cls = ((occupancy < 0.5f) || (k.id > 0u)) && !isinf(e[0]) && !isinf(e[1]) && !isinf(e[2]) ? 1u : 0u;
+  }
+  else
+    k.cls = OccupancyClass(occupancy);
+  return k;
+}
+
+// connected(a, b) for two face-adjacent cells.  Spatial segments: the Euclidean distance of the two extrema in double as
+// sqrt((dx*dx + dy*dy) + dz*dz) (Eigen's norm() of the difference; the library is built with -ffp-contract=off), which must
+// be < threshold; NaN compares false.
+template <int kMode>
+__device__ __forceinline__ bool Connected(const View& v, const CellKey& a, const double ea[3], const CellKey& b,
+                                          const double eb[3])
+{
+  if (kMode == kComponentSegments)
+  {
+    if (!(a.cls & b.cls) || a.id != b.id) return false;
+    const double dx = ea[0] - eb[0], dy = ea[1] - eb[1], dz = ea[2] - eb[2];
+    return sqrt((dx * dx + dy * dy) + dz * dz) < v.threshold;
+  }
+  return a.cls == b.cls && a.cls != 3u && a.id == b.id;
+}
+
+__device__ __forceinline__ double ShuffleUpDouble(double value)
+{
+  const unsigned long long bits = __double_as_longlong(value);
+  const int lo = __shfl_up(static_cast<int>(bits & 0xffffffffu), 1);
+  const int hi = __shfl_up(static_cast<int>(bits >> 32), 1);
+  return __longlong_as_double((static_cast<unsigned long long>(static_cast<unsigned>(hi)) << 32) |
+                              static_cast<unsigned>(lo));
+}
+
+// The key (and extrema) of the lane below; lane 0 gets garbage and must not use it.
+template <int kMode>
+__device__ __forceinline__ CellKey KeyOfLaneBelow(const CellKey& k, const double e[3], double below[3])
+{
+  CellKey p;
+  p.cls = static_cast<uint32_t>(__shfl_up(static_cast<int>(k.cls), 1));
+  p.id = static_cast<uint32_t>(__shfl_up(static_cast<int>(k.id), 1));
+  if (kMode == kComponentSegments)
+    for (int a = 0; a < 3; a++) below[a] = ShuffleUpDouble(e[a]);
+  return p;
+}
+
+template <int kMode>
+__global__ __launch_bounds__(kBlock) void InitRunsKernel(View v, int64_t total, int nz, int32_t* __restrict__ label)
+{
+  // (whole waves run: the shuffles and the ballot need every lane; lanes past the end hold nothing)
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool inside = i < total;
+  double e[3] = {0.0, 0.0, 0.0}, below[3] = {0.0, 0.0, 0.0};
+  CellKey k{3u, 0u};
+  if (inside) k = LoadKey<kMode>(v, i, e);
+  const CellKey p = KeyOfLaneBelow<kMode>(k, e, below);
+  const bool continues = inside && lane > 0 && (i % nz) != 0 && Connected<kMode>(v, p, below, k, e);
+  const unsigned long long starts = __ballot(!continues);
+  if (!inside) return;
+  // start of the lane's run: the highest start bit at or below the lane (lane 0 always starts one)
+  const unsigned long long at_or_below = starts & (~0ull >> (63 - lane));
+  const int start_lane = 63 - __clzll(static_cast<long long>(at_or_below));
+  const bool active = kMode != kComponentSegments || k.cls != 0u;
+  label[i] = active ? static_cast<int32_t>(i - lane + start_lane) : -1;
+}
+
+__device__ __forceinline__ int32_t LoadLabel(const int32_t* label, int32_t i)
+{
+  return __atomic_load_n(label + i, __ATOMIC_RELAXED);
+}
+
+__device__ __forceinline__ int32_t FindRoot(const int32_t* label, int32_t a)
+{
+  // parents are smaller than their children: the walk strictly descends and ends at the set's smallest index.  A stale
+  // read yields an earlier parent -- still an ancestor
+  for (int32_t p = LoadLabel(label, a); p != a; p = LoadLabel(label, a)) a = p;
+  return a;
+}
+
+__device__ __forceinline__ void Union(int32_t* label, int32_t a, int32_t b)
+{
+  for (;;)
+  {
+    a = FindRoot(label, a);
+    b = FindRoot(label, b);
+    if (a == b) return;
+    if (a < b)
+    {
+      const int32_t t = a;
+      a = b;
+      b = t;
+    }
+    // a > b: hang a below b.  If a was no root any more, label[a] is now min(old, b) and old (< a) still has to be
+    // joined with b: go on with it.
+    const int32_t old = atomicMin(label + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+template <int kMode>
+__global__ __launch_bounds__(kBlock) void MergeEdgesKernel(View v, int64_t total, int ny, int nz, int32_t* label)
+{
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool inside = i < total;
+  const int64_t line = inside ? i / nz : 0;
+  const int z = static_cast<int>(inside ? i - line * nz : 0);
+  const int y = static_cast<int>(line % ny);
+  const int64_t x = line / ny;
+  double e[3] = {0.0, 0.0, 0.0}, ey[3] = {0.0, 0.0, 0.0}, ex[3] = {0.0, 0.0, 0.0}, eb[3] = {0.0, 0.0, 0.0};
+  CellKey k{3u, 0u}, ky{3u, 0u}, kx{3u, 0u};
+  if (inside) k = LoadKey<kMode>(v, i, e);
+  const bool has_y = inside && y > 0, has_x = inside && x > 0;
+  const int64_t iy = i - nz, ix = i - static_cast<int64_t>(ny) * nz;
+  if (has_y) ky = LoadKey<kMode>(v, iy, ey);
+  if (has_x) kx = LoadKey<kMode>(v, ix, ex);
+  const bool join_y = has_y && Connected<kMode>(v, ky, ey, k, e);
+  const bool join_x = has_x && Connected<kMode>(v, kx, ex, k, e);
+  bool skip_y = false, skip_x = false;
+  if (kMode != kComponentSegments)
+  {
+    // the edge one cell below (same lines: z > 0, same wave: lane > 0) joins the same two runs when it is connected too
+    // and both cells continue the runs of the cells below them
+    const CellKey pk = KeyOfLaneBelow<kMode>(k, e, eb), pky = KeyOfLaneBelow<kMode>(ky, ey, eb),
+                  pkx = KeyOfLaneBelow<kMode>(kx, ex, eb);
+    const bool below_join_y = __shfl_up(static_cast<int>(join_y), 1) != 0;
+    const bool below_join_x = __shfl_up(static_cast<int>(join_x), 1) != 0;
+    const bool same_wave_line = lane > 0 && z > 0;
+    const bool continues = same_wave_line && Connected<kMode>(v, pk, eb, k, e);
+    skip_y = continues && below_join_y && Connected<kMode>(v, pky, eb, ky, ey);
+    skip_x = continues && below_join_x && Connected<kMode>(v, pkx, eb, kx, ex);
+  }
+  if (!inside) return;
+  if (lane == 0 && z > 0)
+  {
+    // a run that crosses into this wave
+    double ep[3] = {0.0, 0.0, 0.0};
+    const CellKey kp = LoadKey<kMode>(v, i - 1, ep);
+    if (Connected<kMode>(v, kp, ep, k, e)) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(i - 1));
+  }
+  if (join_y && !skip_y) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(iy));
+  if (join_x && !skip_x) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(ix));
+}
+
+// Inclusive prefix sum over the lanes of a wave.
+__device__ __forceinline__ int WaveInclusiveScan(int value, int lane)
+{
+  for (int d = 1; d < 64; d <<= 1)
+  {
+    const int other = __shfl_up(value, d);
+    if (lane >= d) value += other;
+  }
+  return value;
+}
+
+// every cell -> its root; block_roots[b] = roots among the kScanBlockCells cells of block b
+__global__ __launch_bounds__(kBlock) void FlattenCountKernel(int64_t total, int32_t* label,
+                                                             int32_t* __restrict__ block_roots)
+{
+  __shared__ int wave_sum[kBlock / 64];
+  const int64_t first = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * kCellsPerThread;
+  int roots = 0;
+  for (int c = 0; c < kCellsPerThread; c++)
+  {
+    const int64_t i = first + c;
+    if (i >= total) break;
+    const int32_t parent = LoadLabel(label, static_cast<int32_t>(i));
+    if (parent < 0) continue;
+    if (parent == i)
+    {
+      roots++;
+      continue;
+    }
+    // (roots do not move in this kernel; writing a root over a parent keeps every concurrent walk valid)
+    label[i] = FindRoot(label, parent);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int scanned = WaveInclusiveScan(roots, lane);
+  if (lane == 63) wave_sum[wave] = scanned;
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    int sum = 0;
+    for (int w = 0; w < kBlock / 64; w++) sum += wave_sum[w];
+    block_roots[blockIdx.x] = sum;
+  }
+}
+
+// block_roots[b] -> exclusive prefix sum in place, *count = the total.  One workgroup.
+__global__ __launch_bounds__(kScanThreads) void ScanBlocksKernel(int32_t* __restrict__ block_roots, int64_t blocks,
+                                                                 uint32_t* __restrict__ count)
+{
+  __shared__ int wave_sum[kScanThreads / 64];
+  const int64_t chunk = (blocks + kScanThreads - 1) / kScanThreads;
+  const int64_t begin = threadIdx.x * chunk;
+  const int64_t end = begin + chunk < blocks ? begin + chunk : blocks;
+  int sum = 0;
+  for (int64_t b = begin; b < end; b++) sum += block_roots[b];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int scanned = WaveInclusiveScan(sum, lane);
+  if (lane == 63) wave_sum[wave] = scanned;
+  __syncthreads();
+  int offset = scanned - sum;
+  for (int w = 0; w < wave; w++) offset += wave_sum[w];
+  for (int64_t b = begin; b < end; b++)
+  {
+    const int here = block_roots[b];
+    block_roots[b] = offset;
+    offset += here;
+  }
+  if (threadIdx.x == kScanThreads - 1) *count = static_cast<uint32_t>(offset);
+}
+
+// out[root] = 1 + number of roots with a smaller linear index
+__global__ __launch_bounds__(kBlock) void RankRootsKernel(int64_t total, const int32_t* __restrict__ label,
+                                                          const int32_t* __restrict__ block_offset,
+                                                          uint32_t* __restrict__ out)
+{
+  __shared__ int wave_sum[kBlock / 64];
+  const int64_t first = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * kCellsPerThread;
+  bool root[kCellsPerThread];
+  int roots = 0;
+  for (int c = 0; c < kCellsPerThread; c++)
+  {
+    const int64_t i = first + c;
+    root[c] = i < total && label[i] == i;
+    roots += root[c] ? 1 : 0;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int scanned = WaveInclusiveScan(roots, lane);
+  if (lane == 63) wave_sum[wave] = scanned;
+  __syncthreads();
+  int rank = block_offset[blockIdx.x] + scanned - roots;
+  for (int w = 0; w < wave; w++) rank += wave_sum[w];
+  for (int c = 0; c < kCellsPerThread; c++)
+    if (root[c]) out[first + c] = static_cast<uint32_t>(++rank);
+}
+
+__global__ __launch_bounds__(kBlock) void RelabelKernel(int64_t total, const int32_t* __restrict__ label,
+                                                        uint32_t* out)
+{
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= total) return;
+  const int32_t root = label[i];
+  if (root < 0)
+    out[i] = 0u;
+  else if (root != i)
+    out[i] = out[root];  // (written by RankRootsKernel; this kernel writes no root's entry)
+}
+
+// One byte per voxel: the cell's class is selected by `types` (S/occupancy_component_map.cpp:536-565: whatever is
+// neither > 0.5 nor < 0.5 is "unknown", NaN included) and the cell lies on a face of the grid or one of its SIX face
+// neighbours carries another label (:302-349).
+__global__ __launch_bounds__(kBlock) void SurfaceMaskKernel(const float* __restrict__ occupancy,
+                                                           const uint32_t* __restrict__ labels, int nx, int ny, int nz,
+                                                           int types, uint8_t* __restrict__ mask)
+{
+  const int64_t total = static_cast<int64_t>(nx) * ny * nz;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= total) return;
+  const int64_t line = i / nz;
+  const int z = static_cast<int>(i - line * nz);
+  const int y = static_cast<int>(line % ny);
+  const int x = static_cast<int>(line / ny);
+  const float o = occupancy[i];
+  const int bit = o > 0.5f ? 1 : (o < 0.5f ? 2 : 4);
+  bool surface = false;
+  if (types & bit)
+  {
+    surface = x == 0 || y == 0 || z == 0 || x == nx - 1 || y == ny - 1 || z == nz - 1;
+    if (!surface)
+    {
+      const uint32_t own = labels[i];
+      const int64_t sy = nz, sx = static_cast<int64_t>(ny) * nz;
+      surface = labels[i - 1] != own || labels[i + 1] != own || labels[i - sy] != own || labels[i + sy] != own ||
+                labels[i - sx] != own || labels[i + sx] != own;
+    }
+  }
+  mask[i] = surface ? 1 : 0;
+}
+
+unsigned Blocks(int64_t items, int per_block) { return static_cast<unsigned>((items + per_block - 1) / per_block); }
+
+struct ScratchLayout
+{
+  size_t labels, block_roots, count, bytes;
+};
+ScratchLayout CarveScratch(int64_t num_cells)
+{
+  const auto align = [](size_t v) { return (v + 255) / 256 * 256; };
+  ScratchLayout s;
+  s.labels = 0;
+  s.block_roots = align(static_cast<size_t>(num_cells) * sizeof(int32_t));
+  s.count = s.block_roots + align(static_cast<size_t>(Blocks(num_cells, kScanBlockCells)) * sizeof(int32_t));
+  s.bytes = s.count + 256;
+  return s;
+}
+
+template <int kMode>
+hipError_t Label(const View& v, int64_t nx, int64_t ny, int64_t nz, uint32_t* labels_dev, void* scratch_dev,
+                 hipStream_t stream)
+{
+  const int64_t total = nx * ny * nz;
+  const ScratchLayout s = CarveScratch(total);
+  char* const base = static_cast<char*>(scratch_dev);
+  int32_t* const label = reinterpret_cast<int32_t*>(base + s.labels);
+  int32_t* const block_roots = reinterpret_cast<int32_t*>(base + s.block_roots);
+  uint32_t* const count = reinterpret_cast<uint32_t*>(base + s.count);
+  const unsigned cell_blocks = Blocks(total, kBlock), scan_blocks = Blocks(total, kScanBlockCells);
+  InitRunsKernel<kMode><<<cell_blocks, kBlock, 0, stream>>>(v, total, static_cast<int>(nz), label);
+  MergeEdgesKernel<kMode><<<cell_blocks, kBlock, 0, stream>>>(v, total, static_cast<int>(ny), static_cast<int>(nz),
+                                                              label);
+  FlattenCountKernel<<<scan_blocks, kBlock, 0, stream>>>(total, label, block_roots);
+  ScanBlocksKernel<<<1, kScanThreads, 0, stream>>>(block_roots, static_cast<int64_t>(scan_blocks), count);
+  RankRootsKernel<<<scan_blocks, kBlock, 0, stream>>>(total, label, block_roots, labels_dev);
+  RelabelKernel<<<cell_blocks, kBlock, 0, stream>>>(total, label, labels_dev);
+  return hipGetLastError();
+}
+}  // namespace
+
+size_t ComponentScratchBytes(int64_t num_cells) { return num_cells > 0 ? CarveScratch(num_cells).bytes : 0; }
+
+const uint32_t* ComponentCountPtr(const void* scratch_dev, int64_t num_cells)
+{
+  return reinterpret_cast<const uint32_t*>(static_cast<const char*>(scratch_dev) + CarveScratch(num_cells).count);
+}
+
+hipError_t LaunchLabelComponents(const void* cells_dev, int cell_bytes, int object_id_offset, int mode,
+                                 const double* extrema_dev, double connected_threshold, int64_t nx, int64_t ny,
+                                 int64_t nz, uint32_t* labels_dev, void* scratch_dev, hipStream_t stream)
+{
+  View v;
+  v.cells = static_cast<const uint8_t*>(cells_dev);
+  v.cell_bytes = cell_bytes;
+  v.id_offset = mode == kComponentClasses ? -1 : object_id_offset;
+  v.extrema = extrema_dev;
+  v.threshold = connected_threshold;
+  switch (mode)
+  {
+    case kComponentClasses:
+    case kComponentClassesAndIds:
+      // (one kernel for both: without ids every key carries id 0)
+      return Label<kComponentClasses>(v, nx, ny, nz, labels_dev, scratch_dev, stream);
+    case kComponentSegments:
+      return Label<kComponentSegments>(v, nx, ny, nz, labels_dev, scratch_dev, stream);
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+hipError_t LaunchComponentSurfaceMask(const float* occupancy_dev, const uint32_t* labels_dev, int64_t nx, int64_t ny,
+                                      int64_t nz, int component_types, uint8_t* mask_dev, hipStream_t stream)
+{
+  SurfaceMaskKernel<<<Blocks(nx * ny * nz, kBlock), kBlock, 0, stream>>>(
+      occupancy_dev, labels_dev, static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz), component_types,
+      mask_dev);
+  return hipGetLastError();
+}
+}  // namespace vgt

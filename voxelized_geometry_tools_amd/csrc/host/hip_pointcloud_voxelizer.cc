@@ -642,4 +642,110 @@ SignedDistanceField DeviceTaggedObjectMap::ExtractFreeAndNamedObjectsSignedDista
   sdf.locked = true;
   return sdf;
 }
+
+// ---- connected components, spatial segments, component surfaces ----
+
+ComponentLabels DeviceTaggedObjectMap::ConnectedComponents(bool connect_across_objects) const
+{
+  ComponentLabels out;
+  out.labels.resize(static_cast<size_t>(shape_.NumTotalVoxels()));
+  const int rc = vgt_hip_cells_connected_components(ctx_, cells_, connect_across_objects ? 1 : 0, out.labels.data(),
+                                                    &out.count);
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
+  return out;
+}
+
+ComponentLabels DeviceTaggedObjectMap::SpatialSegments(double connected_threshold,
+                                                       const SignedDistanceFieldGenerationParameters& parameters) const
+{
+  ComponentLabels out;
+  out.labels.resize(static_cast<size_t>(shape_.NumTotalVoxels()));
+  const std::array<double, 9> rotation = RotationOf(shape_.OriginTransform());
+  const int rc = vgt_hip_cells_update_spatial_segments(
+      ctx_, cells_, connected_threshold, shape_.Resolution(), parameters.unknown_is_filled ? 1 : 0,
+      parameters.add_virtual_border ? 1 : 0, rotation.data(), out.labels.data(), &out.count);
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
+  return out;
+}
+
+uint32_t UpdateConnectedComponents(OccupancyComponentMap& map, int hip_device)
+{
+  if (!map.IsInitialized()) throw std::invalid_argument("Grid must be initialized");
+  vgt_hip_ctx* ctx = SharedSdfContext(hip_device);
+  vgt_hip_cells* cells = nullptr;
+  int rc = vgt_hip_cells_create(ctx, map.GetImmutableRawData().data(), map.NumXVoxels(), map.NumYVoxels(),
+                                map.NumZVoxels(), static_cast<int32_t>(sizeof(OccupancyComponentCell)), -1, &cells);
+  std::vector<uint32_t> labels(map.GetImmutableRawData().size());
+  uint32_t count = 0;
+  if (rc == VGT_HIP_OK) rc = vgt_hip_cells_connected_components(ctx, cells, 0, labels.data(), &count);
+  const std::string msg = (rc == VGT_HIP_OK) ? std::string() : std::string(vgt_hip_last_error());
+  vgt_hip_cells_destroy(cells);
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, msg);
+  std::vector<OccupancyComponentCell>& data = map.GetMutableRawData();
+  for (size_t i = 0; i < data.size(); i++) data[i].component = labels[i];
+  return count;
+}
+
+uint32_t UpdateConnectedComponents(TaggedObjectOccupancyComponentMap& map, bool connect_across_objects, int hip_device)
+{
+  const ComponentLabels result = DeviceTaggedObjectMap(map, hip_device).ConnectedComponents(connect_across_objects);
+  std::vector<TaggedObjectOccupancyComponentCell>& data = map.GetMutableRawData();
+  for (size_t i = 0; i < data.size(); i++) data[i].component = result.labels[i];
+  return result.count;
+}
+
+uint32_t UpdateSpatialSegments(TaggedObjectOccupancyComponentMap& map, double connected_threshold,
+                               const SignedDistanceFieldGenerationParameters& sdf_parameters)
+{
+  if (!(connected_threshold >= 0.0)) throw std::invalid_argument("the connected threshold must be a number >= 0");
+  const ComponentLabels result =
+      DeviceTaggedObjectMap(map, sdf_parameters.hip_device).SpatialSegments(connected_threshold, sdf_parameters);
+  std::vector<TaggedObjectOccupancyComponentCell>& data = map.GetMutableRawData();
+  for (size_t i = 0; i < data.size(); i++) data[i].spatial_segment = result.labels[i];
+  return result.count;
+}
+
+namespace
+{
+template <typename Cell>
+ComponentSurfaces ExtractSurfaces(const CellGrid<Cell>& map, uint8_t component_types, int hip_device)
+{
+  if (!map.IsInitialized()) throw std::invalid_argument("Grid must be initialized");
+  if (component_types < 1 || component_types > 7)
+    throw std::invalid_argument("component types must be a combination of FILLED_, EMPTY_ and UNKNOWN_COMPONENTS");
+  const std::vector<Cell>& data = map.GetImmutableRawData();
+  std::vector<float> occupancy(data.size());
+  std::vector<uint32_t> labels(data.size());
+  for (size_t i = 0; i < data.size(); i++)
+  {
+    occupancy[i] = data[i].occupancy;
+    labels[i] = data[i].component;
+  }
+  std::vector<uint8_t> mask(data.size());
+  const int rc = vgt_hip_component_surface_mask(SharedSdfContext(hip_device), occupancy.data(), labels.data(),
+                                                map.NumXVoxels(), map.NumYVoxels(), map.NumZVoxels(), component_types,
+                                                mask.data());
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
+  ComponentSurfaces surfaces;
+  const int64_t ny = map.NumYVoxels(), nz = map.NumZVoxels();
+  for (size_t i = 0; i < mask.size(); i++)
+    if (mask[i])
+    {
+      const int64_t index = static_cast<int64_t>(i);
+      surfaces[labels[i]].push_back({index / (ny * nz), (index / nz) % ny, index % nz});
+    }
+  return surfaces;
+}
+}  // namespace
+
+ComponentSurfaces ExtractComponentSurfaces(const OccupancyComponentMap& map, uint8_t component_types, int hip_device)
+{
+  return ExtractSurfaces(map, component_types, hip_device);
+}
+
+ComponentSurfaces ExtractComponentSurfaces(const TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
+                                           int hip_device)
+{
+  return ExtractSurfaces(map, component_types, hip_device);
+}
 }  // namespace vgt_hip

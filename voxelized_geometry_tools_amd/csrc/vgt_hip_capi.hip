@@ -70,6 +70,9 @@ struct vgt_hip_ctx
   size_t sdf_out_bytes = 0;
   void* sdf_ws = nullptr;
   size_t sdf_ws_bytes = 0;
+  // Scratch of the component labelling (union-find labels + scan counts), kept like the buffers above
+  void* component_ws = nullptr;
+  size_t component_ws_bytes = 0;
   // Page-locked staging ring of the batched downloads (DownloadToHostArrays): kStagingSlots slots of kStagingSlotBytes,
   // allocated by the first such call, kept until vgt_hip_trim / vgt_hip_destroy; one event per slot.
   void* host_staging = nullptr;
@@ -254,12 +257,12 @@ hipError_t Reserve(void** ptr, size_t* have, size_t need)
 
 void FreeCachedSdfBuffers(vgt_hip_ctx* ctx)
 {
-  for (void** p : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch})
+  for (void** p : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws})
   {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  ctx->sdf_in_bytes = ctx->sdf_out_bytes = ctx->sdf_ws_bytes = ctx->ray_scratch_bytes = 0;
+  ctx->sdf_in_bytes = ctx->sdf_out_bytes = ctx->sdf_ws_bytes = ctx->ray_scratch_bytes = ctx->component_ws_bytes = 0;
   if (ctx->host_staging) (void)hipHostFree(ctx->host_staging);
   ctx->host_staging = nullptr;
   for (hipEvent_t e : ctx->staging_events)
@@ -2293,6 +2296,28 @@ int vgt_hip_cells_object_sdfs(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint
   return VGT_HIP_OK;
 }
 
+namespace
+{
+// ExtractFreeAndNamedObjectsSignedDistanceField into cells->sdf (extrema in ctx->minmax_out); cells->sdf_named exists.
+// Caller holds the context mutex.
+int RunFreeAndNamedSdf(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const vgt::SdfParams& p)
+{
+  const int64_t n = cells->nx * cells->ny * cells->nz;
+  int rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf);                      // free-space field: every filled cell
+  if (rc == VGT_HIP_OK) rc = RunCellsSdf(ctx, cells, 2, 0, p, cells->sdf_named);  // cells of named objects only
+  if (rc == VGT_HIP_OK)
+  {
+    uint32_t* enc = CarveWorkspace(cells->workspace, cells->nx, cells->ny, cells->nz, ctx->variant).minmax_enc;
+    hipError_t err = vgt::LaunchInitMinMax(enc, ctx->stream);
+    if (err == hipSuccess)
+      err = vgt::LaunchCombineFreeAndNamed(cells->sdf, cells->sdf_named, n, cells->sdf, enc, ctx->stream);
+    if (err == hipSuccess) err = vgt::LaunchDecodeMinMax(enc, ctx->minmax_out, ctx->stream);
+    if (err != hipSuccess) rc = FailHip("combine fields", err);
+  }
+  return rc;
+}
+}  // namespace
+
 int vgt_hip_cells_free_and_named_objects_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double resolution,
                                              int unknown_is_filled, int add_virtual_border, float* sdf_host,
                                              float* out_min, float* out_max)
@@ -2312,17 +2337,7 @@ int vgt_hip_cells_free_and_named_objects_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* ce
                 "allocate second SDF");
   const vgt::SdfParams p{cells->nx, cells->ny, cells->nz, resolution, unknown_is_filled ? 1 : 0,
                          add_virtual_border ? 1 : 0};
-  rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf);                      // free-space field: every filled cell
-  if (rc == VGT_HIP_OK) rc = RunCellsSdf(ctx, cells, 2, 0, p, cells->sdf_named);  // cells of named objects only
-  if (rc == VGT_HIP_OK)
-  {
-    uint32_t* enc = CarveWorkspace(cells->workspace, cells->nx, cells->ny, cells->nz, ctx->variant).minmax_enc;
-    hipError_t err = vgt::LaunchInitMinMax(enc, ctx->stream);
-    if (err == hipSuccess)
-      err = vgt::LaunchCombineFreeAndNamed(cells->sdf, cells->sdf_named, n, cells->sdf, enc, ctx->stream);
-    if (err == hipSuccess) err = vgt::LaunchDecodeMinMax(enc, ctx->minmax_out, ctx->stream);
-    if (err != hipSuccess) rc = FailHip("combine fields", err);
-  }
+  rc = RunFreeAndNamedSdf(ctx, cells, p);
   if (rc != VGT_HIP_OK)
   {
     (void)hipStreamSynchronize(ctx->stream);
@@ -2555,6 +2570,292 @@ int vgt_hip_sdf_local_extrema_map(vgt_hip_ctx* ctx, const float* sdf_host, int64
   if (out_dev) (void)hipFree(out_dev);
   if (result != VGT_HIP_OK) return result;
   VGT_TRY_HIP(err, "local extrema map");
+  return VGT_HIP_OK;
+}
+
+/* ------------------- connected components and spatial segments ------------------- */
+
+namespace
+{
+int CheckComponentGrid(int64_t nx, int64_t ny, int64_t nz)
+{
+  if (nx <= 0 || ny <= 0 || nz <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must be positive");
+  constexpr int64_t kLimit = 0x7fffffffLL;
+  if (nx >= kLimit || ny >= kLimit || nz >= kLimit || nx * ny >= kLimit || nx * ny * nz >= kLimit)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component labelling supports grids below 2^31 cells");
+  return VGT_HIP_OK;
+}
+
+int CheckThreshold(double connected_threshold)
+{
+  if (!(connected_threshold >= 0.0))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the connected threshold must be a number >= 0");
+  return VGT_HIP_OK;
+}
+
+int CheckSegmentCells(const vgt_hip_ctx* ctx, const vgt_hip_cells* cells)
+{
+  const int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (cells->object_id_offset < 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "this cell type carries no object id: it has no spatial segments");
+  return CheckComponentGrid(cells->nx, cells->ny, cells->nz);
+}
+
+// Labels the grid on the context's stream into labels_dev and waits for the number of components.
+// Caller holds the context mutex and has set the device.
+int RunLabelling(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int object_id_offset, int mode,
+                 const double* extrema_dev, double connected_threshold, int64_t nx, int64_t ny, int64_t nz,
+                 uint32_t* labels_dev, uint32_t* num_components)
+{
+  const int64_t n = nx * ny * nz;
+  const size_t need = vgt::ComponentScratchBytes(n);
+  if (need > ctx->component_ws_bytes)
+  {
+    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the labelling scratch");
+    VGT_TRY_HIP(Reserve(&ctx->component_ws, &ctx->component_ws_bytes, need), "allocate labelling scratch");
+  }
+  hipError_t err = vgt::LaunchLabelComponents(cells_dev, cell_bytes, object_id_offset, mode, extrema_dev,
+                                              connected_threshold, nx, ny, nz, labels_dev, ctx->component_ws,
+                                              ctx->stream);
+  uint32_t count = 0;
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&count, vgt::ComponentCountPtr(ctx->component_ws, n), sizeof(count), hipMemcpyDeviceToHost,
+                         ctx->stream);
+  const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (`count` is on this stack)
+  if (err == hipSuccess) err = sync;
+  VGT_TRY_HIP(err, "label components");
+  *num_components = count;
+  return VGT_HIP_OK;
+}
+
+// RunLabelling into a temporary device grid, then the labels to the host.
+int LabelToHost(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int object_id_offset, int mode,
+                const double* extrema_dev, double connected_threshold, int64_t nx, int64_t ny, int64_t nz,
+                uint32_t* labels_host, uint32_t* num_components)
+{
+  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(uint32_t);
+  uint32_t* labels_dev = nullptr;
+  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&labels_dev), bytes), "allocate labels");
+  int rc;
+  hipError_t err = hipSuccess;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, extrema_dev, connected_threshold, nx, ny, nz,
+                      labels_dev, num_components);
+    if (rc == VGT_HIP_OK)
+    {
+      err = hipMemcpyAsync(labels_host, labels_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+      const hipError_t sync = hipStreamSynchronize(ctx->stream);
+      if (err == hipSuccess) err = sync;
+    }
+  }
+  (void)hipFree(labels_dev);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(err, "copy labels to the host");
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+int vgt_hip_connected_components_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t nx, int64_t ny, int64_t nz,
+                                     uint32_t* labels_dev, uint32_t* num_components)
+{
+  const int rc = CheckComponentGrid(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!ctx || !occupancy_dev || !labels_dev || !num_components)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunLabelling(ctx, occupancy_dev, 4, -1, vgt::kComponentClasses, nullptr, 0.0, nx, ny, nz, labels_dev,
+                      num_components);
+}
+
+int vgt_hip_connected_components(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx, int64_t ny, int64_t nz,
+                                 uint32_t* labels_host, uint32_t* num_components)
+{
+  const int rc = CheckComponentGrid(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!ctx || !occupancy_host || !labels_host || !num_components)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(float);
+  float* occupancy_dev = nullptr;
+  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&occupancy_dev), bytes), "allocate occupancy");
+  hipError_t err;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    err = hipMemcpyAsync(occupancy_dev, occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+  }
+  int result = VGT_HIP_OK;
+  if (err == hipSuccess)
+    result = LabelToHost(ctx, occupancy_dev, 4, -1, vgt::kComponentClasses, nullptr, 0.0, nx, ny, nz, labels_host,
+                         num_components);
+  else
+    (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(occupancy_dev);
+  if (result != VGT_HIP_OK) return result;
+  VGT_TRY_HIP(err, "upload occupancy");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
+                                       uint32_t* labels_host, uint32_t* num_components)
+{
+  int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!labels_host || !num_components) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  rc = CheckComponentGrid(cells->nx, cells->ny, cells->nz);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const bool by_object = cells->object_id_offset >= 0 && !connect_across_objects;
+  return LabelToHost(ctx, cells->records, cells->cell_bytes, cells->object_id_offset,
+                     by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, nullptr, 0.0, cells->nx,
+                     cells->ny, cells->nz, labels_host, num_components);
+}
+
+int vgt_hip_cells_spatial_segments_dev(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const double* extrema_dev,
+                                       double connected_threshold, uint32_t* labels_dev, uint32_t* num_segments)
+{
+  int rc = CheckThreshold(connected_threshold);
+  if (rc != VGT_HIP_OK) return rc;
+  rc = CheckSegmentCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!extrema_dev || !labels_dev || !num_segments) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunLabelling(ctx, cells->records, cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
+                      extrema_dev, connected_threshold, cells->nx, cells->ny, cells->nz, labels_dev, num_segments);
+}
+
+int vgt_hip_cells_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const double* extrema_host,
+                                   double connected_threshold, uint32_t* labels_host, uint32_t* num_segments)
+{
+  int rc = CheckThreshold(connected_threshold);
+  if (rc != VGT_HIP_OK) return rc;
+  rc = CheckSegmentCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!extrema_host || !labels_host || !num_segments) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t bytes = static_cast<size_t>(cells->nx * cells->ny * cells->nz) * 3 * sizeof(double);
+  double* extrema_dev = nullptr;
+  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&extrema_dev), bytes), "allocate extrema map");
+  hipError_t err;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    err = hipMemcpyAsync(extrema_dev, extrema_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+  }
+  int result = VGT_HIP_OK;
+  if (err == hipSuccess)
+    result = LabelToHost(ctx, cells->records, cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
+                         extrema_dev, connected_threshold, cells->nx, cells->ny, cells->nz, labels_host, num_segments);
+  else
+    (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(extrema_dev);
+  if (result != VGT_HIP_OK) return result;
+  VGT_TRY_HIP(err, "upload extrema map");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_cells_update_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double connected_threshold,
+                                          double resolution, int unknown_is_filled, int add_virtual_border,
+                                          const double* rotation, uint32_t* labels_host, uint32_t* num_segments)
+{
+  int rc = CheckThreshold(connected_threshold);
+  if (rc != VGT_HIP_OK) return rc;
+  rc = CheckSegmentCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!labels_host || !num_segments) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  rc = CheckSdfShape(cells->nx, cells->ny, cells->nz, resolution);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const int64_t nx = cells->nx, ny = cells->ny, nz = cells->nz, n = nx * ny * nz;
+  double* extrema_dev = nullptr;
+  void* extrema_scratch = nullptr;
+  hipError_t err = hipMalloc(reinterpret_cast<void**>(&extrema_dev), static_cast<size_t>(n) * 3 * sizeof(double));
+  if (err == hipSuccess) err = hipMalloc(&extrema_scratch, vgt::LocalExtremaScratchBytes(n));
+  if (err == hipSuccess)
+  {
+    // S/tagged_object_occupancy_component_map.cpp:786-790: the field of every filled cell with a virtual border, the
+    // free-and-named-objects field without; its extrema map; the segments.  Field and map stay on the device.
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    const vgt::SdfParams p{nx, ny, nz, resolution, unknown_is_filled ? 1 : 0, add_virtual_border ? 1 : 0};
+    if (add_virtual_border)
+      rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf);
+    else
+    {
+      if (!cells->sdf_named)
+        err = hipMalloc(reinterpret_cast<void**>(&cells->sdf_named), static_cast<size_t>(n) * sizeof(float));
+      if (err == hipSuccess) rc = RunFreeAndNamedSdf(ctx, cells, p);
+    }
+    if (err == hipSuccess && rc == VGT_HIP_OK)
+      err = vgt::LaunchLocalExtremaMap(cells->sdf, nx, ny, nz, resolution, rotation, extrema_dev, extrema_scratch,
+                                       ctx->stream);
+    const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (`rotation` is the caller's; the scratch is freed below)
+    if (err == hipSuccess) err = sync;
+  }
+  if (err == hipSuccess && rc == VGT_HIP_OK)
+    rc = LabelToHost(ctx, cells->records, cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
+                     extrema_dev, connected_threshold, nx, ny, nz, labels_host, num_segments);
+  if (extrema_dev) (void)hipFree(extrema_dev);
+  if (extrema_scratch) (void)hipFree(extrema_scratch);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(err, "update spatial segments");
+  return VGT_HIP_OK;
+}
+
+namespace
+{
+int CheckSurfaceMaskArguments(const vgt_hip_ctx* ctx, const void* occupancy, const void* labels, int64_t nx, int64_t ny,
+                              int64_t nz, int component_types, const void* mask)
+{
+  const int rc = CheckComponentGrid(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  if (component_types < 1 || component_types > 7)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component types must be a combination of 1 (filled), 2 (empty), 4 (unknown)");
+  if (!ctx || !occupancy || !labels || !mask) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+int vgt_hip_component_surface_mask_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, const uint32_t* labels_dev,
+                                       int64_t nx, int64_t ny, int64_t nz, int component_types, uint8_t* mask_dev)
+{
+  const int rc = CheckSurfaceMaskArguments(ctx, occupancy_dev, labels_dev, nx, ny, nz, component_types, mask_dev);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(vgt::LaunchComponentSurfaceMask(occupancy_dev, labels_dev, nx, ny, nz, component_types, mask_dev,
+                                              ctx->stream),
+              "component surface mask");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host, const uint32_t* labels_host,
+                                   int64_t nx, int64_t ny, int64_t nz, int component_types, uint8_t* mask_host)
+{
+  const int rc = CheckSurfaceMaskArguments(ctx, occupancy_host, labels_host, nx, ny, nz, component_types, mask_host);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t n = static_cast<size_t>(nx * ny * nz);
+  char* buffer = nullptr;  // occupancy, labels, mask
+  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&buffer), n * 9), "allocate surface mask buffers");
+  float* const occupancy_dev = reinterpret_cast<float*>(buffer);
+  uint32_t* const labels_dev = reinterpret_cast<uint32_t*>(buffer + n * 4);
+  uint8_t* const mask_dev = reinterpret_cast<uint8_t*>(buffer + n * 8);
+  hipError_t err;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    err = hipMemcpyAsync(occupancy_dev, occupancy_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(labels_dev, labels_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (err == hipSuccess)
+      err = vgt::LaunchComponentSurfaceMask(occupancy_dev, labels_dev, nx, ny, nz, component_types, mask_dev,
+                                            ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(mask_host, mask_dev, n, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t sync = hipStreamSynchronize(ctx->stream);
+    if (err == hipSuccess) err = sync;
+  }
+  (void)hipFree(buffer);
+  VGT_TRY_HIP(err, "component surface mask");
   return VGT_HIP_OK;
 }
 

@@ -243,6 +243,30 @@ hipError_t LaunchLocalExtremaMap(const float* sdf_dev, int64_t nx, int64_t ny, i
                                  const double* rotation_host, double* extrema_dev, void* scratch_dev,
                                  hipStream_t stream);
 
+// --- launchers (component_kernels.hip): connected components, spatial segments, component surfaces ---
+// Which predicate joins two face-adjacent cells:
+//   kComponentClasses        both occupancies > 0.5, or both < 0.5, or both == 0.5 (OccupancyComponentMap)
+//   kComponentClassesAndIds  the same and equal object ids (TaggedObjectOccupancyComponentMap, not across objects)
+//   kComponentSegments       UpdateSpatialSegments: cells that are (free or of a named object) and have a finite entry in
+//                            the extrema map; equal object ids and extrema closer than connected_threshold
+constexpr int kComponentClasses = 0;
+constexpr int kComponentClassesAndIds = 1;
+constexpr int kComponentSegments = 2;
+// scratch_dev: ComponentScratchBytes bytes (the int32 union-find labels and the scan's block counts).  labels_dev
+// receives 0 for a cell outside the labelling, else the number of its component: 1, 2, 3 ... in ascending order of the
+// smallest linear index of the component.  The number of components lies at ComponentCountPtr(scratch_dev) afterwards
+// (stream-ordered).  cells_dev: records of cell_bytes bytes with the float occupancy first (a plain float grid: 4, -1).
+// Grids below 2^31 cells.
+size_t ComponentScratchBytes(int64_t num_cells);
+const uint32_t* ComponentCountPtr(const void* scratch_dev, int64_t num_cells);
+hipError_t LaunchLabelComponents(const void* cells_dev, int cell_bytes, int object_id_offset, int mode,
+                                 const double* extrema_dev, double connected_threshold, int64_t nx, int64_t ny,
+                                 int64_t nz, uint32_t* labels_dev, void* scratch_dev, hipStream_t stream);
+// mask_dev[i] = 1 when cell i's occupancy class is selected by component_types (1 filled | 2 empty | 4 unknown) and the
+// cell lies on a face of the grid or has a face neighbour with another label.
+hipError_t LaunchComponentSurfaceMask(const float* occupancy_dev, const uint32_t* labels_dev, int64_t nx, int64_t ny,
+                                      int64_t nz, int component_types, uint8_t* mask_dev, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
