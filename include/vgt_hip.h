@@ -435,6 +435,52 @@ int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host
 int vgt_hip_component_surface_mask_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, const uint32_t* labels_dev,
                                        int64_t nx, int64_t ny, int64_t nz, int component_types, uint8_t* mask_dev);
 
+/* ---- holes and voids per component: ComputeComponentTopology (I/topology_computation.hpp:331-670, called from
+ * S/occupancy_component_map.cpp:594-653 and S/tagged_object_occupancy_component_map.cpp:566-625).
+ * The reference walks hash sets per component; its result is this closed form, computed by csrc/topology_kernels.hip.
+ * `labels` as vgt_hip_connected_components* writes them (1 .. num_components; 0 and anything larger is "no component
+ * of the table"); a cell outside the grid belongs to no component.  For a label c whose class -- 0x01 filled (> 0.5) |
+ * 0x02 empty (< 0.5) | 0x04 unknown (everything else), the rule of vgt_hip_component_surface_mask -- is selected by
+ * component_types:
+ *   1. lattice vertices are (i, j, k), 0 <= i <= nx etc.; the 8 cells round one are (i-1..i, j-1..j, k-1..k).  V_c =
+ *      the vertices where at least one of the 8 is of c and at least one is not;
+ *   2. a lattice edge at a vertex of V_c is exposed when, of the 4 cells round the edge, some are of c and some are
+ *      not; m3 / m5 / m6 = vertices of V_c with exactly 3 / 5 / 6 exposed edges, num_surface_vertices = |V_c|;
+ *   3. num_surfaces = connected components of the graph (V_c, exposed edges);
+ *   4. num_voids = num_surfaces - 1;  num_holes = 1 + (m5 + 2 m6 - m3) / 8 + num_voids, the division as in C on int32
+ *      (toward zero; a component pinched at an edge or a vertex leaves a remainder).
+ * A vertex can lie in V_c of up to 8 components at once; each counts it.  num_holes / num_voids are returned as
+ * computed, negative values included.
+ * DIFFERENCE FROM THE REFERENCE: when it collects V_c it reads the Z + 1 neighbour at Z - 1 (:388-391), so the inner
+ * vertices of a flat +Z face are never inserted and its vertex walk (:257) throws std::out_of_range for any component
+ * with a flat top of 2 x 2 cells or more.  This library implements the evident intent, Z + 1.
+ * Entry [c] of the table belongs to label c; [0] and the entries of labels whose class is not selected are all zero
+ * (present == 0).  The table is written to HOST memory in every variant; out_capacity counts entries and must be at
+ * least *num_components + 1, else the call fails after it has stored *num_components.
+ *   vgt_hip_component_topology_dev    occupancy and labels already on the device (e.g. straight after
+ *                                     vgt_hip_connected_components_dev, no host round trip); out_host has
+ *                                     num_components + 1 entries;
+ *   vgt_hip_component_topology        labels the grid first, as the reference's method does (it calls
+ *                                     UpdateConnectedComponents); labels_host may be NULL, else it receives the labels;
+ *   vgt_hip_cells_component_topology  the same for uploaded cells, connect_across_objects as for
+ *                                     vgt_hip_cells_connected_components.
+ * Grids below 2^31 cells whose vertex lattice (nx + 1)(ny + 1)(nz + 1) is below 2^31 too.  Blocking.
+ * Device memory of a call, linear in voxels + surface nodes (a node is a pair of a vertex and a selected component with
+ * the vertex in V_c): 4 bytes per lattice vertex, 16 bytes per node, 32 bytes per component; the labelling variants add
+ * the labels (4 per voxel) and the labelling scratch the context keeps (4 per voxel).  Nodes below 2^31. */
+typedef struct {
+  int32_t present, num_holes, num_voids, num_surfaces, m3, m5, m6, num_surface_vertices;
+} vgt_hip_component_topology_t;
+int vgt_hip_component_topology_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, const uint32_t* labels_dev,
+                                   int64_t nx, int64_t ny, int64_t nz, int component_types, uint32_t num_components,
+                                   vgt_hip_component_topology_t* out_host);
+int vgt_hip_component_topology(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx, int64_t ny, int64_t nz,
+                               int component_types, uint32_t* labels_host, uint32_t* num_components,
+                               vgt_hip_component_topology_t* out_host, uint64_t out_capacity);
+int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
+                                     int component_types, uint32_t* labels_host, uint32_t* num_components,
+                                     vgt_hip_component_topology_t* out_host, uint64_t out_capacity);
+
 /* ---- multi-GPU: the grid is cut into Z slabs, one device per slab (BASELINE.json config 5).
  * Lines along Y and X are local to a slab; only the first pass (nearest voxel of the other class
  * along Z) crosses slabs, and all it needs from the other slabs is, per (x, y) line, the nearest

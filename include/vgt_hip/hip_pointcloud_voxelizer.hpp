@@ -140,6 +140,22 @@ enum COMPONENT_TYPES : uint8_t { FILLED_COMPONENTS = 0x01, EMPTY_COMPONENTS = 0x
 // component number -> grid indices (x, y, z) of its surface cells, in ascending linear order
 using ComponentSurfaces = std::map<uint32_t, std::vector<std::array<int64_t, 3>>>;
 
+// Holes and voids of one component (topology_computation.hpp:23-48): refuses negative numbers like the reference's class.
+class NumberOfHolesAndVoids
+{
+public:
+  NumberOfHolesAndVoids() = default;
+  NumberOfHolesAndVoids(int32_t num_holes, int32_t num_voids);  // std::invalid_argument when either is negative
+  int32_t NumHoles() const { return holes_; }
+  int32_t NumVoids() const { return voids_; }
+
+private:
+  int32_t holes_ = 0;
+  int32_t voids_ = 0;
+};
+// component number -> its holes and voids, for the components of the selected classes
+using TopologicalInvariants = std::map<uint32_t, NumberOfHolesAndVoids>;
+
 // ---- the other three map types ----
 // OccupancyComponentMap::ExtractSignedDistanceField<float> (occupancy_component_map.hpp:270-306).
 SignedDistanceField ExtractSignedDistanceField(
@@ -175,6 +191,10 @@ public:
   ComponentLabels ConnectedComponents(bool connect_across_objects) const;
   ComponentLabels SpatialSegments(double connected_threshold,
                                   const SignedDistanceFieldGenerationParameters& parameters) const;
+  // ComputeComponentTopology for the uploaded cells (vgt_hip_cells_component_topology): the invariants of the components
+  // whose class component_types selects; `labels` (optional) receives the labelling it ran first.
+  TopologicalInvariants ComponentTopology(bool connect_across_objects, uint8_t component_types,
+                                          ComponentLabels* labels = nullptr) const;
 
 private:
   void Upload(const void* cells, int cell_bytes, int object_id_offset, int hip_device);
@@ -203,4 +223,13 @@ ComponentSurfaces ExtractComponentSurfaces(const OccupancyComponentMap& map, uin
                                            int hip_device = 0);
 ComponentSurfaces ExtractComponentSurfaces(const TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
                                            int hip_device = 0);
+// ComputeComponentTopology (occupancy_component_map.cpp:594-653, tagged_object_occupancy_component_map.cpp:566-625):
+// labels the map like UpdateConnectedComponents -- the cells' `component` members are written, as by the reference's
+// method -- and returns holes and voids of every component whose class component_types selects (csrc/topology_kernels.hip;
+// include/vgt_hip.h defines the numbers and names the one deliberate difference from the reference, Z + 1).
+// std::invalid_argument for an uninitialised map, component_types outside 1..7, a map whose vertex lattice
+// (nx + 1)(ny + 1)(nz + 1) reaches 2^31, and -- from NumberOfHolesAndVoids -- a component whose count comes out negative.
+TopologicalInvariants ComputeComponentTopology(OccupancyComponentMap& map, uint8_t component_types, int hip_device = 0);
+TopologicalInvariants ComputeComponentTopology(TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
+                                               bool connect_across_objects, int hip_device = 0);
 }  // namespace vgt_hip

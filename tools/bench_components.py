@@ -3,6 +3,8 @@
 beside the CPU yardsticks of tests/components_ref.py.  One JSON line per case.
 
   python tools/bench_components.py [--sizes 256 512 1024] [--steps 20] [--warmup 3] [--no-cpu] [--out FILE]
+  python tools/bench_components.py --topology [--sizes 256 1024] [--dists spheres] ...   the component topology
+      (vgt_hip_component_topology_dev) on labelled grids, beside the labelling of the same grid
 
 Timing: wall clock around the call (it ends with the read-back of the count, so the stream is drained; a
 vgt_hip_synchronize before and after brackets it), `steps` repetitions after `warmup`, median and min / max.
@@ -31,6 +33,46 @@ def _stats(ms):
             "max_ms": round(float(ms.max()), 4), "steps": int(ms.size)}
 
 
+def _timed(ctx, call, warmup, steps):
+    ms, result = [], None
+    for step in range(warmup + steps):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        result = call()
+        ctx.synchronize()
+        if step >= warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return ms, result
+
+
+def bench_topology(ctx, args, emit):
+    """vgt_hip_component_topology_dev (all classes) on device-resident labels; the labelling of the same grid as the
+    yardstick.  Both calls block (each reads a count / the table back)."""
+    import torch
+    from voxelized_geometry_tools_amd import synthetic
+    for size in args.sizes:
+        shape = (size, size, size)
+        for dist in args.dists:
+            occ_dev = torch.from_numpy(synthetic.make_occupancy(shape, dist, seed=42)).cuda()
+            labels_dev = torch.empty(shape, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            label_ms, count = _timed(ctx, lambda: ctx.connected_components_dev(occ_dev.data_ptr(), shape,
+                                                                               labels_dev.data_ptr()),
+                                     args.warmup, args.steps)
+            topo_ms, table = _timed(ctx, lambda: ctx.component_topology_dev(occ_dev.data_ptr(), labels_dev.data_ptr(),
+                                                                            shape, 7, count),
+                                    args.warmup, args.steps)
+            rec = {"case": "component_topology_dev", "dist": dist, "shape": list(shape), "components": count,
+                   "component_types": 7, "surface_nodes": int(table["num_surface_vertices"].sum()),
+                   "max_holes": int(table["num_holes"].max()), "max_voids": int(table["num_voids"].max())}
+            rec.update(_stats(topo_ms))
+            rec["labelling_median_ms"] = _stats(label_ms)["median_ms"]
+            rec["ratio_to_labelling"] = round(rec["median_ms"] / rec["labelling_median_ms"], 3)
+            rec["voxels_per_s"] = round(size ** 3 / (rec["median_ms"] * 1e-3), 1)
+            emit(rec)
+            del occ_dev, labels_dev
+
+
 def main():
     import torch
     import components_ref as R
@@ -42,6 +84,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-cpu", action="store_true", help="skip the host yardsticks (they take minutes at 512^3)")
     ap.add_argument("--cpu-max-size", type=int, default=256, help="largest size the fast CPU labelling is timed on")
+    ap.add_argument("--topology", action="store_true", help="time the component topology instead")
+    ap.add_argument("--dists", nargs="+", default=["spheres"], help="--topology: the distributions to time")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     lines = []
@@ -52,6 +96,13 @@ def main():
         lines.append(line)
 
     ctx = capi.Context(0)
+    if args.topology:
+        bench_topology(ctx, args, emit)
+        ctx.close()
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     for size in args.sizes:
         shape = (size, size, size)
         vox = size ** 3

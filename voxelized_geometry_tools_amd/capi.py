@@ -81,6 +81,9 @@ SIGNATURES = {
     "vgt_hip_cells_update_spatial_segments": (_int, [_p, _p, _f64, _f64, _int, _int, _p, _p, _p]),
     "vgt_hip_component_surface_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
     "vgt_hip_component_surface_mask_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
+    "vgt_hip_component_topology_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint32, _p]),
+    "vgt_hip_component_topology": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_uint64]),
+    "vgt_hip_cells_component_topology": (_int, [_p, _p, _int, _int, _p, _p, _p, ctypes.c_uint64]),
     "vgt_hipx_sdf_multi": (_int, [_p, _int, _p, _i64, _i64, _i64, _f64, _int, _int, _p, _p, _p]),
     "vgt_hipx_release": (None, []),
     "vgt_hipx_last_timing": (_int, [_p]),
@@ -125,6 +128,11 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
 }
+
+
+# vgt_hip_component_topology_t
+COMPONENT_TOPOLOGY = np.dtype([(name, np.int32) for name in (
+    "present", "num_holes", "num_voids", "num_surfaces", "m3", "m5", "m6", "num_surface_vertices")])
 
 
 class VgtHipError(RuntimeError):
@@ -206,6 +214,20 @@ def _ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(ctypes.c_void_p)
     return ctypes.c_void_p(int(a))
+
+
+def _topology_table(call, capacity=256):
+    """Runs call(table, capacity, byref(count)) and once more with the reported size when the table was too small."""
+    for _ in range(2):
+        table = np.zeros(capacity, dtype=COMPONENT_TOPOLOGY)
+        count = ctypes.c_uint32(0xffffffff)
+        rc = call(table, capacity, ctypes.byref(count))
+        if rc == 1 and count.value != 0xffffffff and count.value + 1 > capacity:
+            capacity = count.value + 1
+            continue
+        check(rc)
+        return table[:count.value + 1].copy()
+    raise VgtHipError("the component count changed between two calls")
 
 
 def device_count():
@@ -323,6 +345,27 @@ class Context:
         check(self._lib.vgt_hip_component_surface_mask_dev(self.handle, _ptr(occ_ptr), _ptr(labels_ptr),
                                                            *[int(v) for v in shape], int(component_types),
                                                            _ptr(mask_ptr)))
+
+    def component_topology(self, occupancy, component_types, with_labels=False):
+        """ComputeComponentTopology of an occupancy grid (it labels the grid first): a COMPONENT_TOPOLOGY array with one
+        entry per label, [c] for component c, [0] and the components of classes not selected all zero.
+        with_labels=True: (table, uint32 labels)."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.float32)
+        if occ.ndim != 3:
+            raise ValueError("occupancy must be (nx, ny, nz)")
+        labels = np.empty(occ.shape, dtype=np.uint32) if with_labels else None
+        table = _topology_table(
+            lambda out, capacity, count: self._lib.vgt_hip_component_topology(
+                self.handle, _ptr(occ), *occ.shape, int(component_types), _ptr(labels), count, _ptr(out), capacity))
+        return (table, labels) if with_labels else table
+
+    def component_topology_dev(self, occ_ptr, labels_ptr, shape, component_types, num_components):
+        """vgt_hip_component_topology_dev: occupancy and labels on the device -> the table (host)."""
+        table = np.zeros(int(num_components) + 1, dtype=COMPONENT_TOPOLOGY)
+        check(self._lib.vgt_hip_component_topology_dev(self.handle, _ptr(occ_ptr), _ptr(labels_ptr),
+                                                       *[int(v) for v in shape], int(component_types),
+                                                       int(num_components), _ptr(table)))
+        return table
 
     def trim(self):
         """Frees the device buffers the context caches between host-pointer calls."""
@@ -776,6 +819,16 @@ class Cells:
                                                            int(bool(connect_across_objects)), _ptr(labels),
                                                            ctypes.byref(count)))
         return labels, int(count.value)
+
+    def component_topology(self, component_types, connect_across_objects=False, with_labels=False):
+        """ComputeComponentTopology of the uploaded cells: the COMPONENT_TOPOLOGY table of Context.component_topology;
+        with_labels=True: (table, uint32 labels)."""
+        labels = np.empty(self.shape, dtype=np.uint32) if with_labels else None
+        table = _topology_table(
+            lambda out, capacity, count: self._lib.vgt_hip_cells_component_topology(
+                self.ctx.handle, self.handle, int(bool(connect_across_objects)), int(component_types), _ptr(labels),
+                count, _ptr(out), capacity))
+        return (table, labels) if with_labels else table
 
     def spatial_segments(self, extrema, threshold):
         """The labelling step of UpdateSpatialSegments on a given local-extrema map [nx, ny, nz, 3] float64:

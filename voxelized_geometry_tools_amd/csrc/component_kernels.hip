@@ -22,6 +22,7 @@
 //   5. RankRoots   rank of every root inside its block + the block's offset -> out[root] = rank + 1.
 //   6. Relabel     out[i] = out[root(i)], 0 for inactive cells.
 // (The issue that asked for this suggested an LDS tile merge between 1 and 2; it is not here: see DESIGN.md.)
+#include "union_find_device.hpp"
 #include "vgt_internal.hpp"
 
 namespace vgt
@@ -134,40 +135,6 @@ __global__ __launch_bounds__(kBlock) void InitRunsKernel(View v, int64_t total, 
   label[i] = active ? static_cast<int32_t>(i - lane + start_lane) : -1;
 }
 
-__device__ __forceinline__ int32_t LoadLabel(const int32_t* label, int32_t i)
-{
-  return __atomic_load_n(label + i, __ATOMIC_RELAXED);
-}
-
-__device__ __forceinline__ int32_t FindRoot(const int32_t* label, int32_t a)
-{
-  // parents are smaller than their children: the walk strictly descends and ends at the set's smallest index.  A stale
-  // read yields an earlier parent -- still an ancestor
-  for (int32_t p = LoadLabel(label, a); p != a; p = LoadLabel(label, a)) a = p;
-  return a;
-}
-
-__device__ __forceinline__ void Union(int32_t* label, int32_t a, int32_t b)
-{
-  for (;;)
-  {
-    a = FindRoot(label, a);
-    b = FindRoot(label, b);
-    if (a == b) return;
-    if (a < b)
-    {
-      const int32_t t = a;
-      a = b;
-      b = t;
-    }
-    // a > b: hang a below b.  If a was no root any more, label[a] is now min(old, b) and old (< a) still has to be
-    // joined with b: go on with it.
-    const int32_t old = atomicMin(label + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
 template <int kMode>
 __global__ __launch_bounds__(kBlock) void MergeEdgesKernel(View v, int64_t total, int ny, int nz, int32_t* label)
 {
@@ -211,17 +178,6 @@ __global__ __launch_bounds__(kBlock) void MergeEdgesKernel(View v, int64_t total
   }
   if (join_y && !skip_y) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(iy));
   if (join_x && !skip_x) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(ix));
-}
-
-// Inclusive prefix sum over the lanes of a wave.
-__device__ __forceinline__ int WaveInclusiveScan(int value, int lane)
-{
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const int other = __shfl_up(value, d);
-    if (lane >= d) value += other;
-  }
-  return value;
 }
 
 // every cell -> its root; block_roots[b] = roots among the kScanBlockCells cells of block b

@@ -668,6 +668,96 @@ ComponentLabels DeviceTaggedObjectMap::SpatialSegments(double connected_threshol
   return out;
 }
 
+NumberOfHolesAndVoids::NumberOfHolesAndVoids(int32_t num_holes, int32_t num_voids)
+    : holes_(num_holes), voids_(num_voids)
+{
+  if (num_holes < 0) throw std::invalid_argument("negative number of holes: " + std::to_string(num_holes));
+  if (num_voids < 0) throw std::invalid_argument("negative number of voids: " + std::to_string(num_voids));
+}
+
+namespace
+{
+void CheckComponentTypes(uint8_t component_types)
+{
+  if (component_types < 1 || component_types > 7)
+    throw std::invalid_argument("component types must be a combination of FILLED_, EMPTY_ and UNKNOWN_COMPONENTS");
+}
+
+// vgt_hip_cells_component_topology with a table that grows to what the call reports; labels->labels is sized already.
+TopologicalInvariants CellsTopology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, bool connect_across_objects,
+                                    uint8_t component_types, ComponentLabels* labels)
+{
+  std::vector<vgt_hip_component_topology_t> table(64);
+  for (;;)
+  {
+    uint32_t count = 0xffffffffu;
+    const int rc = vgt_hip_cells_component_topology(ctx, cells, connect_across_objects ? 1 : 0, component_types,
+                                                    labels->labels.data(), &count, table.data(), table.size());
+    if (rc == VGT_HIP_OK)
+    {
+      labels->count = count;
+      break;
+    }
+    const std::string msg = vgt_hip_last_error();
+    if (count == 0xffffffffu || static_cast<size_t>(count) + 1 <= table.size()) ThrowForCode(rc, msg);
+    table.assign(static_cast<size_t>(count) + 1, vgt_hip_component_topology_t());
+  }
+  TopologicalInvariants invariants;
+  for (uint32_t c = 1; c <= labels->count; c++)
+    if (table[c].present) invariants.emplace(c, NumberOfHolesAndVoids(table[c].num_holes, table[c].num_voids));
+  return invariants;
+}
+}  // namespace
+
+TopologicalInvariants DeviceTaggedObjectMap::ComponentTopology(bool connect_across_objects, uint8_t component_types,
+                                                               ComponentLabels* labels) const
+{
+  CheckComponentTypes(component_types);
+  ComponentLabels own;
+  ComponentLabels* const out = labels ? labels : &own;
+  out->labels.resize(static_cast<size_t>(shape_.NumTotalVoxels()));
+  return CellsTopology(ctx_, cells_, connect_across_objects, component_types, out);
+}
+
+TopologicalInvariants ComputeComponentTopology(OccupancyComponentMap& map, uint8_t component_types, int hip_device)
+{
+  if (!map.IsInitialized()) throw std::invalid_argument("Grid must be initialized");
+  CheckComponentTypes(component_types);
+  vgt_hip_ctx* ctx = SharedSdfContext(hip_device);
+  vgt_hip_cells* cells = nullptr;
+  const int rc = vgt_hip_cells_create(ctx, map.GetImmutableRawData().data(), map.NumXVoxels(), map.NumYVoxels(),
+                                      map.NumZVoxels(), static_cast<int32_t>(sizeof(OccupancyComponentCell)), -1, &cells);
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
+  ComponentLabels result;
+  result.labels.resize(map.GetImmutableRawData().size());
+  TopologicalInvariants invariants;
+  try
+  {
+    invariants = CellsTopology(ctx, cells, false, component_types, &result);
+  }
+  catch (...)
+  {
+    vgt_hip_cells_destroy(cells);
+    throw;
+  }
+  vgt_hip_cells_destroy(cells);
+  std::vector<OccupancyComponentCell>& data = map.GetMutableRawData();
+  for (size_t i = 0; i < data.size(); i++) data[i].component = result.labels[i];
+  return invariants;
+}
+
+TopologicalInvariants ComputeComponentTopology(TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
+                                               bool connect_across_objects, int hip_device)
+{
+  CheckComponentTypes(component_types);
+  ComponentLabels result;
+  const TopologicalInvariants invariants =
+      DeviceTaggedObjectMap(map, hip_device).ComponentTopology(connect_across_objects, component_types, &result);
+  std::vector<TaggedObjectOccupancyComponentCell>& data = map.GetMutableRawData();
+  for (size_t i = 0; i < data.size(); i++) data[i].component = result.labels[i];
+  return invariants;
+}
+
 uint32_t UpdateConnectedComponents(OccupancyComponentMap& map, int hip_device)
 {
   if (!map.IsInitialized()) throw std::invalid_argument("Grid must be initialized");

@@ -2859,6 +2859,166 @@ int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host
   return VGT_HIP_OK;
 }
 
+/* ------------------------- holes and voids per component ------------------------- */
+
+static_assert(sizeof(vgt_hip_component_topology_t) == 32 &&
+                  sizeof(vgt::ComponentTopologyEntry) == sizeof(vgt_hip_component_topology_t),
+              "the device table is the ABI's table");
+
+namespace
+{
+// Everything that can be said about the arguments of the three entry points before any HIP call.
+int CheckTopologyGrid(int64_t nx, int64_t ny, int64_t nz, int component_types)
+{
+  const int rc = CheckComponentGrid(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  // (each extent is below 2^31 - 1 and their product too: no overflow in 64 bits)
+  if ((nx + 1) * (ny + 1) >= 0x7fffffffLL || vgt::TopologyVertices(nx, ny, nz) >= 0x7fffffffLL)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "component topology needs the vertex lattice (nx + 1)(ny + 1)(nz + 1) below 2^31 vertices");
+  if (component_types < 1 || component_types > 7)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component types must be a combination of 1 (filled), 2 (empty), 4 (unknown)");
+  return VGT_HIP_OK;
+}
+
+// The table of a labelled grid into out_host (num_components + 1 entries).  Caller holds the context mutex and has set
+// the device.
+int RunTopology(vgt_hip_ctx* ctx, const vgt::TopologyGrid& grid, vgt_hip_component_topology_t* out_host)
+{
+  const size_t table_bytes = (static_cast<size_t>(grid.num_components) + 1) * sizeof(vgt::ComponentTopologyEntry);
+  void* vertex_scratch = nullptr;
+  void* node_scratch = nullptr;
+  vgt::ComponentTopologyEntry* table_dev = nullptr;
+  unsigned long long num_nodes = 0;
+  hipError_t err = hipMalloc(&vertex_scratch, vgt::TopologyVertexScratchBytes(grid.nx, grid.ny, grid.nz));
+  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&table_dev), table_bytes);
+  if (err == hipSuccess) err = vgt::LaunchTopologyCountNodes(grid, vertex_scratch, ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&num_nodes, vgt::TopologyNodeCountPtr(vertex_scratch, grid.nx, grid.ny, grid.nz),
+                         sizeof(num_nodes), hipMemcpyDeviceToHost, ctx->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+  int rc = VGT_HIP_OK;
+  if (err == hipSuccess && num_nodes >= 0x7fffffffULL)
+    rc = Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component topology supports fewer than 2^31 surface nodes");
+  if (err == hipSuccess && rc == VGT_HIP_OK && num_nodes > 0)
+    err = hipMalloc(&node_scratch, vgt::TopologyNodeScratchBytes(static_cast<int64_t>(num_nodes)));
+  if (err == hipSuccess && rc == VGT_HIP_OK)
+  {
+    err = vgt::LaunchTopologyFromNodes(grid, vertex_scratch, static_cast<int64_t>(num_nodes), node_scratch, table_dev,
+                                       ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(out_host, table_dev, table_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (the buffers are freed below)
+  if (err == hipSuccess) err = sync;
+  if (vertex_scratch) (void)hipFree(vertex_scratch);
+  if (node_scratch) (void)hipFree(node_scratch);
+  if (table_dev) (void)hipFree(table_dev);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(err, "component topology");
+  return VGT_HIP_OK;
+}
+
+// Labels the cells into a temporary device grid, then the table (and the labels, when asked for) to the host.
+int LabelAndTopology(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int object_id_offset, int mode, int64_t nx,
+                     int64_t ny, int64_t nz, int component_types, uint32_t* labels_host, uint32_t* num_components,
+                     vgt_hip_component_topology_t* out_host, uint64_t out_capacity)
+{
+  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(uint32_t);
+  uint32_t* labels_dev = nullptr;
+  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&labels_dev), bytes), "allocate labels");
+  int rc;
+  hipError_t err = hipSuccess;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    uint32_t count = 0;
+    rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, nullptr, 0.0, nx, ny, nz, labels_dev, &count);
+    if (rc == VGT_HIP_OK)
+    {
+      *num_components = count;
+      if (out_capacity < static_cast<uint64_t>(count) + 1)
+        rc = Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "the topology table needs num_components + 1 = " + std::to_string(static_cast<uint64_t>(count) + 1) +
+                      " entries, out_capacity is " + std::to_string(out_capacity));
+    }
+    if (rc == VGT_HIP_OK)
+      rc = RunTopology(ctx, vgt::TopologyGrid{cells_dev, cell_bytes, labels_dev, nx, ny, nz, component_types, count},
+                       out_host);
+    if (rc == VGT_HIP_OK && labels_host)
+    {
+      err = hipMemcpyAsync(labels_host, labels_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+      const hipError_t sync = hipStreamSynchronize(ctx->stream);
+      if (err == hipSuccess) err = sync;
+    }
+  }
+  (void)hipFree(labels_dev);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(err, "copy labels to the host");
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+int vgt_hip_component_topology_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, const uint32_t* labels_dev,
+                                   int64_t nx, int64_t ny, int64_t nz, int component_types, uint32_t num_components,
+                                   vgt_hip_component_topology_t* out_host)
+{
+  const int rc = CheckTopologyGrid(nx, ny, nz, component_types);
+  if (rc != VGT_HIP_OK) return rc;
+  if (static_cast<int64_t>(num_components) > nx * ny * nz)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a grid cannot hold more components than cells");
+  if (!ctx || !occupancy_dev || !labels_dev || !out_host) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunTopology(ctx, vgt::TopologyGrid{occupancy_dev, 4, labels_dev, nx, ny, nz, component_types, num_components},
+                     out_host);
+}
+
+int vgt_hip_component_topology(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx, int64_t ny, int64_t nz,
+                               int component_types, uint32_t* labels_host, uint32_t* num_components,
+                               vgt_hip_component_topology_t* out_host, uint64_t out_capacity)
+{
+  const int rc = CheckTopologyGrid(nx, ny, nz, component_types);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!ctx || !occupancy_host || !num_components || !out_host)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(float);
+  float* occupancy_dev = nullptr;
+  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&occupancy_dev), bytes), "allocate occupancy");
+  hipError_t err;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    err = hipMemcpyAsync(occupancy_dev, occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+  }
+  int result = VGT_HIP_OK;
+  if (err == hipSuccess)
+    result = LabelAndTopology(ctx, occupancy_dev, 4, -1, vgt::kComponentClasses, nx, ny, nz, component_types, labels_host,
+                              num_components, out_host, out_capacity);
+  else
+    (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(occupancy_dev);
+  if (result != VGT_HIP_OK) return result;
+  VGT_TRY_HIP(err, "upload occupancy");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
+                                     int component_types, uint32_t* labels_host, uint32_t* num_components,
+                                     vgt_hip_component_topology_t* out_host, uint64_t out_capacity)
+{
+  if (component_types < 1 || component_types > 7)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component types must be a combination of 1 (filled), 2 (empty), 4 (unknown)");
+  int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!num_components || !out_host) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  rc = CheckTopologyGrid(cells->nx, cells->ny, cells->nz, component_types);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const bool by_object = cells->object_id_offset >= 0 && !connect_across_objects;
+  return LabelAndTopology(ctx, cells->records, cells->cell_bytes, cells->object_id_offset,
+                          by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, cells->nx, cells->ny,
+                          cells->nz, component_types, labels_host, num_components, out_host, out_capacity);
+}
+
 /* --------------------------------- multi-GPU --------------------------------- */
 
 size_t vgt_hip_sdf_slab_summary_bytes(int64_t nx, int64_t ny)

@@ -267,6 +267,38 @@ hipError_t LaunchLabelComponents(const void* cells_dev, int cell_bytes, int obje
 hipError_t LaunchComponentSurfaceMask(const float* occupancy_dev, const uint32_t* labels_dev, int64_t nx, int64_t ny,
                                       int64_t nz, int component_types, uint8_t* mask_dev, hipStream_t stream);
 
+// --- launchers (topology_kernels.hip): holes and voids per component ---
+// One entry per label, the layout of vgt_hip_component_topology_t (include/vgt_hip.h).
+struct ComponentTopologyEntry
+{
+  int32_t present, num_holes, num_voids, num_surfaces, m3, m5, m6, num_surface_vertices;
+};
+// cells_dev: records of cell_bytes bytes with the float occupancy first (a plain float grid: 4); labels_dev as
+// LaunchLabelComponents writes them.  Labels outside 1..num_components count as "another component" and get no entry.
+struct TopologyGrid
+{
+  const void* cells_dev;
+  int cell_bytes;
+  const uint32_t* labels_dev;
+  int64_t nx, ny, nz;
+  int component_types;  // 1 filled | 2 empty | 4 unknown
+  uint32_t num_components;
+};
+inline int64_t TopologyVertices(int64_t nx, int64_t ny, int64_t nz) { return (nx + 1) * (ny + 1) * (nz + 1); }
+// Two steps, because the node arrays are sized by what the first one counts (nodes = pairs of a lattice vertex and a
+// selected component it lies on the surface of: a surface, not a volume):
+//   LaunchTopologyCountNodes   vertex_scratch_dev: TopologyVertexScratchBytes bytes (4 per lattice vertex + 4 per 256 of
+//                              them); afterwards the number of nodes (64 bits) lies at TopologyNodeCountPtr.
+//   LaunchTopologyFromNodes    node_scratch_dev: TopologyNodeScratchBytes(num_nodes) bytes (16 per node), num_nodes
+//                              below 2^31; table_dev: num_components + 1 entries, [0] zeroed.
+// The lattice (nx + 1)(ny + 1)(nz + 1) must stay below 2^31 vertices.
+size_t TopologyVertexScratchBytes(int64_t nx, int64_t ny, int64_t nz);
+const unsigned long long* TopologyNodeCountPtr(const void* vertex_scratch_dev, int64_t nx, int64_t ny, int64_t nz);
+size_t TopologyNodeScratchBytes(int64_t num_nodes);
+hipError_t LaunchTopologyCountNodes(const TopologyGrid& grid, void* vertex_scratch_dev, hipStream_t stream);
+hipError_t LaunchTopologyFromNodes(const TopologyGrid& grid, void* vertex_scratch_dev, int64_t num_nodes,
+                                   void* node_scratch_dev, ComponentTopologyEntry* table_dev, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
