@@ -22,7 +22,7 @@ inline void BlockMinMax(uint32_t lo, uint32_t hi, uint32_t* minmax_enc)
   minmax_enc[0] = std::min(minmax_enc[0], lo);
   minmax_enc[1] = std::max(minmax_enc[1], hi);
 }
-int ShortLineOverride() { return -1; }  // (edt_kernels.hip defines it for the libraries; the launchers here never ask)
+int ShortLineOverride() { return -1; }  // (vgt_hip_capi.hip defines it for the libraries; the launchers here never ask)
 }  // namespace vgt
 #include "../../voxelized_geometry_tools_amd/csrc/edt_sweep_kernels.hip"
 

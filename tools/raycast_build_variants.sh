@@ -11,7 +11,7 @@ BASE="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -fvisibility=
 while [ $# -gt 0 ]; do
   name=$1; flags=$2; shift 2
   d=$ROOT/diag_$name; mkdir -p $d
-  for f in cell_kernels edt_kernels edt_record_kernels edt_short_kernels edt_sweep_kernels vgt_hip_capi vgt_hipx_multi; do cp -u $f.o $d/ 2>/dev/null; done
+  for f in cell_kernels component_kernels edt_kernels edt_record_kernels edt_short_kernels edt_sweep_kernels topology_kernels vgt_hip_capi vgt_hipx_multi; do cp -u $f.o $d/ 2>/dev/null; done
   ( hipcc $BASE $flags -I../../include -c voxelizer_kernels.hip -o $d/voxelizer_kernels.o && hipcc -shared -fPIC --offload-arch=gfx950 -o $d/libvgt_diag.so $d/*.o -Wl,--version-script=exports.map && echo built $name ) &
 done
 wait

@@ -3,6 +3,7 @@
 #include "../../include/vgt_hip.h"
 
 #include "vgt_internal.hpp"
+#include "edt_crosscheck.hpp"
 #include "host_pages.hpp"
 
 #include <algorithm>
@@ -55,7 +56,7 @@ struct vgt_hip_ctx
   void* ray_scratch = nullptr;   // sort scratch of raycasts of device-resident clouds (context stream)
   size_t ray_scratch_bytes = 0;
   float* minmax_out = nullptr;   // 2 floats (device) for host-facing SDF calls
-  vgt::EdtVariant variant = vgt::EdtVariant::kDefault;
+  int variant = 0;               // 0: the default EDT pipeline; 1: the cross-check (vgt_hip_set_edt_variant, testing library)
   // deferred per-kernel timing (vgt_hip_timing_start / _stop): 8 events per SDF call
   std::vector<hipEvent_t> timing_events;
   std::vector<uint8_t> timing_kind;  // 1 = single-device call, 2 = slab begin + finish
@@ -159,6 +160,9 @@ struct vgt_hip_cells
 namespace
 {
 thread_local std::string g_last_error;
+// What vgt_hip_testing_set_short_line_rows told the line passes (vgt::ShortLineOverride), -1 = nothing.  Only that hook
+// stores to it, and only the testing library has the hook.
+std::atomic<int> g_short_line_override{-1};
 
 int Fail(int code, const std::string& msg)
 {
@@ -171,6 +175,7 @@ namespace vgt
 {
 void SetLastError(const std::string& message) { g_last_error = message; }
 hipStream_t ContextStream(const vgt_hip_ctx* ctx) { return ctx->stream; }
+int ShortLineOverride() { return g_short_line_override.load(); }
 }  // namespace vgt
 namespace
 {
@@ -340,10 +345,20 @@ private:
   const void* shared_ = nullptr;
 };
 
+// The stage helpers from here to LaunchSlabFixup are the only code that knows two EDT pipelines exist: the default one
+// and, in the testing library, the cross-check (edt_crosscheck.hpp; variant 1 of vgt_hip_set_edt_variant).  A carved
+// workspace says which one it is for -- `records` or `t16` --, so the later stages ask the workspace, not the context.
+// The product library links no cross-check: there the arms below are discarded and every workspace has records.
+#ifdef VGT_HIP_TESTING
+constexpr bool kHaveCrossCheck = true;
+#else
+constexpr bool kHaveCrossCheck = false;
+#endif
+
 struct SdfWorkspace
 {
   vgt::ClassRecord* records;  // pass-1 result of the default pipeline ...
-  int16_t* t16;               // ... or of the cross-check pipelines (one of the two, the other is null)
+  int16_t* t16;               // ... or of the cross-check pipeline (one of the two, the other is null)
   int32_t* t32;
   uint32_t* minmax_enc;
   vgt::SweepScratch sweep_scratch;  // work counters, spilled stack entries and sign words of the line passes
@@ -352,22 +367,22 @@ struct SdfWorkspace
 
 // (batch > 1: `batch` grids of nx x ny x nz one after the other -- records and the intermediate field of batch * nx
 // slices, a pair of extrema per grid, the line passes' scratch for the batch's items; default pipeline only)
-SdfWorkspace CarveWorkspace(void* base, int64_t nx, int64_t ny, int64_t nz, vgt::EdtVariant variant, int64_t batch = 1)
+SdfWorkspace CarveWorkspace(void* base, int64_t nx, int64_t ny, int64_t nz, int variant, int64_t batch = 1)
 {
   SdfWorkspace ws;
   const size_t n = static_cast<size_t>(batch * nx * ny * nz);
   size_t off = 0;
   ws.records = nullptr;
   ws.t16 = nullptr;
-  if (variant == vgt::EdtVariant::kDefault)
+  if (kHaveCrossCheck && variant != 0)
   {
-    ws.records = reinterpret_cast<vgt::ClassRecord*>(static_cast<char*>(base) + off);
-    off = AlignUp(off + vgt::ClassRecordBytes(batch * nx, ny, nz), 256);
+    ws.t16 = reinterpret_cast<int16_t*>(static_cast<char*>(base) + off);
+    off = AlignUp(off + vgt::CrossCheckFieldBytes(batch * nx * ny * nz), 256);
   }
   else
   {
-    ws.t16 = reinterpret_cast<int16_t*>(static_cast<char*>(base) + off);
-    off = AlignUp(off + n * sizeof(int16_t), 256);
+    ws.records = reinterpret_cast<vgt::ClassRecord*>(static_cast<char*>(base) + off);
+    off = AlignUp(off + vgt::ClassRecordBytes(batch * nx, ny, nz), 256);
   }
   ws.t32 = reinterpret_cast<int32_t*>(static_cast<char*>(base) + off);
   off = AlignUp(off + n * sizeof(int32_t), 256);
@@ -387,36 +402,49 @@ hipError_t LaunchPassOne(const InT* input_dev, const SdfWorkspace& ws, const vgt
                          vgt::SlabLineSummary* summary, hipStream_t s)
 {
   const int64_t voxel_offset = first_slice * part.ny * part.nz;
-  if (ws.records)
+  if constexpr (kHaveCrossCheck)
   {
-    vgt::ClassRecord* records = ws.records + first_slice * vgt::RecordWords(part.nz) * part.ny;
-    if constexpr (std::is_same<InT, float>::value)
-      return vgt::LaunchClassRecordsFromOccupancy(input_dev + voxel_offset, records, part, summary, s);
-    else
-      return vgt::LaunchClassRecordsFromMask(input_dev + voxel_offset, records, part, summary, s);
+    if (ws.t16)
+    {
+      if constexpr (std::is_same<InT, float>::value)
+        return vgt::LaunchCrossCheckScanZFromOccupancy(input_dev + voxel_offset, ws.t16 + voxel_offset, part, summary, s);
+      else
+        return vgt::LaunchCrossCheckScanZFromMask(input_dev + voxel_offset, ws.t16 + voxel_offset, part, summary, s);
+    }
   }
-#ifdef VGT_HIP_TESTING
+  vgt::ClassRecord* records = ws.records + first_slice * vgt::RecordWords(part.nz) * part.ny;
   if constexpr (std::is_same<InT, float>::value)
-    return vgt::LaunchScanZFromOccupancy(input_dev + voxel_offset, ws.t16 + voxel_offset, part, summary, s);
+    return vgt::LaunchClassRecordsFromOccupancy(input_dev + voxel_offset, records, part, summary, s);
   else
-    return vgt::LaunchScanZFromMask(input_dev + voxel_offset, ws.t16 + voxel_offset, part, summary, s);
-#else
-  return hipErrorInvalidValue;  // (no records: a cross-check variant, not part of this build)
-#endif
+    return vgt::LaunchClassRecordsFromMask(input_dev + voxel_offset, records, part, summary, s);
 }
-hipError_t LaunchPassTwo(const SdfWorkspace& ws, const vgt::SdfParams& part, int64_t first_slice, vgt::EdtVariant variant,
-                         hipStream_t s)
+hipError_t LaunchPassTwo(const SdfWorkspace& ws, const vgt::SdfParams& part, int64_t first_slice, hipStream_t s)
 {
   const int64_t voxel_offset = first_slice * part.ny * part.nz;
-  if (ws.records)
-    return vgt::LaunchPassYSweepRecords(ws.records + first_slice * vgt::RecordWords(part.nz) * part.ny,
-                                        ws.t32 + voxel_offset, ws.sweep_scratch, part, s);
-#ifdef VGT_HIP_TESTING
-  return vgt::LaunchPassY(ws.t16 + voxel_offset, ws.t32 + voxel_offset, ws.sweep_scratch, part, variant, s);
-#else
-  (void)variant;
-  return hipErrorInvalidValue;
-#endif
+  if constexpr (kHaveCrossCheck)
+  {
+    if (ws.t16) return vgt::LaunchCrossCheckPassY(ws.t16 + voxel_offset, ws.t32 + voxel_offset, part, s);
+  }
+  return vgt::LaunchPassYSweepRecords(ws.records + first_slice * vgt::RecordWords(part.nz) * part.ny,
+                                      ws.t32 + voxel_offset, ws.sweep_scratch, part, s);
+}
+// The X pass and the final conversion of the whole grid `p`, into sdf_dev and the workspace's extrema.
+hipError_t LaunchPassThree(const SdfWorkspace& ws, const vgt::SdfParams& p, float* sdf_dev, hipStream_t s)
+{
+  if constexpr (kHaveCrossCheck)
+  {
+    if (ws.t16) return vgt::LaunchCrossCheckPassXFinalize(ws.t32, sdf_dev, ws.minmax_enc, p, s);
+  }
+  return vgt::LaunchPassXFinalize(ws.t32, sdf_dev, ws.minmax_enc, ws.sweep_scratch, p, s);
+}
+// Multi-GPU: folds the other slabs' carries into the pass-1 result of slab `p`.
+hipError_t LaunchSlabFixup(const SdfWorkspace& ws, const vgt::SlabLineCarry* carries, const vgt::SdfParams& p, hipStream_t s)
+{
+  if constexpr (kHaveCrossCheck)
+  {
+    if (ws.t16) return vgt::LaunchCrossCheckSlabFixup(ws.t16, carries, p, s);
+  }
+  return vgt::LaunchSlabRecordFixup(ws.records, carries, p, s);
 }
 
 int CheckSdfShape(int64_t nx, int64_t ny, int64_t nz, double resolution)
@@ -443,7 +471,7 @@ int RunSdfPipeline(vgt_hip_ctx* ctx, const InT* input_dev, const vgt::SdfParams&
                    void* workspace_dev, size_t workspace_bytes, float* minmax_dev,
                    hipEvent_t* events)
 {
-  if (p.batch > 1 && ctx->variant != vgt::EdtVariant::kDefault)
+  if (p.batch > 1 && ctx->variant != 0)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "batches run on the default EDT pipeline only");
   const SdfWorkspace ws = CarveWorkspace(workspace_dev, p.nx, p.ny, p.nz, ctx->variant, p.batch);
   if (workspace_dev == nullptr || workspace_bytes < ws.bytes)
@@ -458,9 +486,9 @@ int RunSdfPipeline(vgt_hip_ctx* ctx, const InT* input_dev, const vgt::SdfParams&
   if (events) VGT_TRY_HIP(hipEventRecord(events[0], s), "event record");
   VGT_TRY_HIP(LaunchPassOne<InT>(input_dev, ws, slices, 0, nullptr, s), "pass 1");
   if (events) VGT_TRY_HIP(hipEventRecord(events[1], s), "event record");
-  VGT_TRY_HIP(LaunchPassTwo(ws, slices, 0, ctx->variant, s), "Y pass");
+  VGT_TRY_HIP(LaunchPassTwo(ws, slices, 0, s), "Y pass");
   if (events) VGT_TRY_HIP(hipEventRecord(events[2], s), "event record");
-  VGT_TRY_HIP(vgt::LaunchPassXFinalize(ws.t32, sdf_dev, ws.minmax_enc, ws.sweep_scratch, p, ctx->variant, s), "X pass");
+  VGT_TRY_HIP(LaunchPassThree(ws, p, sdf_dev, s), "X pass");
   if (events) VGT_TRY_HIP(hipEventRecord(events[3], s), "event record");
   if (minmax_dev) VGT_TRY_HIP(vgt::LaunchDecodeMinMax(ws.minmax_enc, minmax_dev, s, p.batch), "min/max");
   return VGT_HIP_OK;
@@ -680,7 +708,7 @@ int64_t BatchGroup(int64_t batch, int64_t nx, int64_t ny, int64_t nz, size_t dev
 // overlap.  The grid is uploaded in X chunks (contiguous) on a copy stream and every chunk is scanned along Z and
 // swept along Y as soon as it has arrived; the X pass then runs over ranges of Y, and every finished range
 // (nx pieces of ny_range * nz floats) goes back on a second copy stream while the next range is computed.  Only
-// with the tiled line passes (the others need whole axes per launch).  The caller holds ctx->mutex.
+// with the default pipeline (the cross-check's line passes need whole axes per launch).  The caller holds ctx->mutex.
 constexpr int kPipelineChunks = 8;
 std::atomic<int64_t> g_host_pipeline_min_voxels{int64_t{1} << 27};
 
@@ -690,7 +718,7 @@ bool CanPipelineFromHost(const vgt_hip_ctx* ctx, const vgt::SdfParams& p)
   // smallest grid that is pipelined: 2^27 voxels (testing builds: vgt_hip_testing_set_host_pipeline_min_voxels lowers
   // it so that small grids take this path, a negative value turns the pipeline off)
   const int64_t min_voxels = g_host_pipeline_min_voxels.load();
-  if (min_voxels < 0 || !vgt::LinePassesTakeRanges(p, ctx->variant)) return false;
+  if (min_voxels < 0 || ctx->variant != 0) return false;
   return p.nx >= 4 * kPipelineChunks && p.ny >= 4 * kPipelineChunks && p.nx * p.ny * p.nz >= min_voxels;
 }
 
@@ -734,7 +762,7 @@ int SdfFromHostPipelined(vgt_hip_ctx* ctx, const InT* input_host, InT* in_dev, c
     part.nx = x_begin(c + 1) - x_begin(c);
     VGT_TRY_HIP(hipStreamWaitEvent(s, uploaded[c], 0), "wait for a chunk of the upload");
     VGT_TRY_HIP(LaunchPassOne<InT>(in_dev, ws, part, x_begin(c), nullptr, s), "pass 1");
-    VGT_TRY_HIP(LaunchPassTwo(ws, part, x_begin(c), ctx->variant, s), "Y pass");
+    VGT_TRY_HIP(LaunchPassTwo(ws, part, x_begin(c), s), "Y pass");
   }
   // (everything up to here is enqueued and on its way: the moment to make the output array ready for the downloads)
   before_downloads();
@@ -742,7 +770,7 @@ int SdfFromHostPipelined(vgt_hip_ctx* ctx, const InT* input_host, InT* in_dev, c
   for (int c = 0; c < kPipelineChunks; c++)
   {
     const int64_t y0 = y_begin(c), rows = y_begin(c + 1) - y0;
-    VGT_TRY_HIP(vgt::LaunchPassXFinalizeRange(ws.t32, sdf_dev, ws.minmax_enc, ws.sweep_scratch, p, ctx->variant, y0, rows, s),
+    VGT_TRY_HIP(vgt::LaunchPassXFinalizeRange(ws.t32, sdf_dev, ws.minmax_enc, ws.sweep_scratch, p, y0, rows, s),
                 "X pass");
     VGT_TRY_HIP(hipEventRecord(computed[c], s), "event record");
     VGT_TRY_HIP(hipStreamWaitEvent(ctx->copy_out, computed[c], 0), "wait for a range of the field");
@@ -1206,7 +1234,7 @@ int vgt_hip_device_of(const vgt_hip_ctx* ctx) { return ctx ? ctx->device : -1; }
 int vgt_hip_set_edt_variant(vgt_hip_ctx* ctx, int variant)
 {
   if (!ctx || variant < 0 || variant > 1) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "invalid EDT variant");
-  ctx->variant = static_cast<vgt::EdtVariant>(variant);
+  ctx->variant = variant;
   return VGT_HIP_OK;
 }
 
@@ -1241,7 +1269,8 @@ int vgt_hip_testing_set_host_pipeline_min_voxels(int64_t min_voxels)
 
 int vgt_hip_testing_set_short_line_rows(int rows)
 {
-  vgt::SetShortLineRows(rows);
+  // 0 ... kShortLineRowsFewItems; negative: back to the defaults
+  g_short_line_override.store(rows < 0 ? -1 : (rows > vgt::kShortLineRowsFewItems ? vgt::kShortLineRowsFewItems : rows));
   return VGT_HIP_OK;
 }
 
@@ -1732,16 +1761,14 @@ int vgt_hip_retrieve_filtered_grid(vgt_hip_ctx* ctx, const vgt_hip_filter* filte
 size_t vgt_hip_sdf_workspace_bytes(int64_t nx, int64_t ny, int64_t nz)
 {
   if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
-  return CarveWorkspace(nullptr, nx, ny, nz, vgt::EdtVariant::kDefault).bytes;
+  return CarveWorkspace(nullptr, nx, ny, nz, 0).bytes;
 }
 
 size_t vgt_hip_sdf_workspace_bytes_for_variant(int64_t nx, int64_t ny, int64_t nz, int variant)
 {
   if (nx <= 0 || ny <= 0 || nz <= 0 || variant < 0 || variant > 1) return 0;
-#ifndef VGT_HIP_TESTING
-  if (variant != 0) return 0;  // the cross-check variants are not part of this build
-#endif
-  return CarveWorkspace(nullptr, nx, ny, nz, static_cast<vgt::EdtVariant>(variant)).bytes;
+  if (variant != 0 && !kHaveCrossCheck) return 0;  // the cross-check is not part of the product library
+  return CarveWorkspace(nullptr, nx, ny, nz, variant).bytes;
 }
 
 int vgt_hip_sdf_from_occupancy_f32(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx,
@@ -1784,7 +1811,7 @@ int vgt_hip_sdf_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t nx, in
 size_t vgt_hip_sdf_batch_workspace_bytes(int64_t batch, int64_t nx, int64_t ny, int64_t nz)
 {
   if (batch <= 0 || nx <= 0 || ny <= 0 || nz <= 0) return 0;
-  return CarveWorkspace(nullptr, nx, ny, nz, vgt::EdtVariant::kDefault, batch).bytes;
+  return CarveWorkspace(nullptr, nx, ny, nz, 0, batch).bytes;
 }
 
 int vgt_hip_sdf_batch_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t batch, int64_t nx, int64_t ny,
@@ -1822,7 +1849,7 @@ int vgt_hip_sdf_batch_from_occupancy_f32(vgt_hip_ctx* ctx, const float* const* o
   // Grids per launch: as many as the limits of a batch and a memory budget allow (the context keeps the buffers).
   const int64_t group = BatchGroup(batch, nx, ny, nz, size_t{2} << 30, n * 9);
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  const size_t ws_bytes = CarveWorkspace(nullptr, nx, ny, nz, ctx->variant, ctx->variant == vgt::EdtVariant::kDefault ? group : 1).bytes;
+  const size_t ws_bytes = CarveWorkspace(nullptr, nx, ny, nz, ctx->variant, ctx->variant == 0 ? group : 1).bytes;
   VGT_TRY_HIP(Reserve(&ctx->sdf_in, &ctx->sdf_in_bytes, static_cast<size_t>(group) * n * sizeof(float)), "allocate SDF input");
   VGT_TRY_HIP(Reserve(&ctx->sdf_out, &ctx->sdf_out_bytes, static_cast<size_t>(group) * n * sizeof(float) + static_cast<size_t>(group) * 2 * sizeof(float)),
               "allocate SDF output");
@@ -1856,7 +1883,7 @@ int vgt_hip_sdf_batch_from_occupancy_f32(vgt_hip_ctx* ctx, const float* const* o
       VGT_TRY_HIP(moved, "copy occupancy to device");
     }
     vgt::SdfParams p{nx, ny, nz, resolution, unknown_is_filled ? 1 : 0, add_virtual_border ? 1 : 0};
-    if (ctx->variant == vgt::EdtVariant::kDefault)
+    if (ctx->variant == 0)
     {
       p.batch = count;
       rc = RunSdfPipeline<float>(ctx, in_dev, p, out_dev, ctx->sdf_ws, ctx->sdf_ws_bytes, mm_dev, nullptr);
@@ -1864,7 +1891,7 @@ int vgt_hip_sdf_batch_from_occupancy_f32(vgt_hip_ctx* ctx, const float* const* o
     }
     else
     {
-      // (testing builds with a cross-check variant selected: grid by grid)
+      // (the testing library with the cross-check selected: grid by grid)
       for (int64_t b = 0; b < count; b++)
       {
         rc = RunSdfPipeline<float>(ctx, in_dev + static_cast<size_t>(b) * n, p, out_dev + static_cast<size_t>(b) * n,
@@ -1967,7 +1994,7 @@ static int RunCellsSdf(vgt_hip_ctx* ctx, vgt_hip_cells* c, int mode, int num_obj
               "cell predicate");
   vgt::SdfParams mask_params = p;
   mask_params.unknown_is_filled = 0;
-  // (the workspace was sized for the default pipeline: a cross-check variant set later needs more)
+  // (the workspace was sized for the default pipeline: the cross-check, selected later, needs more)
   const size_t need = CarveWorkspace(nullptr, c->nx, c->ny, c->nz, ctx->variant).bytes;
   if (need > c->workspace_bytes)
   {
@@ -2234,7 +2261,7 @@ int vgt_hip_cells_object_sdfs(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint
   // intermediate field, field, records).
   const int64_t group = BatchGroup(num_objects, nx, ny, nz, size_t{4} << 30, n * 10);
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  if (ctx->variant != vgt::EdtVariant::kDefault)
+  if (ctx->variant != 0)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "batches run on the default EDT pipeline only");
   hipStream_t s = ctx->stream;
   const size_t ws_bytes = CarveWorkspace(nullptr, nx, ny, nz, ctx->variant, group).bytes;
@@ -3170,19 +3197,13 @@ int vgt_hip_sdf_slab_finish_dev(vgt_hip_ctx* ctx, int64_t nx, int64_t ny, int64_
   VGT_TRY_HIP(vgt::LaunchInitMinMax(ws.minmax_enc, s), "init min/max");
   VGT_TRY_HIP(timer.Mark(0, s), "event record");
   if (slot) VGT_TRY_HIP(hipEventRecord(slot[4], s), "event record");
-  if (ws.records)
-    VGT_TRY_HIP(vgt::LaunchSlabRecordFixup(ws.records, static_cast<const vgt::SlabLineCarry*>(carries_dev), p, s),
-                "slab fix-up");
-#ifdef VGT_HIP_TESTING
-  else
-    VGT_TRY_HIP(vgt::LaunchSlabFixup(ws.t16, static_cast<const vgt::SlabLineCarry*>(carries_dev), p, s), "slab fix-up");
-#endif
+  VGT_TRY_HIP(LaunchSlabFixup(ws, static_cast<const vgt::SlabLineCarry*>(carries_dev), p, s), "slab fix-up");
   VGT_TRY_HIP(timer.Mark(1, s), "event record");
   if (slot) VGT_TRY_HIP(hipEventRecord(slot[5], s), "event record");
-  VGT_TRY_HIP(LaunchPassTwo(ws, p, 0, ctx->variant, s), "Y pass");
+  VGT_TRY_HIP(LaunchPassTwo(ws, p, 0, s), "Y pass");
   VGT_TRY_HIP(timer.Mark(2, s), "event record");
   if (slot) VGT_TRY_HIP(hipEventRecord(slot[6], s), "event record");
-  VGT_TRY_HIP(vgt::LaunchPassXFinalize(ws.t32, sdf_dev, ws.minmax_enc, ws.sweep_scratch, p, ctx->variant, s), "X pass");
+  VGT_TRY_HIP(LaunchPassThree(ws, p, sdf_dev, s), "X pass");
   VGT_TRY_HIP(timer.Mark(3, s), "event record");
   if (slot)
   {

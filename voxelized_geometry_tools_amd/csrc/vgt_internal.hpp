@@ -23,13 +23,13 @@ namespace vgt
 hipStream_t ContextStream(const vgt_hip_ctx* ctx);
 
 // Intermediate encodings of the signed Euclidean distance transform.
-//  pass 1 (Z scan)  -> int16: +d for a free voxel, -d for a filled voxel, d = distance in
-//                      voxels along Z to the nearest voxel of the OTHER class,
-//                      |value| == kInf16 when the line holds no such voxel.
-//  pass 2 (Y pass)  -> int32: +-(squared distance in the YZ plane), kInf32 when none (two's complement between the
-//                      brute-force passes, sign and magnitude between the sweep passes: the Y and X passes of one
-//                      extraction are always of the same variant).
+//  pass 1 (Z)       -> class records (ClassRecord below): the classes of 64 voxels of a Z line and where the nearest
+//                      class change outside them is; the distance along Z to the nearest voxel of the OTHER class
+//                      follows from them, kInf16 or more when the line holds no such voxel.
+//  pass 2 (Y pass)  -> int32, sign and magnitude: bit 31 = the voxel is filled, bits 0-30 = squared distance in the YZ
+//                      plane, kInf32 when none.
 //  pass 3 (X pass)  -> float SDF.
+// (The testing library's cross-check pipeline has encodings of its own -- an int16 field after pass 1 --: edt_crosscheck.hpp.)
 constexpr int16_t kInf16 = 32767;
 constexpr int32_t kInf32 = 0x7fffffff;
 // Largest supported extent per axis: keeps every squared distance (<= 3*kMaxExtent^2)
@@ -111,27 +111,15 @@ struct SlabLineCarry
   int16_t prev_filled, next_filled, prev_free, next_free;
 };
 
-// kDefault: class records (pass 1, edt_record_kernels.hip) + lane-per-line sweep passes, Felzenszwalb-Huttenlocher
-// stacks with their tops in LDS (edt_sweep_kernels.hip; any extent).  kBruteForce (testing library only): the one
-// independent cross-check -- an int16 Z scan and a pruned outward search per voxel straight from HBM (edt_kernels.hip).
-// Both exact.  (Earlier rounds' other pipelines -- LDS-tiled envelopes, the int16-fed sweeps -- are in the git history
-// and profiles/r2 ... r5/experiments.md.)
-enum class EdtVariant : int { kDefault = 0, kBruteForce = 1 };
+// The pipeline: class records (pass 1, edt_record_kernels.hip) + lane-per-line sweep passes, Felzenszwalb-Huttenlocher
+// stacks with their tops in LDS (edt_sweep_kernels.hip; any extent), short-line kernels for lines of few rows
+// (edt_short_kernels.hip).  (Earlier rounds' other pipelines -- LDS-tiled envelopes, the int16-fed sweeps -- are in the
+// git history and profiles/r2 ... r5/experiments.md.)
 
-// --- launchers (edt_kernels.hip).  All asynchronous on `stream`. ---
-// Z scan: occupancy (float) or mask (u8) -> int16 signed 1-D distance.
-// `summary` (optional) receives one SlabLineSummary per (x, y) line.
-hipError_t LaunchScanZFromOccupancy(const float* occupancy, int16_t* out16, const SdfParams& p,
-                                    SlabLineSummary* summary, hipStream_t stream);
-hipError_t LaunchScanZFromMask(const uint8_t* mask, int16_t* out16, const SdfParams& p,
-                                SlabLineSummary* summary, hipStream_t stream);
-// Multi-GPU: folds the carries of the other slabs into the slab-local pass-1 distances, in place.
-hipError_t LaunchFinalizeCheck(int64_t first, int64_t count, double resolution,
-                               unsigned long long* result_dev, hipStream_t stream);
+// --- launchers of the distance transform.  All asynchronous on `stream`. ---
+// Multi-GPU (edt_kernels.hip): per-line carries of slab `rank` from the gathered summaries of all `world` slabs.
 hipError_t LaunchSlabCarries(const SlabLineSummary* summaries, int world, int rank, int64_t lines, int64_t nz_global,
                              SlabLineCarry* carries, hipStream_t stream);
-hipError_t LaunchSlabFixup(int16_t* io16, const SlabLineCarry* carries, const SdfParams& p,
-                           hipStream_t stream);
 // Pass 1 of the default pipeline (edt_record_kernels.hip): occupancy (float) or mask (u8) -> class records
 // (ClassRecordBytes bytes).  `summary` (optional, multi-GPU) receives one SlabLineSummary per (x, y) line; lines that
 // hold one class are then marked by LaunchSlabRecordFixup, which folds the other slabs' carries into the records.
@@ -151,15 +139,11 @@ struct SweepScratch
 // Y pass of the default pipeline: class records -> int32 signed squared distance (edt_sweep_kernels.hip).
 hipError_t LaunchPassYSweepRecords(const ClassRecord* records, int32_t* out32, SweepScratch scratch, const SdfParams& p,
                                    hipStream_t stream);
-// Y pass: int16 -> int32 signed squared distance.
+// X pass + finalize (edt_kernels.hip: the short-line kernels or the sweeps, by the length of the lines): int32 -> float
+// SDF, min/max folded into minmax_enc (2 x uint32, order-preserving encoding, must be pre-initialised by InitMinMax).
 // `scratch`: SweepPassScratchBytes bytes (part of the SDF workspace).
-hipError_t LaunchPassY(const int16_t* in16, int32_t* out32, SweepScratch scratch, const SdfParams& p,
-                       EdtVariant variant, hipStream_t stream);
-// X pass + finalize: int32 -> float SDF, min/max folded into minmax_enc (2 x uint32,
-// order-preserving encoding, must be pre-initialised by InitMinMax).
-hipError_t LaunchPassXFinalize(const int32_t* in32, float* sdf, uint32_t* minmax_enc,
-                               SweepScratch scratch, const SdfParams& p, EdtVariant variant,
-                               hipStream_t stream);
+hipError_t LaunchPassXFinalize(const int32_t* in32, float* sdf, uint32_t* minmax_enc, SweepScratch scratch,
+                               const SdfParams& p, hipStream_t stream);
 // Lines of at most kShortLineRows rows take the short-line kernels (edt_short_kernels.hip: the whole line in registers,
 // exhaustive search) instead of the sweeps; same encodings, same results.  ShortLineRows() is the limit in force for
 // the X pass: kShortLineRows, or what a testing build was told (vgt_hip_testing_set_short_line_rows; 0 = sweeps for
@@ -170,6 +154,7 @@ constexpr int kShortLineRows = 64;
 constexpr int kShortLineRowsFewItems = 128;
 constexpr int64_t kFewLineItems = 1024;
 // What a testing build was told (vgt_hip_testing_set_short_line_rows), -1 = nothing (the product library: always).
+// Defined next to that hook, in vgt_hip_capi.hip.
 int ShortLineOverride();
 inline int ShortLineRows()
 {
@@ -182,19 +167,20 @@ inline int ShortLineLimit(int64_t items)
   if (told >= 0) return told;  // (a testing build was told: that limit, whatever the item count)
   return items <= kFewLineItems ? kShortLineRowsFewItems : kShortLineRows;
 }
-#ifdef VGT_HIP_TESTING
-void SetShortLineRows(int rows);  // 0 ... kShortLineRowsFewItems; negative: back to the defaults
-#endif
 hipError_t LaunchPassYShortRecords(const ClassRecord* records, int32_t* out32, const SdfParams& p, hipStream_t stream);
 hipError_t LaunchPassXShortFinalizeRange(const int32_t* in32, float* sdf, uint32_t* minmax_enc, const SdfParams& p,
                                          int64_t outer_begin, int64_t outer_count, hipStream_t stream);
-// For callers that pipeline parts of a grid: the Y pass treats X slices independently (call LaunchPassY with nx =
-// slices of a contiguous part), and the X pass can be launched over a range of Y positions (full-grid pointers and
-// extents in `p`; outer_count < 0: the whole axis).  LinePassesTakeRanges: whether `variant` supports that for `p`.
-bool LinePassesTakeRanges(const SdfParams& p, EdtVariant variant);
+// For callers that pipeline parts of a grid: the Y pass treats X slices independently (call LaunchPassYSweepRecords
+// with nx = slices of a contiguous part), and the X pass can be launched over a range of Y positions (full-grid
+// pointers and extents in `p`; outer_count < 0: the whole axis).
 hipError_t LaunchPassXFinalizeRange(const int32_t* in32, float* sdf, uint32_t* minmax_enc, SweepScratch scratch,
-                                    const SdfParams& p, EdtVariant variant, int64_t outer_begin, int64_t outer_count,
-                                    hipStream_t stream);
+                                    const SdfParams& p, int64_t outer_begin, int64_t outer_count, hipStream_t stream);
+// The sweeps' own X pass, whatever the length of the lines (edt_sweep_kernels.hip).
+hipError_t LaunchPassXSweepFinalizeRange(const int32_t* in32, float* sdf, uint32_t* minmax_enc, SweepScratch scratch,
+                                         const SdfParams& p, int64_t outer_begin, int64_t outer_count_or_all,
+                                         hipStream_t stream);
+hipError_t LaunchPassXSweepFinalize(const int32_t* in32, float* sdf, uint32_t* minmax_enc, SweepScratch scratch,
+                                    const SdfParams& p, hipStream_t stream);
 // Scratch for the lane-per-line sweep passes (edt_sweep_kernels.hip): work counter, spilled stack entries and sign
 // words of the workgroups in flight.
 size_t SweepPassScratchBytes(int64_t nx, int64_t ny, int64_t nz, int64_t batch = 1);
