@@ -3,6 +3,7 @@
 #include "../../include/vgt_hip.h"
 
 #include "vgt_internal.hpp"
+#include "device_memory.hpp"
 #include "edt_crosscheck.hpp"
 #include "host_pages.hpp"
 
@@ -32,8 +33,7 @@ struct UploadLane
   std::mutex mutex;
   hipStream_t stream = nullptr;
   hipEvent_t after_ctx = nullptr;  // orders the lane behind what the context's stream holds (grid zeroing)
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
+  vgt::DeviceCache stage;
   // Page-locked host buffer the caller's cloud is copied to first: a 12-MB cloud from pageable memory goes through the
   // runtime's bounce buffers in 5 - 12 ms, page-locking the caller's buffer per call serialises in the driver when
   // several clouds arrive at once; a copy into a buffer that is locked once costs about a millisecond, in parallel
@@ -53,9 +53,8 @@ struct vgt_hip_ctx
   std::mutex mutex;              // serialises enqueues + the staging buffer
   UploadLane lanes[kUploadLanes];
   std::atomic<unsigned> next_lane{0};
-  void* ray_scratch = nullptr;   // sort scratch of raycasts of device-resident clouds (context stream)
-  size_t ray_scratch_bytes = 0;
-  float* minmax_out = nullptr;   // 2 floats (device) for host-facing SDF calls
+  vgt::DeviceCache ray_scratch;  // sort scratch of raycasts of device-resident clouds (context stream)
+  vgt::DeviceCache minmax_out;   // 2 floats (device) for host-facing SDF calls
   int variant = 0;               // 0: the default EDT pipeline; 1: the cross-check (vgt_hip_set_edt_variant, testing library)
   // deferred per-kernel timing (vgt_hip_timing_start / _stop): 8 events per SDF call
   std::vector<hipEvent_t> timing_events;
@@ -65,15 +64,9 @@ struct vgt_hip_ctx
   // Device buffers of the host-pointer SDF entry points (input, field, workspace), kept across calls
   // and grown on demand: a caller that extracts fields repeatedly pays for hipMalloc / hipFree once.
   // vgt_hip_trim() gives them back.
-  void* sdf_in = nullptr;
-  size_t sdf_in_bytes = 0;
-  void* sdf_out = nullptr;
-  size_t sdf_out_bytes = 0;
-  void* sdf_ws = nullptr;
-  size_t sdf_ws_bytes = 0;
+  vgt::DeviceCache sdf_in, sdf_out, sdf_ws;
   // Scratch of the component labelling (union-find labels + scan counts), kept like the buffers above
-  void* component_ws = nullptr;
-  size_t component_ws_bytes = 0;
+  vgt::DeviceCache component_ws;
   // Page-locked staging ring of the batched downloads (DownloadToHostArrays): kStagingSlots slots of kStagingSlotBytes,
   // allocated by the first such call, kept until vgt_hip_trim / vgt_hip_destroy; one event per slot.
   void* host_staging = nullptr;
@@ -86,12 +79,7 @@ struct vgt_hip_ctx
   // Device buffers of destroyed tracking-grid / filter-grid handles, kept for the next handle of the same size (the
   // voxelizer allocates both per call, S/cuda_voxelization_helpers.cu:641-658,701-708; a hipMalloc + hipFree pair of
   // 128 MiB costs more than the raycast it serves).  Guarded by `mutex`; vgt_hip_trim and vgt_hip_destroy free them.
-  struct PooledBuffer
-  {
-    void* ptr;
-    size_t bytes;
-  };
-  std::vector<PooledBuffer> pool;
+  std::vector<vgt::DeviceCache> pool;
   size_t pool_bytes = 0;
   bool pool_closed = false;  // set by vgt_hip_destroy: handles destroyed later free their buffers themselves
   // Z-slab calls: which slab a carries buffer was computed for (vgt_hip_sdf_slab_carries_dev decodes the gathered
@@ -112,7 +100,7 @@ struct vgt_hip_grids
 {
   vgt_hip_ctx* ctx = nullptr;
   int device = -1;
-  int32_t* dev = nullptr;
+  vgt::DeviceCache dev;  // int32 counts
   int64_t num_cells = 0;
   int32_t num_grids = 0;
 };
@@ -121,7 +109,7 @@ struct vgt_hip_filter
 {
   vgt_hip_ctx* ctx = nullptr;
   int device = -1;
-  float* dev = nullptr;
+  vgt::DeviceCache dev;  // floats
   int64_t num_cells = 0;
   // vgt_hip_filter_grid_create_deferred: the upload runs on the context's copy stream; `uploaded` is recorded behind it
   // and the caller's array stays page-locked (`pin`, a ScopedHostPin) until a call has waited for the copy
@@ -139,22 +127,15 @@ struct vgt_hip_cells
   int64_t nx = 0, ny = 0, nz = 0;
   int cell_bytes = 0;
   int object_id_offset = -1;
-  void* records = nullptr;      // [num_cells] records of cell_bytes bytes
-  uint8_t* mask = nullptr;      // [num_cells] predicate result, the Z scan's input
-  float* sdf = nullptr;         // [num_cells]
-  float* sdf_named = nullptr;   // [num_cells], allocated by the first free-and-named extraction
-  void* workspace = nullptr;
-  size_t workspace_bytes = 0;
-  uint32_t* objects = nullptr;  // object list of the current call
-  size_t objects_capacity = 0;
-  uint32_t* scalar = nullptr;   // two uint32: result of a reduction + found flag
+  vgt::DeviceTemp records;      // [num_cells] records of cell_bytes bytes
+  vgt::DeviceTemp mask;         // [num_cells] uint8 predicate result, the Z scan's input
+  vgt::DeviceTemp sdf;          // [num_cells] floats
+  vgt::DeviceCache sdf_named;   // [num_cells] floats, allocated by the first free-and-named extraction
+  vgt::DeviceCache workspace;
+  vgt::DeviceCache objects;     // uint32 object list of the current call
+  vgt::DeviceTemp scalar;       // two uint32: result of a reduction + found flag
   // vgt_hip_cells_object_sdfs: masks, fields (+ extrema) and workspace of a batch of per-object extractions (grow-only)
-  void* batch_masks = nullptr;
-  size_t batch_masks_bytes = 0;
-  void* batch_sdf = nullptr;
-  size_t batch_sdf_bytes = 0;
-  void* batch_ws = nullptr;
-  size_t batch_ws_bytes = 0;
+  vgt::DeviceCache batch_masks, batch_sdf, batch_ws;
 };
 
 namespace
@@ -210,64 +191,55 @@ size_t AlignUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Handle buffers come from / go back to the context's pool (at most kPoolLimit bytes are kept).
 constexpr size_t kPoolLimit = size_t{4} << 30;
-hipError_t PoolAllocate(vgt_hip_ctx* ctx, void** ptr, size_t bytes)
+hipError_t PoolAllocate(vgt_hip_ctx* ctx, vgt::DeviceCache* buffer, size_t bytes)
 {
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
     for (size_t i = 0; i < ctx->pool.size(); i++)
-      if (ctx->pool[i].bytes == bytes)
+      if (ctx->pool[i].bytes() == bytes)
       {
-        *ptr = ctx->pool[i].ptr;
+        *buffer = std::move(ctx->pool[i]);
         ctx->pool_bytes -= bytes;
         ctx->pool.erase(ctx->pool.begin() + static_cast<std::ptrdiff_t>(i));
         return hipSuccess;
       }
   }
-  return hipMalloc(ptr, bytes);
+  return buffer->Reserve(bytes);
 }
 // (the caller has made sure no work uses the buffer any more)
-void PoolRelease(vgt_hip_ctx* ctx, void* ptr, size_t bytes)
+void PoolRelease(vgt_hip_ctx* ctx, vgt::DeviceCache* buffer)
 {
-  if (!ptr) return;
+  if (!buffer->data()) return;
   if (ctx && !ctx->destroyed.load())
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    if (!ctx->pool_closed && ctx->pool_bytes + bytes <= kPoolLimit && ctx->pool.size() < 16)
+    if (!ctx->pool_closed && ctx->pool_bytes + buffer->bytes() <= kPoolLimit && ctx->pool.size() < 16)
     {
-      ctx->pool.push_back({ptr, bytes});
-      ctx->pool_bytes += bytes;
+      ctx->pool_bytes += buffer->bytes();
+      ctx->pool.push_back(std::move(*buffer));
       return;
     }
   }
-  (void)hipFree(ptr);
+  (void)buffer->Release();
 }
 void FreePool(vgt_hip_ctx* ctx)
 {
-  for (const auto& b : ctx->pool) (void)hipFree(b.ptr);
   ctx->pool.clear();
   ctx->pool_bytes = 0;
 }
 
-// Grow-only device buffer.
-hipError_t Reserve(void** ptr, size_t* have, size_t need)
+// Keeps the first error of what was enqueued on `s`, and waits for the stream whatever happened: the buffers that the
+// enqueued work uses are about to go.
+hipError_t DrainKeepingFirst(hipStream_t s, hipError_t err)
 {
-  if (*have >= need && *ptr) return hipSuccess;
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr;
-  *have = 0;
-  const hipError_t err = hipMalloc(ptr, need);
-  if (err == hipSuccess) *have = need;
-  return err;
+  const hipError_t sync = hipStreamSynchronize(s);
+  return err == hipSuccess ? sync : err;
 }
 
 void FreeCachedSdfBuffers(vgt_hip_ctx* ctx)
 {
-  for (void** p : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws})
-  {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  ctx->sdf_in_bytes = ctx->sdf_out_bytes = ctx->sdf_ws_bytes = ctx->ray_scratch_bytes = ctx->component_ws_bytes = 0;
+  for (vgt::DeviceCache* b : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws})
+    (void)b->Release();
   if (ctx->host_staging) (void)hipHostFree(ctx->host_staging);
   ctx->host_staging = nullptr;
   for (hipEvent_t e : ctx->staging_events)
@@ -670,11 +642,7 @@ hipError_t MoveThroughRing(vgt_hip_ctx* ctx, const std::vector<HostArrayCopy>& a
   }
   if (err != hipSuccess) failed.store(1);
   for (auto& th : pool) th.join();
-  if (to_host)
-  {
-    const hipError_t sync = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = sync;
-  }
+  if (to_host) err = DrainKeepingFirst(s, err);
   if (err == hipSuccess && failed.load()) err = hipErrorUnknown;
   return err;
 }
@@ -726,8 +694,8 @@ template <typename InT>
 int SdfFromHostPipelined(vgt_hip_ctx* ctx, const InT* input_host, InT* in_dev, const vgt::SdfParams& p,
                          float* sdf_dev, float* sdf_host, const std::function<void()>& before_downloads)
 {
-  const SdfWorkspace ws = CarveWorkspace(ctx->sdf_ws, p.nx, p.ny, p.nz, ctx->variant);
-  if (ctx->sdf_ws_bytes < ws.bytes) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "SDF workspace too small");
+  const SdfWorkspace ws = CarveWorkspace(ctx->sdf_ws.data(), p.nx, p.ny, p.nz, ctx->variant);
+  if (ctx->sdf_ws.bytes() < ws.bytes) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "SDF workspace too small");
   if (!ctx->copy_in) VGT_TRY_HIP(hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking), "create stream");
   if (!ctx->copy_out) VGT_TRY_HIP(hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking), "create stream");
   while (ctx->pipeline_events.size() < static_cast<size_t>(2 * kPipelineChunks + 1))
@@ -779,7 +747,7 @@ int SdfFromHostPipelined(vgt_hip_ctx* ctx, const InT* input_host, InT* in_dev, c
                                  hipMemcpyDeviceToHost, ctx->copy_out),
                 "copy SDF to host");
   }
-  VGT_TRY_HIP(vgt::LaunchDecodeMinMax(ws.minmax_enc, ctx->minmax_out, s), "min/max");
+  VGT_TRY_HIP(vgt::LaunchDecodeMinMax(ws.minmax_enc, ctx->minmax_out.as<float>(), s), "min/max");
   return VGT_HIP_OK;
 }
 
@@ -804,26 +772,27 @@ int SdfFromHost(vgt_hip_ctx* ctx, const InT* input_host, const vgt::SdfParams& p
     if (!pin_out) pin_out.reset(new ScopedHostPin(sdf_host, nvox * sizeof(float)));
   };
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipError_t err = Reserve(&ctx->sdf_in, &ctx->sdf_in_bytes, nvox * sizeof(InT));
-  if (err == hipSuccess) err = Reserve(&ctx->sdf_out, &ctx->sdf_out_bytes, nvox * sizeof(float));
-  if (err == hipSuccess) err = Reserve(&ctx->sdf_ws, &ctx->sdf_ws_bytes, ws_bytes);
+  hipError_t err = ctx->sdf_in.Reserve(nvox * sizeof(InT));
+  if (err == hipSuccess) err = ctx->sdf_out.Reserve(nvox * sizeof(float));
+  if (err == hipSuccess) err = ctx->sdf_ws.Reserve(ws_bytes);
   if (err != hipSuccess)
   {
     FreeCachedSdfBuffers(ctx);
     return FailHip("allocate SDF buffers", err);
   }
-  InT* in_dev = static_cast<InT*>(ctx->sdf_in);
-  float* sdf_dev = static_cast<float*>(ctx->sdf_out);
+  InT* in_dev = ctx->sdf_in.as<InT>();
+  float* sdf_dev = ctx->sdf_out.as<float>();
+  float* const minmax_dev = ctx->minmax_out.as<float>();
   hipStream_t s = ctx->stream;
   int result = VGT_HIP_OK;
   if (CanPipelineFromHost<InT>(ctx, p))
   {
-    if (!ctx->minmax_out) return Fail(VGT_HIP_ERR_RUNTIME, "context has no extrema buffer");
+    if (!minmax_dev) return Fail(VGT_HIP_ERR_RUNTIME, "context has no extrema buffer");
     result = SdfFromHostPipelined<InT>(ctx, input_host, in_dev, p, sdf_dev, sdf_host, lock_output);
     float mm[2] = {0.0f, 0.0f};
     if (result == VGT_HIP_OK)
     {
-      err = hipMemcpyAsync(mm, ctx->minmax_out, sizeof(mm), hipMemcpyDeviceToHost, s);
+      err = hipMemcpyAsync(mm, minmax_dev, sizeof(mm), hipMemcpyDeviceToHost, s);
       if (err != hipSuccess) result = FailHip("copy extrema to host", err);
     }
     // drain all three streams whatever happened: the caller's arrays are about to be unpinned
@@ -854,8 +823,8 @@ int SdfFromHost(vgt_hip_ctx* ctx, const InT* input_host, const vgt::SdfParams& p
     char* const down = up + kStagingSlotBytes;
     std::memcpy(up, input_host, in_bytes);
     float* const field = reinterpret_cast<float*>(down);
-    result = RunSdfPipeline<InT>(ctx, reinterpret_cast<const InT*>(up), p, field, ctx->sdf_ws, ctx->sdf_ws_bytes,
-                                 field + nvox, nullptr);
+    result = RunSdfPipeline<InT>(ctx, reinterpret_cast<const InT*>(up), p, field, ctx->sdf_ws.data(),
+                                 ctx->sdf_ws.bytes(), field + nvox, nullptr);
     err = hipStreamSynchronize(s);  // (whatever happened: the ring is reused by the next call)
     if (result == VGT_HIP_OK && err != hipSuccess) result = FailHip("small-map SDF extraction", err);
     if (result == VGT_HIP_OK)
@@ -872,14 +841,13 @@ int SdfFromHost(vgt_hip_ctx* ctx, const InT* input_host, const vgt::SdfParams& p
   if (err != hipSuccess)
     result = FailHip("copy occupancy to device", err);
   else
-    result = RunSdfPipeline<InT>(ctx, in_dev, p, sdf_dev, ctx->sdf_ws, ctx->sdf_ws_bytes, ctx->minmax_out, nullptr);
+    result = RunSdfPipeline<InT>(ctx, in_dev, p, sdf_dev, ctx->sdf_ws.data(), ctx->sdf_ws.bytes(), minmax_dev, nullptr);
   if (result == VGT_HIP_OK)
   {
     float mm[2] = {0.0f, 0.0f};
     lock_output();  // (upload and kernels are on their way)
     err = hipMemcpyAsync(sdf_host, sdf_dev, nvox * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(mm, ctx->minmax_out, sizeof(mm), hipMemcpyDeviceToHost, s);
+    if (err == hipSuccess) err = hipMemcpyAsync(mm, minmax_dev, sizeof(mm), hipMemcpyDeviceToHost, s);
     if (err == hipSuccess) err = hipStreamSynchronize(s);
     if (err != hipSuccess)
       result = FailHip("copy SDF to host", err);
@@ -918,9 +886,7 @@ void FreeUploadLanes(vgt_hip_ctx* ctx, bool destroy_streams)
   {
     std::lock_guard<std::mutex> lock(lane.mutex);
     if (lane.stream) (void)hipStreamSynchronize(lane.stream);
-    if (lane.stage) (void)hipFree(lane.stage);
-    lane.stage = nullptr;
-    lane.stage_bytes = 0;
+    (void)lane.stage.Release();
     if (lane.pinned) (void)hipHostFree(lane.pinned);
     lane.pinned = nullptr;
     lane.pinned_bytes = 0;
@@ -968,17 +934,14 @@ int UploadAndRun(vgt_hip_ctx* ctx, const void* host, size_t bytes, size_t scratc
   }
   // staging copy of the cloud, followed by the kernel's scratch (256-byte aligned)
   const size_t scratch_at = AlignUp(bytes, 256);
-  if (lane.stage_bytes < scratch_at + scratch_bytes)
+  if (lane.stage.bytes() < scratch_at + scratch_bytes)
   {
     VGT_TRY_HIP(hipStreamSynchronize(lane.stream), "drain before regrowing staging buffer");
-    if (lane.stage) VGT_TRY_HIP(hipFree(lane.stage), "free staging buffer");
-    lane.stage = nullptr;
-    lane.stage_bytes = 0;
+    VGT_TRY_HIP(lane.stage.Release(), "free staging buffer");
     const size_t total = scratch_at + scratch_bytes;
-    const size_t want = AlignUp(total + total / 4, 1 << 20);
-    VGT_TRY_HIP(hipMalloc(&lane.stage, want), "allocate staging buffer");
-    lane.stage_bytes = want;
+    VGT_TRY_HIP(lane.stage.Reserve(AlignUp(total + total / 4, 1 << 20)), "allocate staging buffer");
   }
+  char* const stage = lane.stage.as<char>();
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
     VGT_TRY_HIP(hipEventRecord(lane.after_ctx, ctx->stream), "record event");
@@ -1012,7 +975,7 @@ int UploadAndRun(vgt_hip_ctx* ctx, const void* host, size_t bytes, size_t scratc
         {
           const size_t piece = std::min(kPiece, bytes - off);
           std::memcpy(static_cast<char*>(lane.pinned) + off, static_cast<const char*>(host) + off, piece);
-          VGT_TRY_HIP(hipMemcpyAsync(static_cast<char*>(lane.stage) + off, static_cast<char*>(lane.pinned) + off, piece,
+          VGT_TRY_HIP(hipMemcpyAsync(stage + off, static_cast<char*>(lane.pinned) + off, piece,
                                      hipMemcpyHostToDevice, lane.stream),
                       "Failed to copy points to the device");
         }
@@ -1021,9 +984,9 @@ int UploadAndRun(vgt_hip_ctx* ctx, const void* host, size_t bytes, size_t scratc
     }
   }
   if (source)
-    VGT_TRY_HIP(hipMemcpyAsync(lane.stage, source, bytes, hipMemcpyHostToDevice, lane.stream),
+    VGT_TRY_HIP(hipMemcpyAsync(stage, source, bytes, hipMemcpyHostToDevice, lane.stream),
                 "Failed to copy points to the device");
-  VGT_TRY_HIP(launch(lane.stage, static_cast<char*>(lane.stage) + scratch_at, lane.stream),
+  VGT_TRY_HIP(launch(stage, stage + scratch_at, lane.stream),
               "Failed to dispatch raycast kernel");
   VGT_TRY_HIP(hipStreamSynchronize(lane.stream), "raycast");
   return VGT_HIP_OK;
@@ -1042,18 +1005,19 @@ int SdfQueriesHost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t 
   if (num_queries == 0) return VGT_HIP_OK;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_queries);
-  float* sdf_dev = nullptr;
-  double* queries_dev = nullptr;
-  double* out_dev = nullptr;
-  uint8_t* has_dev = nullptr;
-  uint32_t* flag_dev = nullptr;
+  vgt::DeviceTemp sdf, queries, out, has, flag_word;
+  VGT_TRY_HIP(sdf.Allocate(n * sizeof(float)), what);
+  VGT_TRY_HIP(queries.Allocate(q * 3 * sizeof(double)), what);
+  VGT_TRY_HIP(out.Allocate(q * out_doubles * sizeof(double)), what);
+  VGT_TRY_HIP(has.Allocate(q), what);
+  VGT_TRY_HIP(flag_word.Allocate(256), what);
+  float* const sdf_dev = sdf.as<float>();
+  double* const queries_dev = queries.as<double>();
+  double* const out_dev = out.as<double>();
+  uint8_t* const has_dev = has.as<uint8_t>();
+  uint32_t* const flag_dev = flag_word.as<uint32_t>();
   uint32_t flag = 0;
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&sdf_dev), n * sizeof(float));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&queries_dev), q * 3 * sizeof(double));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&out_dev), q * out_doubles * sizeof(double));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&has_dev), q);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&flag_dev), 256);
-  if (err == hipSuccess)
+  hipError_t err;
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
     hipStream_t s = ctx->stream;
@@ -1066,12 +1030,8 @@ int SdfQueriesHost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t 
       err = hipMemcpyAsync(out_host, out_dev, q * out_doubles * sizeof(double), hipMemcpyDeviceToHost, s);
     if (err == hipSuccess && has_value_host) err = hipMemcpyAsync(has_value_host, has_dev, q, hipMemcpyDeviceToHost, s);
     if (err == hipSuccess) err = hipMemcpyAsync(&flag, flag_dev, sizeof(flag), hipMemcpyDeviceToHost, s);
-    const hipError_t sync = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = sync;
+    err = DrainKeepingFirst(s, err);
   }
-  for (void* p : {static_cast<void*>(sdf_dev), static_cast<void*>(queries_dev), static_cast<void*>(out_dev),
-                  static_cast<void*>(has_dev), static_cast<void*>(flag_dev)})
-    if (p) (void)hipFree(p);
   VGT_TRY_HIP(err, what);
   if (flag) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Window size for fine gradient is too large for SDF");
   return VGT_HIP_OK;
@@ -1134,7 +1094,7 @@ int vgt_hip_create(int device, int threads_per_block, vgt_hip_ctx** out_ctx)
   ctx->threads_per_block = threads_per_block;
   ctx->raycast_threads = raycast_threads;
   hipError_t err = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&ctx->minmax_out), 256);
+  if (err == hipSuccess) err = ctx->minmax_out.Reserve(256);
   if (err != hipSuccess)
   {
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1152,7 +1112,7 @@ void vgt_hip_destroy(vgt_hip_ctx* ctx)
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   FreeUploadLanes(ctx, true);
-  if (ctx->minmax_out) (void)hipFree(ctx->minmax_out);
+  (void)ctx->minmax_out.Release();
   FreeCachedSdfBuffers(ctx);
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
@@ -1169,7 +1129,6 @@ void vgt_hip_destroy(vgt_hip_ctx* ctx)
   ctx->copy_in = nullptr;
   ctx->copy_out = nullptr;
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  ctx->minmax_out = nullptr;
   ctx->timing_events.clear();
   ctx->own_stream = nullptr;
   ctx->stream = nullptr;
@@ -1245,17 +1204,16 @@ int vgt_hip_debug_finalize_check(vgt_hip_ctx* ctx, int64_t first_d2, int64_t cou
       first_d2 + count > (int64_t{1} << 31))
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "invalid finalize-check range");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  unsigned long long* result = nullptr;
-  VGT_TRY_HIP(hipMalloc(&result, 2 * sizeof(unsigned long long)), "allocate check result");
+  vgt::DeviceTemp result_dev;
+  VGT_TRY_HIP(result_dev.Allocate(2 * sizeof(unsigned long long)), "allocate check result");
+  unsigned long long* const result = result_dev.as<unsigned long long>();
   const unsigned long long init[2] = {0ull, ~0ull};
   hipError_t err = hipMemcpyAsync(result, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream);
   if (err == hipSuccess) err = vgt::LaunchFinalizeCheck(first_d2, count, resolution, result, ctx->stream);
   unsigned long long host[2] = {0ull, ~0ull};
   if (err == hipSuccess)
     err = hipMemcpyAsync(host, result, sizeof(host), hipMemcpyDeviceToHost, ctx->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(result);
-  VGT_TRY_HIP(err, "finalize check");
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "finalize check");
   *mismatches = host[0];
   *first_mismatch = host[1];
   return VGT_HIP_OK;
@@ -1316,15 +1274,14 @@ int vgt_hip_tracking_grids_create(vgt_hip_ctx* ctx, int64_t num_cells, int32_t n
   g->num_cells = num_cells;
   g->num_grids = num_grids;
   const size_t bytes = static_cast<size_t>(num_cells) * num_grids * 2 * sizeof(int32_t);
-  hipError_t err = PoolAllocate(ctx, reinterpret_cast<void**>(&g->dev), bytes);
+  hipError_t err = PoolAllocate(ctx, &g->dev, bytes);
   if (err == hipSuccess)
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemsetAsync(g->dev, 0, bytes, ctx->stream);
+    err = hipMemsetAsync(g->dev.data(), 0, bytes, ctx->stream);
   }
   if (err != hipSuccess)
   {
-    if (g->dev) (void)hipFree(g->dev);
     delete g;
     return FailHip("Failed to allocate tracking grids", err);
   }
@@ -1337,14 +1294,13 @@ void vgt_hip_tracking_grids_destroy(vgt_hip_grids* grids)
 {
   if (!grids) return;
   vgt_hip_ctx* const ctx = grids->ctx;
-  const size_t bytes = static_cast<size_t>(grids->num_cells) * grids->num_grids * 2 * sizeof(int32_t);
   // (the buffer goes back to the pool before the handle's reference, which may be the context's last, is dropped)
   (void)hipSetDevice(grids->device);
   if (ctx->destroyed.load())
     (void)hipDeviceSynchronize();
   else
     (void)hipStreamSynchronize(ctx->stream);
-  PoolRelease(ctx, grids->dev, bytes);
+  PoolRelease(ctx, &grids->dev);
   ReleaseChild(ctx, grids->device);
   delete grids;
 }
@@ -1365,7 +1321,7 @@ int64_t vgt_hip_tracking_grids_offset(const vgt_hip_grids* grids, size_t grid_in
 void* vgt_hip_tracking_grids_dev_ptr(const vgt_hip_grids* grids, size_t grid_index)
 {
   if (!grids || grid_index >= static_cast<size_t>(grids->num_grids)) return nullptr;
-  return grids->dev + static_cast<int64_t>(grid_index) * grids->num_cells * 2;
+  return grids->dev.as<int32_t>() + static_cast<int64_t>(grid_index) * grids->num_cells * 2;
 }
 
 int vgt_hip_tracking_grids_clear(vgt_hip_ctx* ctx, vgt_hip_grids* grids)
@@ -1375,7 +1331,7 @@ int vgt_hip_tracking_grids_clear(vgt_hip_ctx* ctx, vgt_hip_grids* grids)
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   std::lock_guard<std::mutex> lock(ctx->mutex);
   const size_t bytes = static_cast<size_t>(grids->num_cells) * grids->num_grids * 2 * sizeof(int32_t);
-  VGT_TRY_HIP(hipMemsetAsync(grids->dev, 0, bytes, ctx->stream), "clear tracking grids");
+  VGT_TRY_HIP(hipMemsetAsync(grids->dev.data(), 0, bytes, ctx->stream), "clear tracking grids");
   return VGT_HIP_OK;
 }
 
@@ -1409,17 +1365,13 @@ int vgt_hip_raycast_points_f32_dev(vgt_hip_ctx* ctx, vgt_hip_grids* grids, size_
   std::lock_guard<std::mutex> lock(ctx->mutex);
   // stream order protects the scratch: the next call's kernels queue behind this one's
   const size_t scratch_bytes = vgt::RaycastScratchBytes(num_points);
-  if (scratch_bytes > ctx->ray_scratch_bytes)
+  if (scratch_bytes > ctx->ray_scratch.bytes())
   {
     VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing raycast scratch");
-    if (ctx->ray_scratch) (void)hipFree(ctx->ray_scratch);
-    ctx->ray_scratch = nullptr;
-    ctx->ray_scratch_bytes = 0;
-    VGT_TRY_HIP(hipMalloc(&ctx->ray_scratch, scratch_bytes + scratch_bytes / 4), "allocate raycast scratch");
-    ctx->ray_scratch_bytes = scratch_bytes + scratch_bytes / 4;
+    VGT_TRY_HIP(ctx->ray_scratch.Reserve(scratch_bytes + scratch_bytes / 4), "allocate raycast scratch");
   }
   VGT_TRY_HIP(vgt::LaunchRaycastF32(points_xyz_dev, num_points, 3, g, tracking, ctx->raycast_threads,
-                                    ctx->ray_scratch, ctx->ray_scratch_bytes, ctx->stream),
+                                    ctx->ray_scratch.data(), ctx->ray_scratch.bytes(), ctx->stream),
               "Failed to dispatch raycast kernel");
   return VGT_HIP_OK;
 }
@@ -1553,18 +1505,17 @@ int vgt_hip_filter_grid_create(vgt_hip_ctx* ctx, int64_t num_cells, const float*
   f->device = ctx->device;
   f->num_cells = num_cells;
   const size_t bytes = static_cast<size_t>(num_cells) * sizeof(float);
-  hipError_t err = PoolAllocate(ctx, reinterpret_cast<void**>(&f->dev), bytes);
+  hipError_t err = PoolAllocate(ctx, &f->dev, bytes);
   if (err == hipSuccess)
   {
     // the caller's array is page-locked for the copy (a pageable 64 MiB copy is staged at a fifth of the link rate)
     const ScopedHostPin pin(occupancy_host, bytes);
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(f->dev, occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    err = hipMemcpyAsync(f->dev.data(), occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
   }
   if (err != hipSuccess)
   {
-    if (f->dev) (void)hipFree(f->dev);
     delete f;
     return FailHip("Failed to prepare filter grid", err);
   }
@@ -1604,7 +1555,7 @@ int vgt_hip_filter_grid_create_deferred(vgt_hip_ctx* ctx, int64_t num_cells, con
   f->device = ctx->device;
   f->num_cells = num_cells;
   const size_t bytes = static_cast<size_t>(num_cells) * sizeof(float);
-  hipError_t err = PoolAllocate(ctx, reinterpret_cast<void**>(&f->dev), bytes);
+  hipError_t err = PoolAllocate(ctx, &f->dev, bytes);
   if (err == hipSuccess) err = hipEventCreateWithFlags(&f->uploaded, hipEventDisableTiming);
   if (err == hipSuccess)
   {
@@ -1614,7 +1565,8 @@ int vgt_hip_filter_grid_create_deferred(vgt_hip_ctx* ctx, int64_t num_cells, con
     // (a pooled buffer may still be read by work queued on the context's stream: the copy starts behind it)
     if (err == hipSuccess) err = hipEventRecord(f->uploaded, ctx->stream);
     if (err == hipSuccess) err = hipStreamWaitEvent(ctx->copy_in, f->uploaded, 0);
-    if (err == hipSuccess) err = hipMemcpyAsync(f->dev, occupancy_host, bytes, hipMemcpyHostToDevice, ctx->copy_in);
+    if (err == hipSuccess)
+      err = hipMemcpyAsync(f->dev.data(), occupancy_host, bytes, hipMemcpyHostToDevice, ctx->copy_in);
     if (err == hipSuccess) err = hipEventRecord(f->uploaded, ctx->copy_in);
     f->upload_pending = err == hipSuccess;
   }
@@ -1627,7 +1579,6 @@ int vgt_hip_filter_grid_create_deferred(vgt_hip_ctx* ctx, int64_t num_cells, con
     }
     delete static_cast<ScopedHostPin*>(f->pin);
     if (f->uploaded) (void)hipEventDestroy(f->uploaded);
-    if (f->dev) (void)hipFree(f->dev);
     delete f;
     return FailHip("Failed to prepare filter grid", err);
   }
@@ -1648,7 +1599,7 @@ void vgt_hip_filter_grid_destroy(vgt_hip_filter* filter)
     (void)hipDeviceSynchronize();
   else
     (void)hipStreamSynchronize(ctx->stream);
-  PoolRelease(ctx, filter->dev, static_cast<size_t>(filter->num_cells) * sizeof(float));
+  PoolRelease(ctx, &filter->dev);
   ReleaseChild(ctx, filter->device);
   delete filter;
 }
@@ -1684,7 +1635,7 @@ void* vgt_hip_filter_grid_dev_ptr(const vgt_hip_filter* filter)
       return nullptr;
     }
   }
-  return filter->dev;
+  return filter->dev.data();
 }
 
 static int FilterImpl(vgt_hip_ctx* ctx, const vgt_hip_grids* grids, double percent_seen_free,
@@ -1699,9 +1650,9 @@ static int FilterImpl(vgt_hip_ctx* ctx, const vgt_hip_grids* grids, double perce
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   std::lock_guard<std::mutex> lock(ctx->mutex);
   VGT_TRY_HIP(OrderBehindUpload(ctx, filter), "order the filter behind the grid's upload");
-  VGT_TRY_HIP(vgt::LaunchFilter(grids->dev, grids->num_cells, grids->num_grids, percent_seen_free,
+  VGT_TRY_HIP(vgt::LaunchFilter(grids->dev.as<int32_t>(), grids->num_cells, grids->num_grids, percent_seen_free,
                                 outlier_points_threshold, num_cameras_seen_free, ratio_in_double,
-                                filter->dev, ctx->threads_per_block, ctx->stream),
+                                filter->dev.as<float>(), ctx->threads_per_block, ctx->stream),
               "Failed to dispatch filter kernel");
   return VGT_HIP_OK;
 }
@@ -1748,7 +1699,7 @@ int vgt_hip_retrieve_filtered_grid(vgt_hip_ctx* ctx, const vgt_hip_filter* filte
   const ScopedHostPin pin(host_out, bytes);
   std::lock_guard<std::mutex> lock(ctx->mutex);
   VGT_TRY_HIP(OrderBehindUpload(ctx, filter), "order the download behind the grid's upload");
-  VGT_TRY_HIP(hipMemcpyAsync(host_out, filter->dev, bytes, hipMemcpyDeviceToHost, ctx->stream),
+  VGT_TRY_HIP(hipMemcpyAsync(host_out, filter->dev.data(), bytes, hipMemcpyDeviceToHost, ctx->stream),
               "Failed to memcpy the filter grid back to the host");
   VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "retrieve filtered grid");
   // (the handle is logically const for the caller; the finished upload's bookkeeping is not part of its value)
@@ -1850,12 +1801,11 @@ int vgt_hip_sdf_batch_from_occupancy_f32(vgt_hip_ctx* ctx, const float* const* o
   const int64_t group = BatchGroup(batch, nx, ny, nz, size_t{2} << 30, n * 9);
   std::lock_guard<std::mutex> lock(ctx->mutex);
   const size_t ws_bytes = CarveWorkspace(nullptr, nx, ny, nz, ctx->variant, ctx->variant == 0 ? group : 1).bytes;
-  VGT_TRY_HIP(Reserve(&ctx->sdf_in, &ctx->sdf_in_bytes, static_cast<size_t>(group) * n * sizeof(float)), "allocate SDF input");
-  VGT_TRY_HIP(Reserve(&ctx->sdf_out, &ctx->sdf_out_bytes, static_cast<size_t>(group) * n * sizeof(float) + static_cast<size_t>(group) * 2 * sizeof(float)),
-              "allocate SDF output");
-  VGT_TRY_HIP(Reserve(&ctx->sdf_ws, &ctx->sdf_ws_bytes, ws_bytes), "allocate SDF workspace");
-  float* const in_dev = static_cast<float*>(ctx->sdf_in);
-  float* const out_dev = static_cast<float*>(ctx->sdf_out);
+  VGT_TRY_HIP(ctx->sdf_in.Reserve(static_cast<size_t>(group) * n * sizeof(float)), "allocate SDF input");
+  VGT_TRY_HIP(ctx->sdf_out.Reserve(static_cast<size_t>(group) * (n + 2) * sizeof(float)), "allocate SDF output");
+  VGT_TRY_HIP(ctx->sdf_ws.Reserve(ws_bytes), "allocate SDF workspace");
+  float* const in_dev = ctx->sdf_in.as<float>();
+  float* const out_dev = ctx->sdf_out.as<float>();
   float* const mm_dev = out_dev + static_cast<size_t>(group) * n;
   std::vector<float> mm(static_cast<size_t>(group) * 2);
   hipStream_t s = ctx->stream;
@@ -1886,7 +1836,7 @@ int vgt_hip_sdf_batch_from_occupancy_f32(vgt_hip_ctx* ctx, const float* const* o
     if (ctx->variant == 0)
     {
       p.batch = count;
-      rc = RunSdfPipeline<float>(ctx, in_dev, p, out_dev, ctx->sdf_ws, ctx->sdf_ws_bytes, mm_dev, nullptr);
+      rc = RunSdfPipeline<float>(ctx, in_dev, p, out_dev, ctx->sdf_ws.data(), ctx->sdf_ws.bytes(), mm_dev, nullptr);
       if (rc != VGT_HIP_OK) return rc;
     }
     else
@@ -1895,7 +1845,7 @@ int vgt_hip_sdf_batch_from_occupancy_f32(vgt_hip_ctx* ctx, const float* const* o
       for (int64_t b = 0; b < count; b++)
       {
         rc = RunSdfPipeline<float>(ctx, in_dev + static_cast<size_t>(b) * n, p, out_dev + static_cast<size_t>(b) * n,
-                                   ctx->sdf_ws, ctx->sdf_ws_bytes, mm_dev + 2 * b, nullptr);
+                                   ctx->sdf_ws.data(), ctx->sdf_ws.bytes(), mm_dev + 2 * b, nullptr);
         if (rc != VGT_HIP_OK) return rc;
       }
     }
@@ -1960,22 +1910,6 @@ int vgt_hip_sdf_dev_timed(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t 
 
 namespace
 {
-static void FreeCells(vgt_hip_cells* c)
-{
-  if (!c) return;
-  if (c->records) (void)hipFree(c->records);
-  if (c->mask) (void)hipFree(c->mask);
-  if (c->sdf) (void)hipFree(c->sdf);
-  if (c->sdf_named) (void)hipFree(c->sdf_named);
-  if (c->workspace) (void)hipFree(c->workspace);
-  if (c->objects) (void)hipFree(c->objects);
-  if (c->scalar) (void)hipFree(c->scalar);
-  if (c->batch_masks) (void)hipFree(c->batch_masks);
-  if (c->batch_sdf) (void)hipFree(c->batch_sdf);
-  if (c->batch_ws) (void)hipFree(c->batch_ws);
-  delete c;
-}
-
 static int CheckCells(const vgt_hip_ctx* ctx, const vgt_hip_cells* cells)
 {
   if (!ctx || !cells) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
@@ -1989,20 +1923,21 @@ static int RunCellsSdf(vgt_hip_ctx* ctx, vgt_hip_cells* c, int mode, int num_obj
                 float* sdf_dev, float* minmax_dev = nullptr)  // (extrema: the context's two floats unless told otherwise)
 {
   const int64_t n = c->nx * c->ny * c->nz;
-  VGT_TRY_HIP(vgt::LaunchCellMask(c->records, n, c->cell_bytes, c->object_id_offset, mode, c->objects,
-                                  num_objects, p.unknown_is_filled, c->mask, ctx->stream),
+  VGT_TRY_HIP(vgt::LaunchCellMask(c->records.as<void>(), n, c->cell_bytes, c->object_id_offset, mode,
+                                  c->objects.as<uint32_t>(), num_objects, p.unknown_is_filled, c->mask.as<uint8_t>(),
+                                  ctx->stream),
               "cell predicate");
   vgt::SdfParams mask_params = p;
   mask_params.unknown_is_filled = 0;
   // (the workspace was sized for the default pipeline: the cross-check, selected later, needs more)
   const size_t need = CarveWorkspace(nullptr, c->nx, c->ny, c->nz, ctx->variant).bytes;
-  if (need > c->workspace_bytes)
+  if (need > c->workspace.bytes())
   {
     VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "synchronize");
-    VGT_TRY_HIP(Reserve(&c->workspace, &c->workspace_bytes, need), "allocate SDF workspace");
+    VGT_TRY_HIP(c->workspace.Reserve(need), "allocate SDF workspace");
   }
-  return RunSdfPipeline<uint8_t>(ctx, c->mask, mask_params, sdf_dev, c->workspace, c->workspace_bytes,
-                                 minmax_dev ? minmax_dev : ctx->minmax_out, nullptr);
+  return RunSdfPipeline<uint8_t>(ctx, c->mask.as<uint8_t>(), mask_params, sdf_dev, c->workspace.data(),
+                                 c->workspace.bytes(), minmax_dev ? minmax_dev : ctx->minmax_out.as<float>(), nullptr);
 }
 
 // A field of the context's stream into a host array (usually one the caller has just allocated) + the extrema.  The
@@ -2013,6 +1948,7 @@ static int CopySdfToHost(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t n, floa
                   float* out_max)
 {
   float mm[2] = {0.0f, 0.0f};
+  const float* const minmax_dev = ctx->minmax_out.as<float>();
   const size_t bytes = static_cast<size_t>(n) * sizeof(float);
   hipError_t err = hipSuccess;
   if (bytes >= (size_t{32} << 20))
@@ -2021,13 +1957,12 @@ static int CopySdfToHost(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t n, floa
     fresh.Wait();
     const ScopedHostPin pin(sdf_host, bytes);
     err = hipMemcpyAsync(sdf_host, sdf_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(mm, ctx->minmax_out, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (before the array is unlocked, whatever happened)
-    if (err == hipSuccess) err = sync;
+    if (err == hipSuccess) err = hipMemcpyAsync(mm, minmax_dev, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream);
+    err = DrainKeepingFirst(ctx->stream, err);  // (before the array is unlocked, whatever happened)
   }
   else if (bytes >= (size_t{1} << 20))
   {
-    err = hipMemcpyAsync(mm, ctx->minmax_out, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream);
+    err = hipMemcpyAsync(mm, minmax_dev, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream);
     if (err == hipSuccess)
       err = DownloadToHostArrays(ctx, {HostArrayCopy{sdf_dev, sdf_host}}, bytes, ctx->stream);  // (synchronises)
     if (err != hipSuccess) (void)hipStreamSynchronize(ctx->stream);  // (`mm` is on this stack)
@@ -2035,7 +1970,7 @@ static int CopySdfToHost(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t n, floa
   else
   {
     err = hipMemcpyAsync(sdf_host, sdf_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(mm, ctx->minmax_out, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(mm, minmax_dev, sizeof(mm), hipMemcpyDeviceToHost, ctx->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
   }
   if (err != hipSuccess) return FailHip("copy SDF to host", err);
@@ -2058,7 +1993,7 @@ int vgt_hip_cells_create(vgt_hip_ctx* ctx, const void* cells_host, int64_t nx, i
       (object_id_offset < 4 || object_id_offset % 4 != 0 || object_id_offset + 4 > cell_bytes))
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "object id offset outside the cell record");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  vgt_hip_cells* c = new (std::nothrow) vgt_hip_cells();
+  std::unique_ptr<vgt_hip_cells> c(new (std::nothrow) vgt_hip_cells());
   if (!c) return Fail(VGT_HIP_ERR_RUNTIME, "out of host memory");
   c->ctx = ctx;
   c->device = ctx->device;
@@ -2068,26 +2003,20 @@ int vgt_hip_cells_create(vgt_hip_ctx* ctx, const void* cells_host, int64_t nx, i
   c->cell_bytes = cell_bytes;
   c->object_id_offset = object_id_offset;
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  c->workspace_bytes = vgt_hip_sdf_workspace_bytes(nx, ny, nz);
-  hipError_t err = hipMalloc(&c->records, n * static_cast<size_t>(cell_bytes));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&c->mask), n);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&c->sdf), n * sizeof(float));
-  if (err == hipSuccess) err = hipMalloc(&c->workspace, c->workspace_bytes);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&c->scalar), 2 * sizeof(uint32_t));
-  if (err == hipSuccess)
+  VGT_TRY_HIP(c->records.Allocate(n * static_cast<size_t>(cell_bytes)), "upload cell records");
+  VGT_TRY_HIP(c->mask.Allocate(n), "upload cell records");
+  VGT_TRY_HIP(c->sdf.Allocate(n * sizeof(float)), "upload cell records");
+  VGT_TRY_HIP(c->workspace.Reserve(vgt_hip_sdf_workspace_bytes(nx, ny, nz)), "upload cell records");
+  VGT_TRY_HIP(c->scalar.Allocate(2 * sizeof(uint32_t)), "upload cell records");
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(c->records, cells_host, n * static_cast<size_t>(cell_bytes), hipMemcpyHostToDevice,
-                         ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-  }
-  if (err != hipSuccess)
-  {
-    FreeCells(c);
-    return FailHip("upload cell records", err);
+    VGT_TRY_HIP(hipMemcpyAsync(c->records.as<void>(), cells_host, n * static_cast<size_t>(cell_bytes),
+                               hipMemcpyHostToDevice, ctx->stream),
+                "upload cell records");
+    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "upload cell records");
   }
   AdoptChild(ctx);
-  *out_cells = c;
+  *out_cells = c.release();
   return VGT_HIP_OK;
 }
 
@@ -2095,7 +2024,7 @@ void vgt_hip_cells_destroy(vgt_hip_cells* cells)
 {
   if (!cells) return;
   ReleaseChild(cells->ctx, cells->device);
-  FreeCells(cells);
+  delete cells;
 }
 
 int vgt_hip_cells_object_ids(vgt_hip_ctx* ctx, vgt_hip_cells* cells, uint32_t* ids_out, int64_t capacity,
@@ -2123,50 +2052,49 @@ int vgt_hip_cells_object_ids(vgt_hip_ctx* ctx, vgt_hip_cells* cells, uint32_t* i
     if (attempt == 1 && attempts[1] == attempts[0]) break;
     const int kTableLog2 = attempts[attempt];
     const size_t slots = size_t{1} << kTableLog2;
-    uint32_t* table = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&table), (2 * slots + 64) * sizeof(uint32_t));
-    if (err == hipSuccess)
+    vgt::DeviceTemp table_dev;  // (freed under the context's mutex, like the scan it serves)
+    if (table_dev.Allocate((2 * slots + 64) * sizeof(uint32_t)) != hipSuccess)
     {
-      uint32_t* ids_dev = table + slots;
-      uint32_t* count_overflow = ids_dev + slots;
-      uint32_t header[2] = {0u, 1u};
-      std::vector<uint32_t> ids;
-      err = hipMemsetAsync(table, 0, (2 * slots + 64) * sizeof(uint32_t), ctx->stream);
-      if (err == hipSuccess)
-        err = vgt::LaunchDistinctObjectIds(cells->records, n, cells->cell_bytes, cells->object_id_offset, table, kTableLog2,
-                                           ids_dev, count_overflow, ctx->stream);
-      if (err == hipSuccess)
-        err = hipMemcpyAsync(header, count_overflow, sizeof(header), hipMemcpyDeviceToHost, ctx->stream);
-      if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-      if (err == hipSuccess && header[1] == 0u && header[0] > 0u)
-      {
-        ids.resize(header[0]);
-        err = hipMemcpy(ids.data(), ids_dev, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-      }
-      (void)hipFree(table);
-      VGT_TRY_HIP(err, "object id scan");
-      if (header[1] == 0u)
-      {
-        std::sort(ids.begin(), ids.end());
-        *count = static_cast<int64_t>(ids.size());
-        for (int64_t k = 0; k < *count && k < capacity; k++) ids_out[k] = ids[static_cast<size_t>(k)];
-        return VGT_HIP_OK;
-      }
-    }
-    else
       (void)hipGetLastError();
+      continue;
+    }
+    uint32_t* table = table_dev.as<uint32_t>();
+    uint32_t* ids_dev = table + slots;
+    uint32_t* count_overflow = ids_dev + slots;
+    uint32_t header[2] = {0u, 1u};
+    std::vector<uint32_t> ids;
+    hipError_t err = hipMemsetAsync(table, 0, (2 * slots + 64) * sizeof(uint32_t), ctx->stream);
+    if (err == hipSuccess)
+      err = vgt::LaunchDistinctObjectIds(cells->records.as<void>(), n, cells->cell_bytes, cells->object_id_offset, table,
+                                         kTableLog2, ids_dev, count_overflow, ctx->stream);
+    if (err == hipSuccess)
+      err = hipMemcpyAsync(header, count_overflow, sizeof(header), hipMemcpyDeviceToHost, ctx->stream);
+    err = DrainKeepingFirst(ctx->stream, err);
+    if (err == hipSuccess && header[1] == 0u && header[0] > 0u)
+    {
+      ids.resize(header[0]);
+      err = hipMemcpy(ids.data(), ids_dev, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    VGT_TRY_HIP(err, "object id scan");
+    if (header[1] == 0u)
+    {
+      std::sort(ids.begin(), ids.end());
+      *count = static_cast<int64_t>(ids.size());
+      for (int64_t k = 0; k < *count && k < capacity; k++) ids_out[k] = ids[static_cast<size_t>(k)];
+      return VGT_HIP_OK;
+    }
   }
   uint32_t after = 0;  // ids > 0 only (tagged_object_occupancy_map.hpp:279-283)
   for (;;)
   {
     const uint32_t init[2] = {0xffffffffu, 0u};
-    VGT_TRY_HIP(hipMemcpyAsync(cells->scalar, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream),
-                "reset id scan");
-    VGT_TRY_HIP(vgt::LaunchNextObjectId(cells->records, n, cells->cell_bytes, cells->object_id_offset, after,
-                                        cells->scalar, ctx->stream),
+    uint32_t* const scalar = cells->scalar.as<uint32_t>();
+    VGT_TRY_HIP(hipMemcpyAsync(scalar, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream), "reset id scan");
+    VGT_TRY_HIP(vgt::LaunchNextObjectId(cells->records.as<void>(), n, cells->cell_bytes, cells->object_id_offset, after,
+                                        scalar, ctx->stream),
                 "object id scan");
     uint32_t next[2] = {0u, 0u};
-    VGT_TRY_HIP(hipMemcpyAsync(next, cells->scalar, sizeof(next), hipMemcpyDeviceToHost, ctx->stream),
+    VGT_TRY_HIP(hipMemcpyAsync(next, scalar, sizeof(next), hipMemcpyDeviceToHost, ctx->stream),
                 "read id scan");
     VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "id scan");
     if (!next[1]) break;
@@ -2196,19 +2124,14 @@ int vgt_hip_cells_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* ob
   std::sort(objects.begin(), objects.end());
   objects.erase(std::unique(objects.begin(), objects.end()), objects.end());
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  if (objects.size() > cells->objects_capacity)
+  if (objects.size() * sizeof(uint32_t) > cells->objects.bytes())
   {
     VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing object list");
-    if (cells->objects) (void)hipFree(cells->objects);
-    cells->objects = nullptr;
-    cells->objects_capacity = 0;
-    VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&cells->objects), objects.size() * sizeof(uint32_t)),
-                "allocate object list");
-    cells->objects_capacity = objects.size();
+    VGT_TRY_HIP(cells->objects.Reserve(objects.size() * sizeof(uint32_t)), "allocate object list");
   }
   if (!objects.empty())
   {
-    VGT_TRY_HIP(hipMemcpyAsync(cells->objects, objects.data(), objects.size() * sizeof(uint32_t),
+    VGT_TRY_HIP(hipMemcpyAsync(cells->objects.data(), objects.data(), objects.size() * sizeof(uint32_t),
                                hipMemcpyHostToDevice, ctx->stream),
                 "upload object list");
     // `objects` is pageable host memory: the copy has been staged when the call returns
@@ -2230,13 +2153,13 @@ int vgt_hip_cells_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* ob
     if (out_max) *out_max = field[n + 1];
     return VGT_HIP_OK;
   }
-  rc = RunCellsSdf(ctx, cells, objects.empty() ? 0 : 1, static_cast<int>(objects.size()), p, cells->sdf);
+  rc = RunCellsSdf(ctx, cells, objects.empty() ? 0 : 1, static_cast<int>(objects.size()), p, cells->sdf.as<float>());
   if (rc != VGT_HIP_OK)
   {
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
-  return CopySdfToHost(ctx, cells->sdf, cells->nx * cells->ny * cells->nz, sdf_host, out_min, out_max);
+  return CopySdfToHost(ctx, cells->sdf.as<float>(), cells->nx * cells->ny * cells->nz, sdf_host, out_min, out_max);
 }
 
 int vgt_hip_cells_object_sdfs(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* object_ids,
@@ -2266,39 +2189,34 @@ int vgt_hip_cells_object_sdfs(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint
   hipStream_t s = ctx->stream;
   const size_t ws_bytes = CarveWorkspace(nullptr, nx, ny, nz, ctx->variant, group).bytes;
   const size_t sdf_bytes = static_cast<size_t>(group) * (n + 2) * sizeof(float);
-  if (cells->batch_masks_bytes < static_cast<size_t>(group) * n || cells->batch_sdf_bytes < sdf_bytes ||
-      cells->batch_ws_bytes < ws_bytes || cells->objects_capacity < static_cast<size_t>(group))
+  const size_t ids_bytes = static_cast<size_t>(group) * sizeof(uint32_t);
+  if (cells->batch_masks.bytes() < static_cast<size_t>(group) * n || cells->batch_sdf.bytes() < sdf_bytes ||
+      cells->batch_ws.bytes() < ws_bytes || cells->objects.bytes() < ids_bytes)
     VGT_TRY_HIP(hipStreamSynchronize(s), "drain before regrowing the batch buffers");
-  VGT_TRY_HIP(Reserve(&cells->batch_masks, &cells->batch_masks_bytes, static_cast<size_t>(group) * n), "allocate masks");
-  VGT_TRY_HIP(Reserve(&cells->batch_sdf, &cells->batch_sdf_bytes, sdf_bytes), "allocate fields");
-  VGT_TRY_HIP(Reserve(&cells->batch_ws, &cells->batch_ws_bytes, ws_bytes), "allocate SDF workspace");
-  if (cells->objects_capacity < static_cast<size_t>(group))
-  {
-    if (cells->objects) (void)hipFree(cells->objects);
-    cells->objects = nullptr;
-    cells->objects_capacity = 0;
-    VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&cells->objects), static_cast<size_t>(group) * sizeof(uint32_t)),
-                "allocate object list");
-    cells->objects_capacity = static_cast<size_t>(group);
-  }
-  float* const sdf_dev = static_cast<float*>(cells->batch_sdf);
+  VGT_TRY_HIP(cells->batch_masks.Reserve(static_cast<size_t>(group) * n), "allocate masks");
+  VGT_TRY_HIP(cells->batch_sdf.Reserve(sdf_bytes), "allocate fields");
+  VGT_TRY_HIP(cells->batch_ws.Reserve(ws_bytes), "allocate SDF workspace");
+  VGT_TRY_HIP(cells->objects.Reserve(ids_bytes), "allocate object list");
+  uint32_t* const ids_dev = cells->objects.as<uint32_t>();
+  uint8_t* const masks_dev = cells->batch_masks.as<uint8_t>();
+  float* const sdf_dev = cells->batch_sdf.as<float>();
   float* const mm_dev = sdf_dev + static_cast<size_t>(group) * n;
   std::vector<float> mm(static_cast<size_t>(group) * 2);
   for (int64_t first = 0; first < num_objects; first += group)
   {
     const int64_t count = num_objects - first < group ? num_objects - first : group;
     // (pageable source: staged when the call returns)
-    VGT_TRY_HIP(hipMemcpyAsync(cells->objects, object_ids + first, static_cast<size_t>(count) * sizeof(uint32_t),
+    VGT_TRY_HIP(hipMemcpyAsync(ids_dev, object_ids + first, static_cast<size_t>(count) * sizeof(uint32_t),
                                hipMemcpyHostToDevice, s),
                 "upload object ids");
-    VGT_TRY_HIP(vgt::LaunchCellObjectMasks(cells->records, static_cast<int64_t>(n), cells->cell_bytes,
-                                           cells->object_id_offset, cells->objects, static_cast<int>(count),
-                                           unknown_is_filled ? 1 : 0, static_cast<uint8_t*>(cells->batch_masks), s),
+    VGT_TRY_HIP(vgt::LaunchCellObjectMasks(cells->records.as<void>(), static_cast<int64_t>(n), cells->cell_bytes,
+                                           cells->object_id_offset, ids_dev, static_cast<int>(count),
+                                           unknown_is_filled ? 1 : 0, masks_dev, s),
                 "object masks");
     vgt::SdfParams p{nx, ny, nz, resolution, 0, add_virtual_border ? 1 : 0};
     p.batch = count;
-    rc = RunSdfPipeline<uint8_t>(ctx, static_cast<const uint8_t*>(cells->batch_masks), p, sdf_dev, cells->batch_ws,
-                                 cells->batch_ws_bytes, mm_dev, nullptr);
+    rc = RunSdfPipeline<uint8_t>(ctx, masks_dev, p, sdf_dev, cells->batch_ws.data(), cells->batch_ws.bytes(), mm_dev,
+                                 nullptr);
     if (rc != VGT_HIP_OK)
     {
       (void)hipStreamSynchronize(s);
@@ -2330,15 +2248,16 @@ namespace
 int RunFreeAndNamedSdf(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const vgt::SdfParams& p)
 {
   const int64_t n = cells->nx * cells->ny * cells->nz;
-  int rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf);                      // free-space field: every filled cell
-  if (rc == VGT_HIP_OK) rc = RunCellsSdf(ctx, cells, 2, 0, p, cells->sdf_named);  // cells of named objects only
+  float* const sdf = cells->sdf.as<float>();
+  float* const sdf_named = cells->sdf_named.as<float>();
+  int rc = RunCellsSdf(ctx, cells, 0, 0, p, sdf);                      // free-space field: every filled cell
+  if (rc == VGT_HIP_OK) rc = RunCellsSdf(ctx, cells, 2, 0, p, sdf_named);  // cells of named objects only
   if (rc == VGT_HIP_OK)
   {
-    uint32_t* enc = CarveWorkspace(cells->workspace, cells->nx, cells->ny, cells->nz, ctx->variant).minmax_enc;
+    uint32_t* enc = CarveWorkspace(cells->workspace.data(), cells->nx, cells->ny, cells->nz, ctx->variant).minmax_enc;
     hipError_t err = vgt::LaunchInitMinMax(enc, ctx->stream);
-    if (err == hipSuccess)
-      err = vgt::LaunchCombineFreeAndNamed(cells->sdf, cells->sdf_named, n, cells->sdf, enc, ctx->stream);
-    if (err == hipSuccess) err = vgt::LaunchDecodeMinMax(enc, ctx->minmax_out, ctx->stream);
+    if (err == hipSuccess) err = vgt::LaunchCombineFreeAndNamed(sdf, sdf_named, n, sdf, enc, ctx->stream);
+    if (err == hipSuccess) err = vgt::LaunchDecodeMinMax(enc, ctx->minmax_out.as<float>(), ctx->stream);
     if (err != hipSuccess) rc = FailHip("combine fields", err);
   }
   return rc;
@@ -2359,9 +2278,7 @@ int vgt_hip_cells_free_and_named_objects_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* ce
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const int64_t n = cells->nx * cells->ny * cells->nz;
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  if (!cells->sdf_named)
-    VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&cells->sdf_named), static_cast<size_t>(n) * sizeof(float)),
-                "allocate second SDF");
+  VGT_TRY_HIP(cells->sdf_named.Reserve(static_cast<size_t>(n) * sizeof(float)), "allocate second SDF");
   const vgt::SdfParams p{cells->nx, cells->ny, cells->nz, resolution, unknown_is_filled ? 1 : 0,
                          add_virtual_border ? 1 : 0};
   rc = RunFreeAndNamedSdf(ctx, cells, p);
@@ -2370,7 +2287,7 @@ int vgt_hip_cells_free_and_named_objects_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* ce
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
-  return CopySdfToHost(ctx, cells->sdf, n, sdf_host, out_min, out_max);
+  return CopySdfToHost(ctx, cells->sdf.as<float>(), n, sdf_host, out_min, out_max);
 }
 
 /* ------------------------------ deferred timing ------------------------------ */
@@ -2468,30 +2385,20 @@ int vgt_hip_sdf_coarse_gradient(vgt_hip_ctx* ctx, const float* sdf_host, int64_t
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  float* sdf_dev = nullptr;
-  double* grad_dev = nullptr;
-  uint8_t* has_dev = nullptr;
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&sdf_dev), n * sizeof(float));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&grad_dev), n * 3 * sizeof(double));
-  if (err == hipSuccess && has_value_host) err = hipMalloc(reinterpret_cast<void**>(&has_dev), n);
+  vgt::DeviceTemp sdf_dev, grad_dev, has_dev;
+  VGT_TRY_HIP(sdf_dev.Allocate(n * sizeof(float)), "coarse gradient");
+  VGT_TRY_HIP(grad_dev.Allocate(n * 3 * sizeof(double)), "coarse gradient");
+  if (has_value_host) VGT_TRY_HIP(has_dev.Allocate(n), "coarse gradient");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipError_t err = hipMemcpyAsync(sdf_dev.as<float>(), sdf_host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
   if (err == hipSuccess)
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(sdf_dev, sdf_host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess)
-      err = vgt::LaunchCoarseGradient(sdf_dev, nx, ny, nz, resolution, enable_edge_gradients ? 1 : 0, rotation,
-                                      grad_dev, has_dev, ctx->stream);
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(gradient_host, grad_dev, n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess && has_value_host)
-      err = hipMemcpyAsync(has_value_host, has_dev, n, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t sync = hipStreamSynchronize(ctx->stream);
-    if (err == hipSuccess) err = sync;
-  }
-  if (sdf_dev) (void)hipFree(sdf_dev);
-  if (grad_dev) (void)hipFree(grad_dev);
-  if (has_dev) (void)hipFree(has_dev);
-  VGT_TRY_HIP(err, "coarse gradient");
+    err = vgt::LaunchCoarseGradient(sdf_dev.as<float>(), nx, ny, nz, resolution, enable_edge_gradients ? 1 : 0, rotation,
+                                    grad_dev.as<double>(), has_dev.as<uint8_t>(), ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(gradient_host, grad_dev.as<void>(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (err == hipSuccess && has_value_host)
+    err = hipMemcpyAsync(has_value_host, has_dev.as<uint8_t>(), n, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "coarse gradient");
   return VGT_HIP_OK;
 }
 
@@ -2550,17 +2457,12 @@ int vgt_hip_sdf_local_extrema_map_dev(vgt_hip_ctx* ctx, const float* sdf_dev, in
   if (nx * ny * nz >= 0x7fffffffLL)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the local extrema map supports grids below 2^31 cells");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  void* scratch = nullptr;
-  VGT_TRY_HIP(hipMalloc(&scratch, vgt::LocalExtremaScratchBytes(nx * ny * nz)), "allocate extrema scratch");
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = vgt::LaunchLocalExtremaMap(sdf_dev, nx, ny, nz, resolution, rotation, extrema_dev, scratch, ctx->stream);
-    const hipError_t sync = hipStreamSynchronize(ctx->stream);  // the scratch is freed below
-    if (err == hipSuccess) err = sync;
-  }
-  (void)hipFree(scratch);
-  VGT_TRY_HIP(err, "local extrema map");
+  vgt::DeviceTemp scratch;
+  VGT_TRY_HIP(scratch.Allocate(vgt::LocalExtremaScratchBytes(nx * ny * nz)), "allocate extrema scratch");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  const hipError_t err = vgt::LaunchLocalExtremaMap(sdf_dev, nx, ny, nz, resolution, rotation, extrema_dev,
+                                                    scratch.as<void>(), ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "local extrema map");  // (the scratch goes with the call)
   return VGT_HIP_OK;
 }
 
@@ -2572,29 +2474,24 @@ int vgt_hip_sdf_local_extrema_map(vgt_hip_ctx* ctx, const float* sdf_host, int64
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  float* sdf_dev = nullptr;
-  double* out_dev = nullptr;
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&sdf_dev), n * sizeof(float));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&out_dev), n * 3 * sizeof(double));
+  vgt::DeviceTemp sdf_dev, out_dev;
+  VGT_TRY_HIP(sdf_dev.Allocate(n * sizeof(float)), "local extrema map");
+  VGT_TRY_HIP(out_dev.Allocate(n * 3 * sizeof(double)), "local extrema map");
+  hipError_t err;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    err = hipMemcpyAsync(sdf_dev.as<float>(), sdf_host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+  }
   int result = VGT_HIP_OK;
   if (err == hipSuccess)
+    result = vgt_hip_sdf_local_extrema_map_dev(ctx, sdf_dev.as<float>(), nx, ny, nz, resolution, rotation,
+                                               out_dev.as<double>());
   {
-    {
-      std::lock_guard<std::mutex> lock(ctx->mutex);
-      err = hipMemcpyAsync(sdf_dev, sdf_host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (err == hipSuccess)
-      result = vgt_hip_sdf_local_extrema_map_dev(ctx, sdf_dev, nx, ny, nz, resolution, rotation, out_dev);
+    std::lock_guard<std::mutex> lock(ctx->mutex);
     if (err == hipSuccess && result == VGT_HIP_OK)
-    {
-      std::lock_guard<std::mutex> lock(ctx->mutex);
-      err = hipMemcpyAsync(extrema_host, out_dev, n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-      const hipError_t sync = hipStreamSynchronize(ctx->stream);
-      if (err == hipSuccess) err = sync;
-    }
+      err = hipMemcpyAsync(extrema_host, out_dev.as<void>(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    err = DrainKeepingFirst(ctx->stream, err);  // (whatever happened: the upload may still be in flight)
   }
-  if (sdf_dev) (void)hipFree(sdf_dev);
-  if (out_dev) (void)hipFree(out_dev);
   if (result != VGT_HIP_OK) return result;
   VGT_TRY_HIP(err, "local extrema map");
   return VGT_HIP_OK;
@@ -2637,21 +2534,18 @@ int RunLabelling(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int ob
 {
   const int64_t n = nx * ny * nz;
   const size_t need = vgt::ComponentScratchBytes(n);
-  if (need > ctx->component_ws_bytes)
+  if (need > ctx->component_ws.bytes())
   {
     VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the labelling scratch");
-    VGT_TRY_HIP(Reserve(&ctx->component_ws, &ctx->component_ws_bytes, need), "allocate labelling scratch");
+    VGT_TRY_HIP(ctx->component_ws.Reserve(need), "allocate labelling scratch");
   }
+  void* const scratch = ctx->component_ws.data();
   hipError_t err = vgt::LaunchLabelComponents(cells_dev, cell_bytes, object_id_offset, mode, extrema_dev,
-                                              connected_threshold, nx, ny, nz, labels_dev, ctx->component_ws,
-                                              ctx->stream);
+                                              connected_threshold, nx, ny, nz, labels_dev, scratch, ctx->stream);
   uint32_t count = 0;
   if (err == hipSuccess)
-    err = hipMemcpyAsync(&count, vgt::ComponentCountPtr(ctx->component_ws, n), sizeof(count), hipMemcpyDeviceToHost,
-                         ctx->stream);
-  const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (`count` is on this stack)
-  if (err == hipSuccess) err = sync;
-  VGT_TRY_HIP(err, "label components");
+    err = hipMemcpyAsync(&count, vgt::ComponentCountPtr(scratch, n), sizeof(count), hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "label components");  // (`count` is on this stack)
   *num_components = count;
   return VGT_HIP_OK;
 }
@@ -2662,24 +2556,14 @@ int LabelToHost(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int obj
                 uint32_t* labels_host, uint32_t* num_components)
 {
   const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(uint32_t);
-  uint32_t* labels_dev = nullptr;
-  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&labels_dev), bytes), "allocate labels");
-  int rc;
-  hipError_t err = hipSuccess;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, extrema_dev, connected_threshold, nx, ny, nz,
-                      labels_dev, num_components);
-    if (rc == VGT_HIP_OK)
-    {
-      err = hipMemcpyAsync(labels_host, labels_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
-      const hipError_t sync = hipStreamSynchronize(ctx->stream);
-      if (err == hipSuccess) err = sync;
-    }
-  }
-  (void)hipFree(labels_dev);
-  if (rc != VGT_HIP_OK) return rc;
-  VGT_TRY_HIP(err, "copy labels to the host");
+  vgt::DeviceTemp labels_dev;
+  VGT_TRY_HIP(labels_dev.Allocate(bytes), "allocate labels");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  const int rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, extrema_dev, connected_threshold, nx,
+                              ny, nz, labels_dev.as<uint32_t>(), num_components);
+  if (rc != VGT_HIP_OK) return rc;  // (it has waited for whatever it enqueued)
+  const hipError_t err = hipMemcpyAsync(labels_host, labels_dev.as<void>(), bytes, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "copy labels to the host");
   return VGT_HIP_OK;
 }
 }  // namespace
@@ -2706,23 +2590,21 @@ int vgt_hip_connected_components(vgt_hip_ctx* ctx, const float* occupancy_host, 
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(float);
-  float* occupancy_dev = nullptr;
-  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&occupancy_dev), bytes), "allocate occupancy");
+  vgt::DeviceTemp occupancy_dev;
+  VGT_TRY_HIP(occupancy_dev.Allocate(bytes), "allocate occupancy");
   hipError_t err;
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(occupancy_dev, occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    err = hipMemcpyAsync(occupancy_dev.as<void>(), occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
   }
-  int result = VGT_HIP_OK;
+  int result;
   if (err == hipSuccess)
-    result = LabelToHost(ctx, occupancy_dev, 4, -1, vgt::kComponentClasses, nullptr, 0.0, nx, ny, nz, labels_host,
-                         num_components);
+    result = LabelToHost(ctx, occupancy_dev.as<void>(), 4, -1, vgt::kComponentClasses, nullptr, 0.0, nx, ny, nz,
+                         labels_host, num_components);
   else
-    (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(occupancy_dev);
-  if (result != VGT_HIP_OK) return result;
-  VGT_TRY_HIP(err, "upload occupancy");
-  return VGT_HIP_OK;
+    result = FailHip("upload occupancy", err);
+  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
+  return result;
 }
 
 int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
@@ -2735,7 +2617,7 @@ int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, i
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const bool by_object = cells->object_id_offset >= 0 && !connect_across_objects;
-  return LabelToHost(ctx, cells->records, cells->cell_bytes, cells->object_id_offset,
+  return LabelToHost(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
                      by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, nullptr, 0.0, cells->nx,
                      cells->ny, cells->nz, labels_host, num_components);
 }
@@ -2750,7 +2632,7 @@ int vgt_hip_cells_spatial_segments_dev(vgt_hip_ctx* ctx, vgt_hip_cells* cells, c
   if (!extrema_dev || !labels_dev || !num_segments) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  return RunLabelling(ctx, cells->records, cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
+  return RunLabelling(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
                       extrema_dev, connected_threshold, cells->nx, cells->ny, cells->nz, labels_dev, num_segments);
 }
 
@@ -2764,23 +2646,22 @@ int vgt_hip_cells_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const
   if (!extrema_host || !labels_host || !num_segments) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t bytes = static_cast<size_t>(cells->nx * cells->ny * cells->nz) * 3 * sizeof(double);
-  double* extrema_dev = nullptr;
-  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&extrema_dev), bytes), "allocate extrema map");
+  vgt::DeviceTemp extrema_dev;
+  VGT_TRY_HIP(extrema_dev.Allocate(bytes), "allocate extrema map");
   hipError_t err;
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(extrema_dev, extrema_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    err = hipMemcpyAsync(extrema_dev.as<void>(), extrema_host, bytes, hipMemcpyHostToDevice, ctx->stream);
   }
-  int result = VGT_HIP_OK;
+  int result;
   if (err == hipSuccess)
-    result = LabelToHost(ctx, cells->records, cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
-                         extrema_dev, connected_threshold, cells->nx, cells->ny, cells->nz, labels_host, num_segments);
+    result = LabelToHost(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
+                         vgt::kComponentSegments, extrema_dev.as<double>(), connected_threshold, cells->nx, cells->ny,
+                         cells->nz, labels_host, num_segments);
   else
-    (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(extrema_dev);
-  if (result != VGT_HIP_OK) return result;
-  VGT_TRY_HIP(err, "upload extrema map");
-  return VGT_HIP_OK;
+    result = FailHip("upload extrema map", err);
+  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
+  return result;
 }
 
 int vgt_hip_cells_update_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double connected_threshold,
@@ -2796,38 +2677,31 @@ int vgt_hip_cells_update_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const int64_t nx = cells->nx, ny = cells->ny, nz = cells->nz, n = nx * ny * nz;
-  double* extrema_dev = nullptr;
-  void* extrema_scratch = nullptr;
-  hipError_t err = hipMalloc(reinterpret_cast<void**>(&extrema_dev), static_cast<size_t>(n) * 3 * sizeof(double));
-  if (err == hipSuccess) err = hipMalloc(&extrema_scratch, vgt::LocalExtremaScratchBytes(n));
-  if (err == hipSuccess)
+  vgt::DeviceTemp extrema_dev, extrema_scratch;
+  VGT_TRY_HIP(extrema_dev.Allocate(static_cast<size_t>(n) * 3 * sizeof(double)), "update spatial segments");
+  VGT_TRY_HIP(extrema_scratch.Allocate(vgt::LocalExtremaScratchBytes(n)), "update spatial segments");
+  hipError_t err = hipSuccess;
   {
     // S/tagged_object_occupancy_component_map.cpp:786-790: the field of every filled cell with a virtual border, the
     // free-and-named-objects field without; its extrema map; the segments.  Field and map stay on the device.
     std::lock_guard<std::mutex> lock(ctx->mutex);
     const vgt::SdfParams p{nx, ny, nz, resolution, unknown_is_filled ? 1 : 0, add_virtual_border ? 1 : 0};
     if (add_virtual_border)
-      rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf);
+      rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf.as<float>());
     else
     {
-      if (!cells->sdf_named)
-        err = hipMalloc(reinterpret_cast<void**>(&cells->sdf_named), static_cast<size_t>(n) * sizeof(float));
+      err = cells->sdf_named.Reserve(static_cast<size_t>(n) * sizeof(float));
       if (err == hipSuccess) rc = RunFreeAndNamedSdf(ctx, cells, p);
     }
     if (err == hipSuccess && rc == VGT_HIP_OK)
-      err = vgt::LaunchLocalExtremaMap(cells->sdf, nx, ny, nz, resolution, rotation, extrema_dev, extrema_scratch,
-                                       ctx->stream);
-    const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (`rotation` is the caller's; the scratch is freed below)
-    if (err == hipSuccess) err = sync;
+      err = vgt::LaunchLocalExtremaMap(cells->sdf.as<float>(), nx, ny, nz, resolution, rotation,
+                                       extrema_dev.as<double>(), extrema_scratch.as<void>(), ctx->stream);
+    err = DrainKeepingFirst(ctx->stream, err);  // (`rotation` is the caller's; the scratch goes with the call)
   }
-  if (err == hipSuccess && rc == VGT_HIP_OK)
-    rc = LabelToHost(ctx, cells->records, cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
-                     extrema_dev, connected_threshold, nx, ny, nz, labels_host, num_segments);
-  if (extrema_dev) (void)hipFree(extrema_dev);
-  if (extrema_scratch) (void)hipFree(extrema_scratch);
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(err, "update spatial segments");
-  return VGT_HIP_OK;
+  return LabelToHost(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
+                     extrema_dev.as<double>(), connected_threshold, nx, ny, nz, labels_host, num_segments);
 }
 
 namespace
@@ -2864,25 +2738,18 @@ int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  char* buffer = nullptr;  // occupancy, labels, mask
-  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&buffer), n * 9), "allocate surface mask buffers");
-  float* const occupancy_dev = reinterpret_cast<float*>(buffer);
-  uint32_t* const labels_dev = reinterpret_cast<uint32_t*>(buffer + n * 4);
-  uint8_t* const mask_dev = reinterpret_cast<uint8_t*>(buffer + n * 8);
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(occupancy_dev, occupancy_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(labels_dev, labels_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess)
-      err = vgt::LaunchComponentSurfaceMask(occupancy_dev, labels_dev, nx, ny, nz, component_types, mask_dev,
-                                            ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(mask_host, mask_dev, n, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t sync = hipStreamSynchronize(ctx->stream);
-    if (err == hipSuccess) err = sync;
-  }
-  (void)hipFree(buffer);
-  VGT_TRY_HIP(err, "component surface mask");
+  vgt::DeviceTemp buffer;  // occupancy, labels, mask
+  VGT_TRY_HIP(buffer.Allocate(n * 9), "allocate surface mask buffers");
+  float* const occupancy_dev = buffer.as<float>();
+  uint32_t* const labels_dev = reinterpret_cast<uint32_t*>(buffer.as<char>() + n * 4);
+  uint8_t* const mask_dev = buffer.as<uint8_t>() + n * 8;
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipError_t err = hipMemcpyAsync(occupancy_dev, occupancy_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(labels_dev, labels_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (err == hipSuccess)
+    err = vgt::LaunchComponentSurfaceMask(occupancy_dev, labels_dev, nx, ny, nz, component_types, mask_dev, ctx->stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(mask_host, mask_dev, n, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "component surface mask");
   return VGT_HIP_OK;
 }
 
@@ -2913,35 +2780,26 @@ int CheckTopologyGrid(int64_t nx, int64_t ny, int64_t nz, int component_types)
 int RunTopology(vgt_hip_ctx* ctx, const vgt::TopologyGrid& grid, vgt_hip_component_topology_t* out_host)
 {
   const size_t table_bytes = (static_cast<size_t>(grid.num_components) + 1) * sizeof(vgt::ComponentTopologyEntry);
-  void* vertex_scratch = nullptr;
-  void* node_scratch = nullptr;
-  vgt::ComponentTopologyEntry* table_dev = nullptr;
+  vgt::DeviceTemp vertex_scratch, node_scratch, table_dev;
   unsigned long long num_nodes = 0;
-  hipError_t err = hipMalloc(&vertex_scratch, vgt::TopologyVertexScratchBytes(grid.nx, grid.ny, grid.nz));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&table_dev), table_bytes);
-  if (err == hipSuccess) err = vgt::LaunchTopologyCountNodes(grid, vertex_scratch, ctx->stream);
+  VGT_TRY_HIP(vertex_scratch.Allocate(vgt::TopologyVertexScratchBytes(grid.nx, grid.ny, grid.nz)), "component topology");
+  VGT_TRY_HIP(table_dev.Allocate(table_bytes), "component topology");
+  void* const vertices = vertex_scratch.as<void>();
+  hipError_t err = vgt::LaunchTopologyCountNodes(grid, vertices, ctx->stream);
   if (err == hipSuccess)
-    err = hipMemcpyAsync(&num_nodes, vgt::TopologyNodeCountPtr(vertex_scratch, grid.nx, grid.ny, grid.nz),
-                         sizeof(num_nodes), hipMemcpyDeviceToHost, ctx->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-  int rc = VGT_HIP_OK;
-  if (err == hipSuccess && num_nodes >= 0x7fffffffULL)
-    rc = Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component topology supports fewer than 2^31 surface nodes");
-  if (err == hipSuccess && rc == VGT_HIP_OK && num_nodes > 0)
-    err = hipMalloc(&node_scratch, vgt::TopologyNodeScratchBytes(static_cast<int64_t>(num_nodes)));
-  if (err == hipSuccess && rc == VGT_HIP_OK)
-  {
-    err = vgt::LaunchTopologyFromNodes(grid, vertex_scratch, static_cast<int64_t>(num_nodes), node_scratch, table_dev,
-                                       ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(out_host, table_dev, table_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  }
-  const hipError_t sync = hipStreamSynchronize(ctx->stream);  // (the buffers are freed below)
-  if (err == hipSuccess) err = sync;
-  if (vertex_scratch) (void)hipFree(vertex_scratch);
-  if (node_scratch) (void)hipFree(node_scratch);
-  if (table_dev) (void)hipFree(table_dev);
-  if (rc != VGT_HIP_OK) return rc;
-  VGT_TRY_HIP(err, "component topology");
+    err = hipMemcpyAsync(&num_nodes, vgt::TopologyNodeCountPtr(vertices, grid.nx, grid.ny, grid.nz), sizeof(num_nodes),
+                         hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "component topology");
+  if (num_nodes >= 0x7fffffffULL)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component topology supports fewer than 2^31 surface nodes");
+  if (num_nodes > 0)
+    VGT_TRY_HIP(node_scratch.Allocate(vgt::TopologyNodeScratchBytes(static_cast<int64_t>(num_nodes))),
+                "component topology");
+  err = vgt::LaunchTopologyFromNodes(grid, vertices, static_cast<int64_t>(num_nodes), node_scratch.as<void>(),
+                                     table_dev.as<vgt::ComponentTopologyEntry>(), ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(out_host, table_dev.as<void>(), table_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "component topology");  // (the buffers go with the call)
   return VGT_HIP_OK;
 }
 
@@ -2951,35 +2809,23 @@ int LabelAndTopology(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, in
                      vgt_hip_component_topology_t* out_host, uint64_t out_capacity)
 {
   const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(uint32_t);
-  uint32_t* labels_dev = nullptr;
-  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&labels_dev), bytes), "allocate labels");
-  int rc;
-  hipError_t err = hipSuccess;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    uint32_t count = 0;
-    rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, nullptr, 0.0, nx, ny, nz, labels_dev, &count);
-    if (rc == VGT_HIP_OK)
-    {
-      *num_components = count;
-      if (out_capacity < static_cast<uint64_t>(count) + 1)
-        rc = Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
-                  "the topology table needs num_components + 1 = " + std::to_string(static_cast<uint64_t>(count) + 1) +
-                      " entries, out_capacity is " + std::to_string(out_capacity));
-    }
-    if (rc == VGT_HIP_OK)
-      rc = RunTopology(ctx, vgt::TopologyGrid{cells_dev, cell_bytes, labels_dev, nx, ny, nz, component_types, count},
-                       out_host);
-    if (rc == VGT_HIP_OK && labels_host)
-    {
-      err = hipMemcpyAsync(labels_host, labels_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
-      const hipError_t sync = hipStreamSynchronize(ctx->stream);
-      if (err == hipSuccess) err = sync;
-    }
-  }
-  (void)hipFree(labels_dev);
-  if (rc != VGT_HIP_OK) return rc;
-  VGT_TRY_HIP(err, "copy labels to the host");
+  vgt::DeviceTemp labels;
+  VGT_TRY_HIP(labels.Allocate(bytes), "allocate labels");
+  uint32_t* const labels_dev = labels.as<uint32_t>();
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  uint32_t count = 0;
+  int rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, nullptr, 0.0, nx, ny, nz, labels_dev, &count);
+  if (rc != VGT_HIP_OK) return rc;  // (here and below: the callee has waited for whatever it enqueued)
+  *num_components = count;
+  if (out_capacity < static_cast<uint64_t>(count) + 1)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "the topology table needs num_components + 1 = " + std::to_string(static_cast<uint64_t>(count) + 1) +
+                    " entries, out_capacity is " + std::to_string(out_capacity));
+  rc = RunTopology(ctx, vgt::TopologyGrid{cells_dev, cell_bytes, labels_dev, nx, ny, nz, component_types, count},
+                   out_host);
+  if (rc != VGT_HIP_OK || !labels_host) return rc;
+  const hipError_t err = hipMemcpyAsync(labels_host, labels_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "copy labels to the host");
   return VGT_HIP_OK;
 }
 }  // namespace
@@ -3009,23 +2855,21 @@ int vgt_hip_component_topology(vgt_hip_ctx* ctx, const float* occupancy_host, in
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(float);
-  float* occupancy_dev = nullptr;
-  VGT_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&occupancy_dev), bytes), "allocate occupancy");
+  vgt::DeviceTemp occupancy_dev;
+  VGT_TRY_HIP(occupancy_dev.Allocate(bytes), "allocate occupancy");
   hipError_t err;
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(occupancy_dev, occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    err = hipMemcpyAsync(occupancy_dev.as<void>(), occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
   }
-  int result = VGT_HIP_OK;
+  int result;
   if (err == hipSuccess)
-    result = LabelAndTopology(ctx, occupancy_dev, 4, -1, vgt::kComponentClasses, nx, ny, nz, component_types, labels_host,
-                              num_components, out_host, out_capacity);
+    result = LabelAndTopology(ctx, occupancy_dev.as<void>(), 4, -1, vgt::kComponentClasses, nx, ny, nz, component_types,
+                              labels_host, num_components, out_host, out_capacity);
   else
-    (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(occupancy_dev);
-  if (result != VGT_HIP_OK) return result;
-  VGT_TRY_HIP(err, "upload occupancy");
-  return VGT_HIP_OK;
+    result = FailHip("upload occupancy", err);
+  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
+  return result;
 }
 
 int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
@@ -3041,7 +2885,7 @@ int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const bool by_object = cells->object_id_offset >= 0 && !connect_across_objects;
-  return LabelAndTopology(ctx, cells->records, cells->cell_bytes, cells->object_id_offset,
+  return LabelAndTopology(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
                           by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, cells->nx, cells->ny,
                           cells->nz, component_types, labels_host, num_components, out_host, out_capacity);
 }

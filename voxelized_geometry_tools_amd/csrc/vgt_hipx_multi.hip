@@ -23,6 +23,7 @@
 #include "../../include/vgt_hip.h"
 
 #include "vgt_internal.hpp"
+#include "device_memory.hpp"
 #include "host_pages.hpp"
 
 #include <rccl/rccl.h>  // types and prototypes only: the library itself is loaded on first use (below)
@@ -123,14 +124,10 @@ struct Slab
   hipStream_t stream = nullptr;
   hipEvent_t summary_ready = nullptr;
   hipEvent_t marks[4] = {nullptr, nullptr, nullptr, nullptr};  // start, uploaded, computed, downloaded
-  float* occ = nullptr;
-  float* sdf = nullptr;
-  void* workspace = nullptr;
-  size_t workspace_bytes = 0;
-  void* summary = nullptr;
-  void* gathered = nullptr;
-  void* carries = nullptr;
-  float* minmax = nullptr;
+  vgt::DeviceTemp occ, sdf;  // floats
+  vgt::DeviceCache workspace;
+  vgt::DeviceTemp summary, gathered, carries;
+  vgt::DeviceTemp minmax;  // two floats
   float minmax_host[2] = {0.0f, 0.0f};
 };
 
@@ -161,9 +158,7 @@ struct SlabSet
       for (hipEvent_t e : s.marks)
         if (e) (void)hipEventDestroy(e);
       if (s.stream) (void)hipStreamDestroy(s.stream);
-      for (void* p : {static_cast<void*>(s.occ), static_cast<void*>(s.sdf), s.workspace, s.summary, s.gathered,
-                      s.carries, static_cast<void*>(s.minmax)})
-        if (p) (void)hipFree(p);
+      s = Slab();  // (the buffers, with their device current)
     }
   }
 };
@@ -239,14 +234,13 @@ int BuildSlabSet(SlabSet* set)
     for (hipEvent_t& e : s.marks) VGTX_HIP(hipEventCreate(&e), "create event");
     VGTX_CALL(vgt_hip_set_stream(s.ctx, s.stream));
     const size_t slab_voxels = lines * static_cast<size_t>(s.nzl);
-    s.workspace_bytes = vgt_hip_sdf_workspace_bytes(set->nx, set->ny, s.nzl);
-    VGTX_HIP(hipMalloc(reinterpret_cast<void**>(&s.occ), slab_voxels * sizeof(float)), "allocate slab occupancy");
-    VGTX_HIP(hipMalloc(reinterpret_cast<void**>(&s.sdf), slab_voxels * sizeof(float)), "allocate slab SDF");
-    VGTX_HIP(hipMalloc(&s.workspace, s.workspace_bytes), "allocate slab workspace");
-    VGTX_HIP(hipMalloc(&s.summary, record_bytes), "allocate slab summary");
-    VGTX_HIP(hipMalloc(&s.gathered, record_bytes * world), "allocate gathered summaries");
-    VGTX_HIP(hipMalloc(&s.carries, carries_bytes), "allocate slab carries");
-    VGTX_HIP(hipMalloc(reinterpret_cast<void**>(&s.minmax), 256), "allocate extrema");
+    VGTX_HIP(s.occ.Allocate(slab_voxels * sizeof(float)), "allocate slab occupancy");
+    VGTX_HIP(s.sdf.Allocate(slab_voxels * sizeof(float)), "allocate slab SDF");
+    VGTX_HIP(s.workspace.Reserve(vgt_hip_sdf_workspace_bytes(set->nx, set->ny, s.nzl)), "allocate slab workspace");
+    VGTX_HIP(s.summary.Allocate(record_bytes), "allocate slab summary");
+    VGTX_HIP(s.gathered.Allocate(record_bytes * world), "allocate gathered summaries");
+    VGTX_HIP(s.carries.Allocate(carries_bytes), "allocate slab carries");
+    VGTX_HIP(s.minmax.Allocate(256), "allocate extrema");
   }
   return VGT_HIP_OK;
 }
@@ -269,7 +263,7 @@ struct RaySet
   std::vector<int> helper_devices;
   int64_t num_cells = 0;
   std::vector<RayHelper> helpers;
-  int32_t* landing = nullptr;
+  vgt::DeviceTemp landing;  // int32 counts
 
   ~RaySet()
   {
@@ -285,7 +279,7 @@ struct RaySet
     if (landing)
     {
       (void)hipSetDevice(primary_device);
-      (void)hipFree(landing);
+      landing.Release();
     }
   }
 };
@@ -409,13 +403,13 @@ extern "C" int vgt_hipx_sdf_multi(const int* devices, int num_devices, const flo
   {
     VGTX_HIP(hipSetDevice(s.device), "set device");
     VGTX_HIP(hipEventRecord(s.marks[0], s.stream), "record event");
-    VGTX_HIP(hipMemcpy2DAsync(s.occ, static_cast<size_t>(s.nzl) * sizeof(float), occupancy_host + s.z0,
+    VGTX_HIP(hipMemcpy2DAsync(s.occ.as<float>(), static_cast<size_t>(s.nzl) * sizeof(float), occupancy_host + s.z0,
                               static_cast<size_t>(nz) * sizeof(float), static_cast<size_t>(s.nzl) * sizeof(float), lines,
                               hipMemcpyHostToDevice, s.stream),
              "copy slab occupancy to device");
     VGTX_HIP(hipEventRecord(s.marks[1], s.stream), "record event");
-    VGTX_CALL(vgt_hip_sdf_slab_begin_dev(s.ctx, s.occ, nx, ny, s.nzl, s.z0, unknown_is_filled, s.workspace,
-                                         s.workspace_bytes, s.summary, nullptr));
+    VGTX_CALL(vgt_hip_sdf_slab_begin_dev(s.ctx, s.occ.as<float>(), nx, ny, s.nzl, s.z0, unknown_is_filled,
+                                         s.workspace.data(), s.workspace.bytes(), s.summary.as<void>(), nullptr));
     VGTX_HIP(hipEventRecord(s.summary_ready, s.stream), "record event");
   }
 
@@ -433,8 +427,8 @@ extern "C" int vgt_hipx_sdf_multi(const int* devices, int num_devices, const flo
     {
       Slab& s = set.slabs[r];
       // 4-byte records moved as int32 words; rank r's block lands at gathered + r * record_bytes
-      const ncclResult_t res = rccl.AllGather(s.summary, s.gathered, record_bytes / sizeof(int32_t), ncclInt32,
-                                              comms->comms[r], s.stream);
+      const ncclResult_t res = rccl.AllGather(s.summary.as<void>(), s.gathered.as<void>(), record_bytes / sizeof(int32_t),
+                                              ncclInt32, comms->comms[r], s.stream);
       if (res != ncclSuccess)
       {
         (void)rccl.GroupEnd();
@@ -454,12 +448,12 @@ extern "C" int vgt_hipx_sdf_multi(const int* devices, int num_devices, const flo
       {
         Slab& src = set.slabs[q];
         VGTX_HIP(hipStreamWaitEvent(dst.stream, src.summary_ready, 0), "wait for summary");
-        char* to = static_cast<char*>(dst.gathered) + static_cast<size_t>(q) * record_bytes;
+        char* to = dst.gathered.as<char>() + static_cast<size_t>(q) * record_bytes;
         if (src.device == dst.device)
-          VGTX_HIP(hipMemcpyAsync(to, src.summary, record_bytes, hipMemcpyDeviceToDevice, dst.stream),
+          VGTX_HIP(hipMemcpyAsync(to, src.summary.as<void>(), record_bytes, hipMemcpyDeviceToDevice, dst.stream),
                    "copy summary between slabs");
         else
-          VGTX_HIP(hipMemcpyPeerAsync(to, dst.device, src.summary, src.device, record_bytes, dst.stream),
+          VGTX_HIP(hipMemcpyPeerAsync(to, dst.device, src.summary.as<void>(), src.device, record_bytes, dst.stream),
                    "copy summary between slabs");
       }
     }
@@ -472,16 +466,18 @@ extern "C" int vgt_hipx_sdf_multi(const int* devices, int num_devices, const flo
   {
     Slab& s = set.slabs[r];
     VGTX_HIP(hipSetDevice(s.device), "set device");
-    VGTX_CALL(vgt_hip_sdf_slab_carries_dev(s.ctx, s.gathered, world, r, nx, ny, nz, s.carries));
-    VGTX_CALL(vgt_hip_sdf_slab_finish_dev(s.ctx, nx, ny, s.nzl, s.z0, nz, resolution, add_virtual_border, s.carries,
-                                          s.sdf, s.workspace, s.workspace_bytes, s.minmax, nullptr));
+    void* const carries = s.carries.as<void>();
+    VGTX_CALL(vgt_hip_sdf_slab_carries_dev(s.ctx, s.gathered.as<void>(), world, r, nx, ny, nz, carries));
+    VGTX_CALL(vgt_hip_sdf_slab_finish_dev(s.ctx, nx, ny, s.nzl, s.z0, nz, resolution, add_virtual_border, carries,
+                                          s.sdf.as<float>(), s.workspace.data(), s.workspace.bytes(),
+                                          s.minmax.as<float>(), nullptr));
     VGTX_HIP(hipEventRecord(s.marks[2], s.stream), "record event");
-    VGTX_HIP(hipMemcpy2DAsync(sdf_host + s.z0, static_cast<size_t>(nz) * sizeof(float), s.sdf,
+    VGTX_HIP(hipMemcpy2DAsync(sdf_host + s.z0, static_cast<size_t>(nz) * sizeof(float), s.sdf.as<float>(),
                               static_cast<size_t>(s.nzl) * sizeof(float), static_cast<size_t>(s.nzl) * sizeof(float), lines,
                               hipMemcpyDeviceToHost, s.stream),
              "copy slab SDF to host");
     VGTX_HIP(hipEventRecord(s.marks[3], s.stream), "record event");
-    VGTX_HIP(hipMemcpyAsync(s.minmax_host, s.minmax, 2 * sizeof(float), hipMemcpyDeviceToHost, s.stream),
+    VGTX_HIP(hipMemcpyAsync(s.minmax_host, s.minmax.as<float>(), 2 * sizeof(float), hipMemcpyDeviceToHost, s.stream),
              "copy extrema to host");
   }
   float lo = INFINITY, hi = -INFINITY;
@@ -599,7 +595,7 @@ extern "C" int vgt_hipx_raycast_points_split(vgt_hip_ctx* ctx, vgt_hip_grids* gr
       for (int k = 0; k < helpers; k++)
         if (helper_list[k] != primary_device) need_landing = true;
       if (need_landing && (hipSetDevice(primary_device) != hipSuccess ||
-                           hipMalloc(reinterpret_cast<void**>(&fresh->landing), grid_bytes) != hipSuccess))
+                           fresh->landing.Allocate(grid_bytes) != hipSuccess))
         rc = FailMulti(VGT_HIP_ERR_RUNTIME, "[allocate landing grid] HIP error");
     }
     if (rc != VGT_HIP_OK)
@@ -692,9 +688,9 @@ extern "C" int vgt_hipx_raycast_points_split(vgt_hip_ctx* ctx, vgt_hip_grids* gr
     const auto* mine = static_cast<const int32_t*>(vgt_hip_tracking_grids_dev_ptr(h.grids, 0));
     if (h.device != primary_device)
     {
-      VGTX_HIP(hipMemcpyPeerAsync(set.landing, primary_device, mine, h.device, grid_bytes, primary_stream),
+      VGTX_HIP(hipMemcpyPeerAsync(set.landing.as<void>(), primary_device, mine, h.device, grid_bytes, primary_stream),
                "copy a share's tracking grid");
-      mine = set.landing;
+      mine = set.landing.as<int32_t>();
     }
     VGTX_HIP(vgt::LaunchAccumulateCounts(target, mine, static_cast<int64_t>(counts), primary_stream),
              "add a share's tracking grid");
