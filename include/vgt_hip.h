@@ -481,6 +481,49 @@ int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int
                                      int component_types, uint32_t* labels_host, uint32_t* num_components,
                                      vgt_hip_component_topology_t* out_host, uint64_t out_capacity);
 
+/* ---- triangle meshes into occupancy: mesh_rasterizer::RasterizeMesh (I/mesh_rasterizer.hpp,
+ * S/mesh_rasterizer.cpp:105-229), csrc/mesh_kernels.hip.  Per triangle the bounding box of its vertices becomes an index
+ * range (LocationToGridIndex), every cell of the range is a candidate, and a cell whose centre lies within
+ * pow(resolution * 0.5 * sqrt(3.0), 2.0) (squared) of the triangle's "closest point" gets occupancy 1.0f; no other cell
+ * and no other byte is written.
+ *   vertices_xyz      3 doubles per vertex, in the frame world_from_grid maps to
+ *   triangles         3 int32 vertex indices per triangle
+ *   cells, cell_bytes the map: records of 4 (OccupancyCell) or 8 bytes (OccupancyComponentCell), the float occupancy at
+ *                     offset 0, X-major / Z fastest; modified in place
+ *   world_from_grid   OriginTransform, 16 doubles column-major (cell centre -> location); grid_from_world its inverse
+ *                     (bounding box -> indices), as the reference's grid holds both.  NULL for both: the grid frame.
+ *   enforce_contains  non-zero: an intersecting cell outside the grid fails the call (VGT_HIP_ERR_RUNTIME, "Triangle is
+ *                     not contained by occupancy map (triangle N)", N the first such triangle); the host map is not
+ *                     written then, a device map's content is unspecified.  Outside cells of a range are evaluated
+ *                     literally in this mode.  Zero: ranges are clamped to the grid first (same result: the reference
+ *                     skips outside cells).
+ *   rule              VGT_HIP_MESH_RULE_REFERENCE: the literal port of CalcClosestPointOnTriangle (:59-102), which ranks
+ *                     the three edge candidates by their own squared norm -- their distance to the frame's origin, not
+ *                     to the query point (:82-84) --, so its result changes when a mesh is translated and cells along
+ *                     slanted edges can be missed.  VGT_HIP_MESH_RULE_NEAREST: the same structure, ranked by the squared
+ *                     distance to the query point (an extension: the watertight variant).
+ * All geometry in double without FMA contraction, in the operation order stated at the top of csrc/mesh_kernels.hip.
+ * Errors (VGT_HIP_ERR_INVALID_ARGUMENT, nothing rasterized): a vertex index out of range, a non-finite vertex, a
+ * triangle whose normal has squared norm 0 (the reference's behaviour for the last two depends on code that is not
+ * available; rejected here), and index ranges of more than 2^36 candidate cells in total.
+ * The _dev form takes device pointers for vertices, triangles and cells and waits for the triangles' validation; without
+ * enforce_contains the rasterization itself is left enqueued on the context's stream.
+ * vgt_hip_mesh_grid_for: the map RasterizeMeshIntoOccupancyMap builds (:243-269): per-axis lower / upper over ALL
+ * vertices, counts = ceil(((upper - lower) + 2 * resolution) / resolution), origin = lower - resolution (a translation).
+ * Pure host code. */
+#define VGT_HIP_MESH_RULE_REFERENCE 0
+#define VGT_HIP_MESH_RULE_NEAREST 1
+int vgt_hip_rasterize_mesh(vgt_hip_ctx* ctx, const double* vertices_xyz_host, int64_t num_vertices,
+                           const int32_t* triangles_host, int64_t num_triangles, void* cells_host, int cell_bytes,
+                           int64_t nx, int64_t ny, int64_t nz, double resolution, const double* world_from_grid,
+                           const double* grid_from_world, int enforce_contains, int rule);
+int vgt_hip_rasterize_mesh_dev(vgt_hip_ctx* ctx, const double* vertices_xyz_dev, int64_t num_vertices,
+                               const int32_t* triangles_dev, int64_t num_triangles, void* cells_dev, int cell_bytes,
+                               int64_t nx, int64_t ny, int64_t nz, double resolution, const double* world_from_grid,
+                               const double* grid_from_world, int enforce_contains, int rule);
+int vgt_hip_mesh_grid_for(const double* vertices_xyz_host, int64_t num_vertices, double resolution, int64_t* nx,
+                          int64_t* ny, int64_t* nz, double* origin_xyz);
+
 /* ---- multi-GPU: the grid is cut into Z slabs, one device per slab (BASELINE.json config 5).
  * Lines along Y and X are local to a slab; only the first pass (nearest voxel of the other class
  * along Z) crosses slabs, and all it needs from the other slabs is, per (x, y) line, the nearest

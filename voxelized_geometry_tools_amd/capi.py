@@ -84,6 +84,9 @@ SIGNATURES = {
     "vgt_hip_component_topology_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint32, _p]),
     "vgt_hip_component_topology": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_uint64]),
     "vgt_hip_cells_component_topology": (_int, [_p, _p, _int, _int, _p, _p, _p, ctypes.c_uint64]),
+    "vgt_hip_rasterize_mesh": (_int, [_p, _p, _i64, _p, _i64, _p, _int, _i64, _i64, _i64, _f64, _p, _p, _int, _int]),
+    "vgt_hip_rasterize_mesh_dev": (_int, [_p, _p, _i64, _p, _i64, _p, _int, _i64, _i64, _i64, _f64, _p, _p, _int, _int]),
+    "vgt_hip_mesh_grid_for": (_int, [_p, _i64, _f64, _p, _p, _p, _p]),
     "vgt_hipx_sdf_multi": (_int, [_p, _int, _p, _i64, _i64, _i64, _f64, _int, _int, _p, _p, _p]),
     "vgt_hipx_release": (None, []),
     "vgt_hipx_last_timing": (_int, [_p]),
@@ -129,6 +132,10 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
 }
 
+
+# closest-point rules of the mesh rasterizer (VGT_HIP_MESH_RULE_*)
+MESH_RULE_REFERENCE = 0
+MESH_RULE_NEAREST = 1
 
 # vgt_hip_component_topology_t
 COMPONENT_TOPOLOGY = np.dtype([(name, np.int32) for name in (
@@ -228,6 +235,23 @@ def _topology_table(call, capacity=256):
         check(rc)
         return table[:count.value + 1].copy()
     raise VgtHipError("the component count changed between two calls")
+
+
+def mesh_grid_for(vertices, resolution):
+    """vgt_hip_mesh_grid_for: ((nx, ny, nz), origin xyz float64[3]) of the map RasterizeMeshIntoOccupancyMap builds for
+    these vertices.  Pure host code, no device needed."""
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    counts = (_i64 * 3)()
+    origin = np.zeros(3, dtype=np.float64)
+    check(load().vgt_hip_mesh_grid_for(_ptr(v), len(v), float(resolution), ctypes.byref(counts, 0),
+                                       ctypes.byref(counts, 8), ctypes.byref(counts, 16), _ptr(origin)))
+    return (int(counts[0]), int(counts[1]), int(counts[2])), origin
+
+
+def _mesh_transforms(world_from_grid, grid_from_world):
+    wfg = None if world_from_grid is None else np.ascontiguousarray(world_from_grid, dtype=np.float64).reshape(16)
+    gfw = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+    return wfg, gfw
 
 
 def device_count():
@@ -366,6 +390,64 @@ class Context:
                                                        *[int(v) for v in shape], int(component_types),
                                                        int(num_components), _ptr(table)))
         return table
+
+    def rasterize_mesh(self, vertices, triangles, cells, resolution, world_from_grid=None, grid_from_world=None,
+                       enforce_contains=False, rule=MESH_RULE_REFERENCE):
+        """RasterizeMesh into a host map, in place: `cells` is a C-contiguous (nx, ny, nz) array of float32 or of
+        8-byte records with the float occupancy first (OCCUPANCY_COMPONENT_CELL).  Transforms: 16 doubles column-major
+        each, both or neither (None = the grid frame).  Returns `cells`."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        if not isinstance(cells, np.ndarray) or cells.ndim != 3 or not cells.flags.c_contiguous or \
+                not cells.flags.writeable:
+            raise ValueError("cells must be a writeable C-contiguous (nx, ny, nz) array")
+        wfg, gfw = _mesh_transforms(world_from_grid, grid_from_world)
+        check(self._lib.vgt_hip_rasterize_mesh(self.handle, _ptr(v), len(v), _ptr(t), len(t), _ptr(cells),
+                                               cells.dtype.itemsize, *cells.shape, float(resolution), _ptr(wfg),
+                                               _ptr(gfw), int(bool(enforce_contains)), int(rule)))
+        return cells
+
+    def rasterize_mesh_dev(self, vertices_ptr, num_vertices, triangles_ptr, num_triangles, cells_ptr, cell_bytes, shape,
+                           resolution, world_from_grid=None, grid_from_world=None, enforce_contains=False,
+                           rule=MESH_RULE_REFERENCE):
+        """vgt_hip_rasterize_mesh_dev: vertices (float64), triangles (int32) and the map on the device, the map
+        modified in place (the transforms are host arrays)."""
+        wfg, gfw = _mesh_transforms(world_from_grid, grid_from_world)
+        check(self._lib.vgt_hip_rasterize_mesh_dev(self.handle, _ptr(vertices_ptr), int(num_vertices),
+                                                   _ptr(triangles_ptr), int(num_triangles), _ptr(cells_ptr),
+                                                   int(cell_bytes), *[int(c) for c in shape], float(resolution),
+                                                   _ptr(wfg), _ptr(gfw), int(bool(enforce_contains)), int(rule)))
+
+    def mesh_sdf(self, vertices, triangles, resolution, rule=MESH_RULE_REFERENCE, unknown_is_filled=True,
+                 add_virtual_border=False, with_occupancy=False):
+        """Mesh -> SDF: mesh_grid_for -> a zeroed device map -> rasterize_mesh_dev -> sdf_dev; the grid never visits the
+        host in between.  Returns (sdf float32 (nx, ny, nz), minimum, maximum, origin xyz) -- the map's transform is the
+        translation to `origin` -- and, with_occupancy=True, the rasterized occupancy as a fifth item."""
+        import torch
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        shape, origin = mesh_grid_for(v, resolution)
+        wfg = np.eye(4)
+        wfg[:3, 3] = origin
+        gfw = np.eye(4)
+        gfw[:3, 3] = -origin
+        device = "cuda:%d" % self._lib.vgt_hip_device_of(self.handle)
+        v_dev = torch.from_numpy(v).to(device)
+        t_dev = torch.from_numpy(t).to(device)
+        occ_dev = torch.zeros(shape, dtype=torch.float32, device=device)
+        sdf_dev = torch.empty(shape, dtype=torch.float32, device=device)
+        ws_bytes = sdf_workspace_bytes(shape)
+        ws_dev = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        minmax_dev = torch.empty(2, dtype=torch.float32, device=device)
+        torch.cuda.synchronize(device)
+        self.rasterize_mesh_dev(v_dev.data_ptr(), len(v), t_dev.data_ptr(), len(t), occ_dev.data_ptr(), 4, shape,
+                                resolution, wfg.T.reshape(16), gfw.T.reshape(16), True, rule)
+        self.sdf_dev(occ_dev.data_ptr(), shape, resolution, sdf_dev.data_ptr(), ws_dev.data_ptr(), ws_bytes,
+                     minmax_dev.data_ptr(), unknown_is_filled, add_virtual_border)
+        self.synchronize()
+        lo, hi = (float(x) for x in minmax_dev.cpu().numpy())
+        out = (sdf_dev.cpu().numpy(), lo, hi, origin)
+        return out + (occ_dev.cpu().numpy(),) if with_occupancy else out
 
     def trim(self):
         """Frees the device buffers the context caches between host-pointer calls."""

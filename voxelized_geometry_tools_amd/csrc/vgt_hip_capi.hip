@@ -4,10 +4,13 @@
 
 #include "vgt_internal.hpp"
 #include "device_memory.hpp"
+#include "mesh_kernels.hpp"
 #include "edt_crosscheck.hpp"
 #include "host_pages.hpp"
 
 #include <algorithm>
+#include <cmath>
+#include <limits>
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -67,6 +70,8 @@ struct vgt_hip_ctx
   vgt::DeviceCache sdf_in, sdf_out, sdf_ws;
   // Scratch of the component labelling (union-find labels + scan counts), kept like the buffers above
   vgt::DeviceCache component_ws;
+  // Scratch of the mesh rasterizer (triangle records, work-list offsets, totals and status), kept likewise
+  vgt::DeviceCache mesh_ws;
   // Page-locked staging ring of the batched downloads (DownloadToHostArrays): kStagingSlots slots of kStagingSlotBytes,
   // allocated by the first such call, kept until vgt_hip_trim / vgt_hip_destroy; one event per slot.
   void* host_staging = nullptr;
@@ -238,7 +243,8 @@ hipError_t DrainKeepingFirst(hipStream_t s, hipError_t err)
 
 void FreeCachedSdfBuffers(vgt_hip_ctx* ctx)
 {
-  for (vgt::DeviceCache* b : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws})
+  for (vgt::DeviceCache* b : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws,
+                             &ctx->mesh_ws})
     (void)b->Release();
   if (ctx->host_staging) (void)hipHostFree(ctx->host_staging);
   ctx->host_staging = nullptr;
@@ -2888,6 +2894,205 @@ int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int
   return LabelAndTopology(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
                           by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, cells->nx, cells->ny,
                           cells->nz, component_types, labels_host, num_components, out_host, out_capacity);
+}
+
+/* ------------------------------ mesh rasterizer ------------------------------ */
+
+namespace
+{
+constexpr int64_t kMeshMaxCells = int64_t{1} << 40;
+constexpr int64_t kMeshMaxTriangles = 0x7fffffffLL;
+
+// Everything that can be said about the arguments of the two entry points before any HIP call.
+int CheckMeshArguments(const vgt_hip_ctx* ctx, const void* vertices, int64_t num_vertices, const void* triangles,
+                       int64_t num_triangles, const void* cells, int cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                       double resolution, const double* world_from_grid, const double* grid_from_world, int rule)
+{
+  if (!ctx || !vertices || !triangles || !cells) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_vertices < 0 || num_triangles < 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the numbers of vertices and triangles must not be negative");
+  if (num_triangles > kMeshMaxTriangles) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "at most 2^31 - 1 triangles per call");
+  if (nx <= 0 || ny <= 0 || nz <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must be positive");
+  if (nx > kMeshMaxCells || ny > kMeshMaxCells / nx || nz > kMeshMaxCells / (nx * ny))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the mesh rasterizer supports grids of at most 2^40 cells");
+  if (!(resolution > 0.0) || !std::isfinite(resolution))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "resolution must be finite and greater than zero");
+  if (cell_bytes != 4 && cell_bytes != 8)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "cell_bytes must be 4 (OccupancyCell) or 8 (OccupancyComponentCell)");
+  if (rule != VGT_HIP_MESH_RULE_REFERENCE && rule != VGT_HIP_MESH_RULE_NEAREST)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "rule must be 0 (reference) or 1 (nearest)");
+  if ((world_from_grid == nullptr) != (grid_from_world == nullptr))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "give both transforms (world_from_grid and grid_from_world) or neither");
+  return VGT_HIP_OK;
+}
+
+vgt::MeshGrid MakeMeshGrid(int cell_bytes, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                           const double* world_from_grid, const double* grid_from_world, int enforce_contains, int rule)
+{
+  vgt::MeshGrid grid{};
+  grid.nx = nx;
+  grid.ny = ny;
+  grid.nz = nz;
+  grid.resolution = resolution;
+  // S/mesh_rasterizer.cpp:117-119, in that form
+  const double min_check_radius = resolution * 0.5;
+  const double max_check_radius = min_check_radius * std::sqrt(3.0);
+  grid.max_check_radius_squared = std::pow(max_check_radius, 2.0);
+  grid.has_transform = world_from_grid ? 1 : 0;
+  if (world_from_grid)
+  {
+    std::memcpy(grid.world_from_grid, world_from_grid, sizeof(grid.world_from_grid));
+    std::memcpy(grid.grid_from_world, grid_from_world, sizeof(grid.grid_from_world));
+  }
+  grid.enforce = enforce_contains ? 1 : 0;
+  grid.rule = rule;
+  grid.cell_bytes = cell_bytes;
+  return grid;
+}
+
+// Set-up, the checks between the two steps, the bricks.  Caller holds the context mutex and has set the device.  Waits
+// for the set-up's findings; under `enforce` also for the bricks' (otherwise the bricks are left enqueued).
+int RunMeshRasterize(vgt_hip_ctx* ctx, const double* vertices_dev, int64_t num_vertices, const int32_t* triangles_dev,
+                     int64_t num_triangles, void* cells_dev, const vgt::MeshGrid& grid)
+{
+  const size_t need = vgt::MeshScratchBytes(num_triangles);
+  if (need > ctx->mesh_ws.bytes())
+  {
+    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the mesh scratch");
+    VGT_TRY_HIP(ctx->mesh_ws.Reserve(need), "allocate mesh scratch");
+  }
+  void* const scratch = ctx->mesh_ws.data();
+  vgt::MeshTotals totals{};
+  vgt::MeshStatus status{};
+  hipError_t err = vgt::LaunchMeshSetup(vertices_dev, num_vertices, triangles_dev, num_triangles, grid, scratch, ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&totals, vgt::MeshTotalsPtr(scratch, num_triangles), sizeof(totals), hipMemcpyDeviceToHost,
+                         ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&status, vgt::MeshStatusPtr(scratch, num_triangles), sizeof(status), hipMemcpyDeviceToHost,
+                         ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "mesh set-up");  // (both are on this stack)
+  if (status.bits & vgt::kMeshBadIndex)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "triangle " + std::to_string(status.first[0]) + " has a vertex index out of range");
+  if (status.bits & vgt::kMeshNonFinite)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "triangle " + std::to_string(status.first[1]) + " has a non-finite vertex");
+  if (status.bits & vgt::kMeshDegenerate)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "triangle " + std::to_string(status.first[2]) + " is degenerate (its normal has zero length)");
+  if (totals.cells > vgt::kMeshMaxCandidateCells)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "the triangles' index ranges hold more than 2^36 candidate cells: refused (is the mesh inside the map?)");
+  VGT_TRY_HIP(vgt::LaunchMeshBricks(grid, num_triangles, totals.bricks, scratch, cells_dev, ctx->stream), "mesh bricks");
+  if (!grid.enforce) return VGT_HIP_OK;
+  err = hipMemcpyAsync(&status, vgt::MeshStatusPtr(scratch, num_triangles), sizeof(status), hipMemcpyDeviceToHost,
+                       ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "mesh bricks");
+  if (status.bits & vgt::kMeshNotContained)
+    return Fail(VGT_HIP_ERR_RUNTIME,
+                "Triangle is not contained by occupancy map (triangle " + std::to_string(status.first[3]) + ")");
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+int vgt_hip_rasterize_mesh_dev(vgt_hip_ctx* ctx, const double* vertices_xyz_dev, int64_t num_vertices,
+                               const int32_t* triangles_dev, int64_t num_triangles, void* cells_dev, int cell_bytes,
+                               int64_t nx, int64_t ny, int64_t nz, double resolution, const double* world_from_grid,
+                               const double* grid_from_world, int enforce_contains, int rule)
+{
+  const int rc = CheckMeshArguments(ctx, vertices_xyz_dev, num_vertices, triangles_dev, num_triangles, cells_dev,
+                                    cell_bytes, nx, ny, nz, resolution, world_from_grid, grid_from_world, rule);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_triangles == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const vgt::MeshGrid grid =
+      MakeMeshGrid(cell_bytes, nx, ny, nz, resolution, world_from_grid, grid_from_world, enforce_contains, rule);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunMeshRasterize(ctx, vertices_xyz_dev, num_vertices, triangles_dev, num_triangles, cells_dev, grid);
+}
+
+int vgt_hip_rasterize_mesh(vgt_hip_ctx* ctx, const double* vertices_xyz_host, int64_t num_vertices,
+                           const int32_t* triangles_host, int64_t num_triangles, void* cells_host, int cell_bytes,
+                           int64_t nx, int64_t ny, int64_t nz, double resolution, const double* world_from_grid,
+                           const double* grid_from_world, int enforce_contains, int rule)
+{
+  const int rc = CheckMeshArguments(ctx, vertices_xyz_host, num_vertices, triangles_host, num_triangles, cells_host,
+                                    cell_bytes, nx, ny, nz, resolution, world_from_grid, grid_from_world, rule);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_triangles == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const vgt::MeshGrid grid =
+      MakeMeshGrid(cell_bytes, nx, ny, nz, resolution, world_from_grid, grid_from_world, enforce_contains, rule);
+  const size_t vertex_bytes = static_cast<size_t>(num_vertices) * 3 * sizeof(double);
+  const size_t triangle_bytes = static_cast<size_t>(num_triangles) * 3 * sizeof(int32_t);
+  const size_t map_bytes = static_cast<size_t>(nx * ny * nz) * static_cast<size_t>(cell_bytes);
+  vgt::DeviceTemp vertices_dev, triangles_dev, map_dev;
+  VGT_TRY_HIP(vertices_dev.Allocate(vertex_bytes ? vertex_bytes : sizeof(double)), "allocate vertices");
+  VGT_TRY_HIP(triangles_dev.Allocate(triangle_bytes), "allocate triangles");
+  VGT_TRY_HIP(map_dev.Allocate(map_bytes), "allocate the map");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipError_t err = hipSuccess;
+  if (vertex_bytes)
+    err = hipMemcpyAsync(vertices_dev.as<void>(), vertices_xyz_host, vertex_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(triangles_dev.as<void>(), triangles_host, triangle_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(map_dev.as<void>(), cells_host, map_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (err != hipSuccess)
+  {
+    (void)hipStreamSynchronize(ctx->stream);  // (an upload may still be in flight)
+    return FailHip("upload the mesh and the map", err);
+  }
+  const int result = RunMeshRasterize(ctx, vertices_dev.as<double>(), num_vertices, triangles_dev.as<int32_t>(),
+                                      num_triangles, map_dev.as<void>(), grid);
+  if (result != VGT_HIP_OK)
+  {
+    (void)hipStreamSynchronize(ctx->stream);  // the host map stays as it was
+    return result;
+  }
+  err = hipMemcpyAsync(cells_host, map_dev.as<void>(), map_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "download the map");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_mesh_grid_for(const double* vertices_xyz_host, int64_t num_vertices, double resolution, int64_t* nx,
+                          int64_t* ny, int64_t* nz, double* origin_xyz)
+{
+  if (!vertices_xyz_host || !nx || !ny || !nz || !origin_xyz) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_vertices <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a mesh needs at least one vertex");
+  if (!(resolution > 0.0) || !std::isfinite(resolution))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "resolution must be finite and greater than zero");
+  // S/mesh_rasterizer.cpp:243-269
+  double lower[3], upper[3];
+  for (int a = 0; a < 3; a++)
+  {
+    lower[a] = std::numeric_limits<double>::infinity();
+    upper[a] = -std::numeric_limits<double>::infinity();
+  }
+  for (int64_t i = 0; i < num_vertices; i++)
+    for (int a = 0; a < 3; a++)
+    {
+      const double v = vertices_xyz_host[3 * i + a];
+      if (!std::isfinite(v)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "vertex " + std::to_string(i) + " is not finite");
+      lower[a] = v < lower[a] ? v : lower[a];
+      upper[a] = v > upper[a] ? v : upper[a];
+    }
+  const double buffer_size = resolution * 2.0;
+  int64_t counts[3];
+  for (int a = 0; a < 3; a++)
+  {
+    const double object_size = upper[a] - lower[a];
+    const double grid_dimension = object_size + buffer_size;
+    const double cells = std::ceil(grid_dimension / resolution);  // VoxelGridSizes::FromGridSizes
+    if (!(cells >= 1.0 && cells <= 2147483647.0))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the mesh needs more than 2^31 - 1 cells along an axis at this resolution");
+    counts[a] = static_cast<int64_t>(cells);
+  }
+  *nx = counts[0];
+  *ny = counts[1];
+  *nz = counts[2];
+  for (int a = 0; a < 3; a++) origin_xyz[a] = lower[a] - resolution;
+  return VGT_HIP_OK;
 }
 
 /* --------------------------------- multi-GPU --------------------------------- */

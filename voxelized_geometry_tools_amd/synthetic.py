@@ -155,3 +155,95 @@ def kernel_sources_sha256(group="edt"):
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()
+
+
+# ---- triangle meshes for the mesh rasterizer: (vertices float64 [V, 3], triangles int32 [T, 3]) ----
+def mesh_box(lower=(0.0, 0.0, 0.0), upper=(1.0, 1.0, 1.0)):
+    """An axis-aligned box, 8 vertices and 12 outward-facing triangles."""
+    lo, hi = np.asarray(lower, np.float64), np.asarray(upper, np.float64)
+    v = np.array([[(hi if (i >> a) & 1 else lo)[a] for a in range(3)] for i in range(8)], dtype=np.float64)
+    t = np.array([[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4],
+                  [2, 6, 3], [3, 6, 7], [0, 4, 2], [2, 4, 6], [1, 3, 5], [3, 7, 5]], dtype=np.int32)
+    return v, t
+
+
+def mesh_icosphere(subdivisions=2, radius=1.0, centre=(0.0, 0.0, 0.0)):
+    """An icosahedron subdivided `subdivisions` times, every vertex pushed onto the sphere: 20 * 4^s triangles with
+    non-dyadic coordinates."""
+    g = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+         (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    v = [tuple(np.asarray(p, np.float64) / np.sqrt(1.0 + g * g)) for p in v]
+    t = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+         (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7),
+         (9, 8, 1)]
+    for _ in range(int(subdivisions)):
+        middle = {}
+
+        def mid(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in middle:
+                m = (np.asarray(v[a]) + np.asarray(v[b])) * 0.5
+                v.append(tuple(m / np.sqrt((m * m).sum())))
+                middle[key] = len(v) - 1
+            return middle[key]
+
+        t = [tri for a, b, c in t for tri in
+             ((a, mid(a, b), mid(c, a)), (b, mid(b, c), mid(a, b)), (c, mid(c, a), mid(b, c)),
+              (mid(a, b), mid(b, c), mid(c, a)))]
+    vertices = np.asarray(v, dtype=np.float64) * float(radius) + np.asarray(centre, dtype=np.float64)
+    return vertices, np.asarray(t, dtype=np.int32)
+
+
+def mesh_torus(major_radius=1.0, minor_radius=0.35, major_segments=48, minor_segments=24, centre=(0.0, 0.0, 0.0)):
+    """A torus around the Z axis: 2 * major_segments * minor_segments triangles."""
+    nu, nv = int(major_segments), int(minor_segments)
+    u = 2.0 * np.pi * np.arange(nu) / nu
+    w = 2.0 * np.pi * np.arange(nv) / nv
+    uu, ww = np.meshgrid(u, w, indexing="ij")
+    ring = major_radius + minor_radius * np.cos(ww)
+    vertices = np.stack([ring * np.cos(uu), ring * np.sin(uu), minor_radius * np.sin(ww)], axis=-1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    a = (i * nv + j).reshape(-1)
+    b = (((i + 1) % nu) * nv + j).reshape(-1)
+    c = (((i + 1) % nu) * nv + (j + 1) % nv).reshape(-1)
+    d = (i * nv + (j + 1) % nv).reshape(-1)
+    triangles = np.concatenate([np.stack([a, b, c], axis=1), np.stack([a, c, d], axis=1)]).astype(np.int32)
+    return vertices + np.asarray(centre, dtype=np.float64), triangles
+
+
+def mesh_triangle_soup(num_triangles, lower=(0.0, 0.0, 0.0), upper=(1.0, 1.0, 1.0), max_edge=0.1, seed=42):
+    """`num_triangles` unconnected random triangles inside a box: a corner uniform in the box, the other two within
+    max_edge of it per axis (clipped to the box).  Non-dyadic coordinates, three vertices of its own per triangle."""
+    n = int(num_triangles)
+    lo, hi = np.asarray(lower, np.float64), np.asarray(upper, np.float64)
+    u = uniform_array(seed, 9 * n).reshape(n, 3, 3)
+    first = lo + u[:, 0, :] * (hi - lo)
+    vertices = np.empty((n, 3, 3), dtype=np.float64)
+    vertices[:, 0] = first
+    vertices[:, 1] = np.clip(first + (2.0 * u[:, 1, :] - 1.0) * max_edge, lo, hi)
+    vertices[:, 2] = np.clip(first + (2.0 * u[:, 2, :] - 1.0) * max_edge, lo, hi)
+    return vertices.reshape(-1, 3), np.arange(3 * n, dtype=np.int32).reshape(n, 3)
+
+
+def rigid_xform(axis=(0.0, 0.0, 1.0), angle=0.0, translation=(0.0, 0.0, 0.0)):
+    """(transform, inverse) of a rotation about `axis` by `angle` followed by a translation, each as 16 doubles
+    column-major; the inverse is R^T, -(R^T t), as a rigid transform's inverse is formed."""
+    k = np.asarray(axis, np.float64)
+    k = k / np.sqrt((k * k).sum())
+    kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]], dtype=np.float64)
+    rot = np.eye(3) + np.sin(angle) * kx + (1.0 - np.cos(angle)) * (kx @ kx)
+    t = np.asarray(translation, np.float64)
+    m = np.eye(4)
+    m[:3, :3] = rot
+    m[:3, 3] = t
+    inv = np.eye(4)
+    inv[:3, :3] = rot.T
+    inv[:3, 3] = -(rot.T @ t)
+    return m.T.reshape(16).copy(), inv.T.reshape(16).copy()
+
+
+def mesh_transformed(vertices, xform):
+    """The vertices mapped through a column-major 4x4 transform (translate / rotate a mesh)."""
+    m = np.asarray(xform, np.float64).reshape(4, 4).T
+    return np.asarray(vertices, np.float64) @ m[:3, :3].T + m[:3, 3]
