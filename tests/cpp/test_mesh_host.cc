@@ -3,6 +3,7 @@
 //   test_mesh_host              needs a HIP device
 //   test_mesh_host --no-device  only the errors that are raised before a device is touched
 #include <vgt_hip.h>
+#include <vgt_hip/hip_pointcloud_voxelizer.hpp>  // ReleaseCachedDeviceMemory
 #include <vgt_hip/mesh_rasterizer.hpp>
 
 #include <cstdio>
@@ -139,6 +140,23 @@ int main(int argc, char** argv)
     for (int64_t x = 0; x < 10; x++)
       for (int64_t y = 0; y < 10; y++)
         for (int64_t z = 0; z < 2; z++) CHECK((sdf.GetIndexImmutable(x, y, z) < 0.0f) == (Occupancy(map, x, y, z) == 1.0f));
+
+    // The rasterizer's scratch is cached by the process's one context of the device, which ReleaseCachedDeviceMemory()
+    // trims: the same mesh into a fresh map afterwards gives the same cells, and mesh -> SDF the same field bit for bit.
+    ReleaseCachedDeviceMemory();
+    OccupancyMap fresh(Isometry3::Translation(-0.125, -0.125, -0.125), "mesh", resolution, 10, 10, 2, 0.0f);
+    mesh_rasterizer::RasterizeMesh(vertices, triangles, fresh);
+    const auto same_bits = [](const OccupancyMap& a, const OccupancyMap& b) {
+      return a.GetImmutableRawData().size() == b.GetImmutableRawData().size() &&
+             std::memcmp(a.GetImmutableRawData().data(), b.GetImmutableRawData().data(),
+                         a.GetImmutableRawData().size() * sizeof(float)) == 0;
+    };
+    CHECK(same_bits(fresh, map));
+    ReleaseCachedDeviceMemory();
+    const SignedDistanceField sdf_again =
+        mesh_rasterizer::MeshToSignedDistanceField(vertices, triangles, resolution, parameters);
+    CHECK(same_bits(sdf_again.grid, sdf.grid));
+    CHECK(sdf_again.minimum == sdf.minimum && sdf_again.maximum == sdf.maximum);
   }
   if (g_failures == 0) std::printf("PASSED\n");
   return g_failures == 0 ? 0 : 1;

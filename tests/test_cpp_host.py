@@ -9,15 +9,13 @@ import sys
 import pytest
 
 from conftest import ROOT
+from cpp_build import build
 
 BINARY = os.path.join(ROOT, "tests", "cpp", "test_hip_host")
 
 
 def _build():
-    if not os.path.exists(os.path.join(ROOT, "voxelized_geometry_tools_amd", "libvgt_hip.so")):
-        subprocess.check_call(["make", "-s", "-j4", "-C",
-                               os.path.join(ROOT, "voxelized_geometry_tools_amd", "csrc")])
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp")])
+    build("test_hip_host")
 
 
 def test_backend_unavailable_behaviour():

@@ -1,29 +1,18 @@
 """ComputeComponentTopology of the C++ host layer (include/vgt_hip/hip_pointcloud_voxelizer.hpp) through
-tests/cpp/test_topology_host.cc, which this module compiles itself against the host layer's library."""
+tests/cpp/test_topology_host.cc (built by tests/cpp/Makefile)."""
 import os
 import subprocess
 
 import pytest
 
 from conftest import ROOT
+from cpp_build import build
 
-CPP = os.path.join(ROOT, "tests", "cpp")
-PKG = os.path.join(ROOT, "voxelized_geometry_tools_amd")
-BINARY = os.path.join(CPP, "test_topology_host")
+BINARY = os.path.join(ROOT, "tests", "cpp", "test_topology_host")
 
 
 def _build():
-    if not os.path.exists(os.path.join(PKG, "libvgt_hip.so")):
-        subprocess.check_call(["make", "-s", "-j4", "-C", os.path.join(PKG, "csrc")])
-    subprocess.check_call(["make", "-s", "-C", CPP, os.path.join("..", "..", "voxelized_geometry_tools_amd",
-                                                                 "libvgt_hip_host.so")])
-    source = os.path.join(CPP, "test_topology_host.cc")
-    newest = max(os.path.getmtime(p) for p in (source, os.path.join(PKG, "libvgt_hip_host.so")))
-    if os.path.exists(BINARY) and os.path.getmtime(BINARY) >= newest:
-        return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I" + os.path.join(ROOT, "include"),
-                           "-o", BINARY, source, "-L" + PKG, "-lvgt_hip_host", "-lvgt_hip",
-                           "-Wl,-rpath,$ORIGIN/../../voxelized_geometry_tools_amd"])
+    build("test_topology_host")
 
 
 def test_argument_errors_without_device():

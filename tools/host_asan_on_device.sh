@@ -17,7 +17,7 @@ build)
     HIPFLAGS="-O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -fvisibility=hidden -fsanitize=address -fno-gpu-sanitize -fno-omit-frame-pointer"
   $CL -std=c++17 -O1 -g -pthread -fsanitize=address -shared-libasan -fno-omit-frame-pointer \
     -o "$ROOT/tests/cpp/test_hip_host_devasan" "$ROOT/tests/cpp/test_hip_host.cc" \
-    "$PKG/csrc/host/hip_voxelization_helpers.cc" "$PKG/csrc/host/hip_pointcloud_voxelizer.cc" \
+    "$PKG"/csrc/host/hip_*.cc \
     -L"$PKG" -lvgt_hip_hostasan -Wl,-rpath,"$PKG" -Wl,-rpath,"$RT"
   ;;
 run)

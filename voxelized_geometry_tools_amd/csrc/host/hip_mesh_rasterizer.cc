@@ -1,13 +1,8 @@
 // include/vgt_hip/mesh_rasterizer.hpp on the C ABI (vgt_hip_rasterize_mesh, vgt_hip_mesh_grid_for).
 #include "../../../include/vgt_hip/mesh_rasterizer.hpp"
 
-#include "../../../include/vgt_hip.h"
 #include "../../../include/vgt_hip/hip_pointcloud_voxelizer.hpp"
-
-#include <map>
-#include <mutex>
-#include <stdexcept>
-#include <string>
+#include "host_internal.hpp"
 
 namespace vgt_hip
 {
@@ -18,26 +13,7 @@ namespace
 static_assert(sizeof(Vector3d) == 3 * sizeof(double) && sizeof(Vector3i) == 3 * sizeof(int32_t),
               "vertices and triangles are passed to the C ABI as packed arrays");
 
-[[noreturn]] void ThrowForCode(int rc, const std::string& message)
-{
-  if (rc == VGT_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(message);
-  throw std::runtime_error(message);
-}
-
-// One context per device for the life of the process (it keeps the rasterizer's scratch between calls).
-vgt_hip_ctx* SharedMeshContext(int hip_device)
-{
-  static std::mutex guard;
-  static std::map<int, vgt_hip_ctx*>* const contexts = new std::map<int, vgt_hip_ctx*>();
-  std::lock_guard<std::mutex> lock(guard);
-  auto found = contexts->find(hip_device);
-  if (found != contexts->end()) return found->second;
-  vgt_hip_ctx* ctx = nullptr;
-  const int rc = vgt_hip_create(hip_device, -1, &ctx);
-  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
-  (*contexts)[hip_device] = ctx;
-  return ctx;
-}
+using detail::ThrowForCode;
 
 template <typename Map>
 void Rasterize(const std::vector<Vector3d>& vertices, const Vector3i* triangles, size_t num_triangles, Map& map,
@@ -47,7 +23,8 @@ void Rasterize(const std::vector<Vector3d>& vertices, const Vector3i* triangles,
   auto& cells = map.GetMutableRawData();
   static_assert(sizeof(cells[0]) == 4 || sizeof(cells[0]) == 8, "OccupancyCell or OccupancyComponentCell");
   if (num_triangles == 0) return;
-  vgt_hip_ctx* const ctx = SharedMeshContext(hip_device);
+  // (the process's context of that device: it keeps the rasterizer's scratch between calls)
+  vgt_hip_ctx* const ctx = detail::SharedSdfContext(hip_device);
   const double no_vertex[3] = {0.0, 0.0, 0.0};  // (an empty vector has no data(): every index is out of range then)
   const int rc = vgt_hip_rasterize_mesh(
       ctx, vertices.empty() ? no_vertex : vertices.data()->data(), static_cast<int64_t>(vertices.size()),

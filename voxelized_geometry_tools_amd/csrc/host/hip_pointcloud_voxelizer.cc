@@ -11,10 +11,12 @@
 #include <mutex>
 #include <thread>
 
-#include "../../../include/vgt_hip.h"
+#include "host_internal.hpp"
 
 namespace vgt_hip
 {
+using detail::SharedSdfContext;
+using detail::ThrowForCode;
 using voxelized_geometry_tools::pointcloud_voxelization::FilterGridHandle;
 using voxelized_geometry_tools::pointcloud_voxelization::RetrieveOptionOrDefault;
 using voxelized_geometry_tools::pointcloud_voxelization::TrackingGridsHandle;
@@ -284,11 +286,7 @@ VoxelizerRuntime HipPointCloudVoxelizer::DoVoxelizePointClouds(
 
 namespace
 {
-// One context per device for the free-standing SDF entry points, created on first use and kept for
-// the life of the process (deliberately never destroyed: static destruction order against the HIP
-// runtime is not defined).  The context caches its device buffers, so a caller that extracts
-// fields repeatedly pays for context creation and hipMalloc once; the C ABI serialises concurrent
-// calls on one context.
+// the contexts of detail::SharedSdfContext (host_internal.hpp)
 std::mutex& SharedContextGuard()
 {
   static std::mutex guard;
@@ -299,8 +297,9 @@ std::map<int, vgt_hip_ctx*>& SharedContexts()
   static std::map<int, vgt_hip_ctx*>* contexts = new std::map<int, vgt_hip_ctx*>();
   return *contexts;
 }
+}  // namespace
 
-vgt_hip_ctx* SharedSdfContext(int device)
+vgt_hip_ctx* detail::SharedSdfContext(int device)
 {
   std::lock_guard<std::mutex> lock(SharedContextGuard());
   auto& contexts = SharedContexts();
@@ -312,7 +311,6 @@ vgt_hip_ctx* SharedSdfContext(int device)
   contexts[device] = ctx;
   return ctx;
 }
-}  // namespace
 
 void ReleaseCachedDeviceMemory()
 {
@@ -354,9 +352,7 @@ SignedDistanceField ExtractSignedDistanceField(
       map.Resolution(), parameters.unknown_is_filled ? 1 : 0,
       parameters.add_virtual_border ? 1 : 0, sdf.grid.GetMutableRawData().data(), &sdf.minimum,
       &sdf.maximum);
-  const std::string msg = (rc == VGT_HIP_OK) ? std::string() : std::string(vgt_hip_last_error());
-  if (rc == VGT_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(msg);
-  if (rc != VGT_HIP_OK) throw std::runtime_error(msg);
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
   sdf.locked = true;  // min / max were computed on the device: Lock() has nothing left to scan
   return sdf;
 }
@@ -386,9 +382,7 @@ std::vector<SignedDistanceField> ExtractSignedDistanceFields(
       ctx, inputs.data(), static_cast<int64_t>(maps.size()), first.NumXVoxels(), first.NumYVoxels(),
       first.NumZVoxels(), first.Resolution(), parameters.unknown_is_filled ? 1 : 0,
       parameters.add_virtual_border ? 1 : 0, outputs.data(), minima.data(), maxima.data());
-  const std::string msg = (rc == VGT_HIP_OK) ? std::string() : std::string(vgt_hip_last_error());
-  if (rc == VGT_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(msg);
-  if (rc != VGT_HIP_OK) throw std::runtime_error(msg);
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
   for (size_t i = 0; i < maps.size(); i++)
   {
     fields[i].minimum = minima[i];
@@ -400,12 +394,6 @@ std::vector<SignedDistanceField> ExtractSignedDistanceFields(
 
 namespace
 {
-[[noreturn]] void ThrowForCode(int rc, const std::string& msg)
-{
-  if (rc == VGT_HIP_ERR_INVALID_ARGUMENT) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
-
 // rotation block of the field's origin transform, row-major (what the reference multiplies gradients with)
 std::array<double, 9> RotationOf(const Isometry3& t)
 {
