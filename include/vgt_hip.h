@@ -375,6 +375,57 @@ int vgt_hip_sdf_fine_gradient(vgt_hip_ctx* ctx, const float* sdf_host, int64_t n
                               int64_t num_queries, double nominal_window_size, double* gradient_host,
                               uint8_t* has_value_host);
 
+/* SignedDistanceField::ProjectLocationOutOfCollisionToMinimumDistance (I/signed_distance_field.hpp:1111-1203;
+ * ProjectLocationOutOfCollision is minimum_distance = 0) for N points at once, one lane per point, the whole loop in
+ * one kernel.  Frames as above: queries and results are in the frame `grid_from_world` maps from (16 doubles
+ * column-major, NULL = the grid frame); `rotation` (9 doubles row-major = the rotation of OriginTransform(), NULL =
+ * none) turns the grid-aligned gradient into that frame, and the step is taken there.  Per point:
+ *   1. not in the grid (the has_value test of vgt_hip_sdf_estimate_distance; NaN and infinite coordinates too): the
+ *      point is returned unchanged, with a value.
+ *   2. margin = minimum_distance + resolution * stepsize_multiplier * 1e-3, max_step = resolution *
+ *      stepsize_multiplier, d = the estimate of vgt_hip_sdf_estimate_distance.
+ *   3. while d <= minimum_distance: g = the coarse gradient (edge gradients on, rotated) of the cell the point is in;
+ *      no value, or norm <= resolution * 0.25: no result; else point += (g / norm) * min(max_step, margin - d) and
+ *      d is estimated again.  (A NaN estimate ends the loop like the reference's comparison does.)
+ * The operation order of the step, which the reference takes from Eigen's norm() / normalized(), is, in double and
+ * without contraction:
+ *   norm = sqrt((gx*gx + gy*gy) + gz*gz);   n_a = g_a / norm;   loc_a = loc_a + n_a * step
+ * so results agree with the reference to rounding and are bit-identical to a restatement in this order.
+ * Outputs per point (has_value, status and iterations may each be NULL):
+ *   status               meaning                                                        position      has_value
+ *   0 OK                 clear of minimum_distance, possibly after 0 steps              projected     1
+ *   1 OUTSIDE            the start is not in the grid                                   the input     1
+ *   2 FLAT_GRADIENT      norm <= resolution * 0.25, or the gradient has no value        NaN x3        0
+ *   3 LEFT_GRID          a step left the grid                                           NaN x3        0
+ *   4 ITERATION_LIMIT    still d <= minimum_distance after max_iterations steps         NaN x3        0
+ *   iterations[i] = the steps taken (int32).
+ * Two divergences from the reference, both where it leaves the outcome open:
+ *   - The reference's loop has no iteration limit and does not end where the gradients of neighbouring cells point at
+ *     each other while the estimate stays <= minimum_distance (a free corridor narrower than twice the clearance).
+ *     Here the loop ends after max_iterations steps with status 4; max_iterations == 0 selects
+ *     ceil(2 * (nx + ny + nz) / stepsize_multiplier), twice the full-size steps of a straight path across the grid:
+ *     a safety limit, not a tuning number.
+ *   - A step can carry the point off the grid (edge gradients are on); the reference then takes .Value() of an empty
+ *     estimate, which throws.  Here that point gets status 3 and the call succeeds.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: stepsize_multiplier not positive and finite, minimum_distance
+ * NaN, max_iterations < 0, resolution not positive, a grid of 2^31 cells or more, a NULL required pointer. */
+#define VGT_HIP_PROJECT_OK 0
+#define VGT_HIP_PROJECT_OUTSIDE 1
+#define VGT_HIP_PROJECT_FLAT_GRADIENT 2
+#define VGT_HIP_PROJECT_LEFT_GRID 3
+#define VGT_HIP_PROJECT_ITERATION_LIMIT 4
+int vgt_hip_sdf_project_out_of_collision(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz,
+                                         double resolution, const double* grid_from_world, const double* rotation,
+                                         const double* query_xyz_host, int64_t num_queries, double minimum_distance,
+                                         double stepsize_multiplier, int32_t max_iterations, double* position_host,
+                                         uint8_t* has_value_host, uint8_t* status_host, int32_t* iterations_host);
+/* Same on device buffers (e.g. straight after vgt_hip_sdf_dev); enqueued on the context's stream, not blocking. */
+int vgt_hip_sdf_project_out_of_collision_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                                             double resolution, const double* grid_from_world, const double* rotation,
+                                             const double* query_xyz_dev, int64_t num_queries, double minimum_distance,
+                                             double stepsize_multiplier, int32_t max_iterations, double* position_dev,
+                                             uint8_t* has_value_dev, uint8_t* status_dev, int32_t* iterations_dev);
+
 /* SignedDistanceField::ComputeLocalExtremaMap (I/signed_distance_field.hpp:1205-1231 over :385-541; consumed by
  * TaggedObjectOccupancyComponentMap::UpdateSpatialSegments, S/tagged_object_occupancy_component_map.cpp:775-868):
  * for every voxel the grid-frame location (3 doubles) of the cell its gradient chain ends at -- the chain follows

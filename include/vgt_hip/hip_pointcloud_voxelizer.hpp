@@ -119,6 +119,22 @@ struct Gradients
 // frame the field's origin transform maps to), signed_distance_field.hpp:808-833.
 DistanceEstimates EstimateLocationDistances(const SignedDistanceField& sdf, const std::vector<double>& locations_xyz,
                                             int hip_device = 0);
+// SignedDistanceField::ProjectLocationOutOfCollisionToMinimumDistance (:1111-1203) for every point of `locations_xyz`,
+// with the field's inverse origin transform and rotation.  A batch reports per-point outcomes instead of throwing:
+// status[i] is one of the VGT_HIP_PROJECT_* values of vgt_hip.h (0 clear of minimum_distance, 1 the start is outside
+// the grid and returned unchanged, 2 flat gradient, 3 a step left the grid -- where the reference throws --, 4 still in
+// collision after max_iterations steps), has_value[i] == 0 and a NaN position for 2, 3 and 4.  max_iterations == 0
+// selects ceil(2 * (nx + ny + nz) / stepsize_multiplier); the reference's loop has no limit.
+struct ProjectedPositions
+{
+  std::vector<double> position;     // 3 per point, in the frame of `locations_xyz`
+  std::vector<uint8_t> has_value;
+  std::vector<uint8_t> status;
+  std::vector<int32_t> iterations;  // steps taken
+};
+ProjectedPositions ProjectLocationsOutOfCollision(const SignedDistanceField& sdf, const std::vector<double>& locations_xyz,
+                                                  double minimum_distance = 0.0, double stepsize_multiplier = 0.1,
+                                                  int32_t max_iterations = 0, int hip_device = 0);
 // SignedDistanceField::GetLocationFineGradient (:1050-1091); throws std::runtime_error("Window size for fine
 // gradient is too large for SDF") exactly when the reference does for one of the points.
 Gradients GetLocationFineGradients(const SignedDistanceField& sdf, const std::vector<double>& locations_xyz,

@@ -71,6 +71,10 @@ SIGNATURES = {
     "vgt_hip_sdf_estimate_distance": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _i64, _p, _p]),
     "vgt_hip_sdf_estimate_distance_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _i64, _p, _p]),
     "vgt_hip_sdf_fine_gradient": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _i64, _f64, _p, _p]),
+    "vgt_hip_sdf_project_out_of_collision": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _f64, _f64, _i32,
+                                                    _p, _p, _p, _p]),
+    "vgt_hip_sdf_project_out_of_collision_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _f64, _f64,
+                                                        _i32, _p, _p, _p, _p]),
     "vgt_hip_sdf_local_extrema_map": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_sdf_local_extrema_map_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_connected_components": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
@@ -136,6 +140,13 @@ TESTING_SIGNATURES = {
 # closest-point rules of the mesh rasterizer (VGT_HIP_MESH_RULE_*)
 MESH_RULE_REFERENCE = 0
 MESH_RULE_NEAREST = 1
+
+# statuses of sdf_project_out_of_collision (VGT_HIP_PROJECT_*)
+PROJECT_OK = 0
+PROJECT_OUTSIDE = 1
+PROJECT_FLAT_GRADIENT = 2
+PROJECT_LEFT_GRID = 3
+PROJECT_ITERATION_LIMIT = 4
 
 # vgt_hip_component_topology_t
 COMPONENT_TOPOLOGY = np.dtype([(name, np.int32) for name in (
@@ -324,6 +335,36 @@ class Context:
         check(self._lib.vgt_hip_sdf_fine_gradient(self.handle, _ptr(field), *field.shape, float(resolution), _ptr(xf),
                                                   _ptr(q), len(q), float(window), _ptr(out), _ptr(has)))
         return out, has.astype(bool)
+
+    def sdf_project_out_of_collision(self, sdf, resolution, queries, minimum_distance=0.0, stepsize_multiplier=0.1,
+                                     max_iterations=0, grid_from_world=None, rotation=None):
+        """ProjectLocationOutOfCollisionToMinimumDistance for a batch of query points [N, 3] -> (position [N, 3] float64,
+        has_value [N] bool, status [N] uint8 (PROJECT_*), iterations [N] int32); max_iterations=0: the library's limit."""
+        field = np.ascontiguousarray(sdf, dtype=np.float32)
+        q = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, 3)
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        position = np.empty((len(q), 3), dtype=np.float64)
+        has = np.empty(len(q), dtype=np.uint8)
+        status = np.empty(len(q), dtype=np.uint8)
+        iterations = np.empty(len(q), dtype=np.int32)
+        check(self._lib.vgt_hip_sdf_project_out_of_collision(
+            self.handle, _ptr(field), *field.shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(q), len(q),
+            float(minimum_distance), float(stepsize_multiplier), int(max_iterations), _ptr(position), _ptr(has),
+            _ptr(status), _ptr(iterations)))
+        return position, has.astype(bool), status, iterations
+
+    def sdf_project_out_of_collision_dev(self, sdf_ptr, shape, resolution, queries_ptr, num_queries, position_ptr,
+                                         has_value_ptr=None, status_ptr=None, iterations_ptr=None, minimum_distance=0.0,
+                                         stepsize_multiplier=0.1, max_iterations=0, grid_from_world=None, rotation=None):
+        """vgt_hip_sdf_project_out_of_collision_dev: field, queries and outputs on the device (the transforms are host
+        arrays); enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        check(self._lib.vgt_hip_sdf_project_out_of_collision_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
+            _ptr(queries_ptr), int(num_queries), float(minimum_distance), float(stepsize_multiplier),
+            int(max_iterations), _ptr(position_ptr), _ptr(has_value_ptr), _ptr(status_ptr), _ptr(iterations_ptr)))
 
     def sdf_local_extrema_map(self, sdf, resolution, rotation=None):
         """ComputeLocalExtremaMap: [nx, ny, nz, 3] float64 (grid-frame extremum location per voxel, +inf = off the grid)."""

@@ -271,6 +271,57 @@ struct Rotation
   int enabled;
 };
 
+// The per-voxel rule, shared by the whole-field kernel and the projection loop (voxel i = x*sx + y*sy + z).  Returns
+// false, with NaN in all three components, where the reference's GradientQuery is empty.
+__device__ __forceinline__ bool CoarseGradientAt(const float* __restrict__ sdf, int nx, int ny, int nz, int64_t sx,
+                                                 int64_t sy, double resolution, int enable_edge_gradients,
+                                                 const Rotation& rot, int64_t i, int x, int y, int z, double& gx,
+                                                 double& gy, double& gz)
+{
+  gx = 0.0;
+  gy = 0.0;
+  gz = 0.0;
+  if (x > 0 && y > 0 && z > 0 && x < nx - 1 && y < ny - 1 && z < nz - 1)
+  {
+    const double inv_twice_resolution = 1.0 / (2.0 * resolution);
+    gx = static_cast<double>(sdf[i + sx] - sdf[i - sx]) * inv_twice_resolution;
+    gy = static_cast<double>(sdf[i + sy] - sdf[i - sy]) * inv_twice_resolution;
+    gz = static_cast<double>(sdf[i + 1] - sdf[i - 1]) * inv_twice_resolution;
+  }
+  else if (enable_edge_gradients)
+  {
+    const int lx = max(0, x - 1), hx = min(nx - 1, x + 1);
+    const int ly = max(0, y - 1), hy = min(ny - 1, y + 1);
+    const int lz = max(0, z - 1), hz = min(nz - 1, z + 1);
+    const double x_increment = static_cast<double>(hx - lx) * resolution;
+    const double y_increment = static_cast<double>(hy - ly) * resolution;
+    const double z_increment = static_cast<double>(hz - lz) * resolution;
+    if (x_increment > 0.0)
+      gx = (static_cast<double>(sdf[i + (hx - x) * sx]) - static_cast<double>(sdf[i - (x - lx) * sx])) *
+           (1.0 / x_increment);
+    if (y_increment > 0.0)
+      gy = (static_cast<double>(sdf[i + (hy - y) * sy]) - static_cast<double>(sdf[i - (y - ly) * sy])) *
+           (1.0 / y_increment);
+    if (z_increment > 0.0)
+      gz = (static_cast<double>(sdf[i + (hz - z)]) - static_cast<double>(sdf[i - (z - lz)])) * (1.0 / z_increment);
+  }
+  else
+  {
+    gx = gy = gz = __longlong_as_double(0x7ff8000000000000ll);
+    return false;
+  }
+  if (rot.enabled)
+  {
+    const double wx = rot.m[0] * gx + rot.m[1] * gy + rot.m[2] * gz;
+    const double wy = rot.m[3] * gx + rot.m[4] * gy + rot.m[5] * gz;
+    const double wz = rot.m[6] * gx + rot.m[7] * gy + rot.m[8] * gz;
+    gx = wx;
+    gy = wy;
+    gz = wz;
+  }
+  return true;
+}
+
 __global__ __launch_bounds__(256) void CoarseGradientKernel(const float* __restrict__ sdf, int nx, int ny, int nz,
                                                            double resolution, int enable_edge_gradients,
                                                            const Rotation rot, double* __restrict__ gradient,
@@ -284,46 +335,9 @@ __global__ __launch_bounds__(256) void CoarseGradientKernel(const float* __restr
     const int z = static_cast<int>(i % nz);
     const int y = static_cast<int>((i / nz) % ny);
     const int x = static_cast<int>(i / sx);
-    double gx = 0.0, gy = 0.0, gz = 0.0;
-    bool ok = true;
-    if (x > 0 && y > 0 && z > 0 && x < nx - 1 && y < ny - 1 && z < nz - 1)
-    {
-      const double inv_twice_resolution = 1.0 / (2.0 * resolution);
-      gx = static_cast<double>(sdf[i + sx] - sdf[i - sx]) * inv_twice_resolution;
-      gy = static_cast<double>(sdf[i + sy] - sdf[i - sy]) * inv_twice_resolution;
-      gz = static_cast<double>(sdf[i + 1] - sdf[i - 1]) * inv_twice_resolution;
-    }
-    else if (enable_edge_gradients)
-    {
-      const int lx = max(0, x - 1), hx = min(nx - 1, x + 1);
-      const int ly = max(0, y - 1), hy = min(ny - 1, y + 1);
-      const int lz = max(0, z - 1), hz = min(nz - 1, z + 1);
-      const double x_increment = static_cast<double>(hx - lx) * resolution;
-      const double y_increment = static_cast<double>(hy - ly) * resolution;
-      const double z_increment = static_cast<double>(hz - lz) * resolution;
-      if (x_increment > 0.0)
-        gx = (static_cast<double>(sdf[i + (hx - x) * sx]) - static_cast<double>(sdf[i - (x - lx) * sx])) *
-             (1.0 / x_increment);
-      if (y_increment > 0.0)
-        gy = (static_cast<double>(sdf[i + (hy - y) * sy]) - static_cast<double>(sdf[i - (y - ly) * sy])) *
-             (1.0 / y_increment);
-      if (z_increment > 0.0)
-        gz = (static_cast<double>(sdf[i + (hz - z)]) - static_cast<double>(sdf[i - (z - lz)])) * (1.0 / z_increment);
-    }
-    else
-    {
-      ok = false;
-      gx = gy = gz = __longlong_as_double(0x7ff8000000000000ll);
-    }
-    if (ok && rot.enabled)
-    {
-      const double wx = rot.m[0] * gx + rot.m[1] * gy + rot.m[2] * gz;
-      const double wy = rot.m[3] * gx + rot.m[4] * gy + rot.m[5] * gz;
-      const double wz = rot.m[6] * gx + rot.m[7] * gy + rot.m[8] * gz;
-      gx = wx;
-      gy = wy;
-      gz = wz;
-    }
+    double gx, gy, gz;
+    const bool ok = CoarseGradientAt(sdf, nx, ny, nz, sx, sy, resolution, enable_edge_gradients, rot, i, x, y, z, gx,
+                                     gy, gz);
     gradient[3 * i + 0] = gx;
     gradient[3 * i + 1] = gy;
     gradient[3 * i + 2] = gz;
@@ -399,42 +413,81 @@ __device__ __forceinline__ double CorrectedCenterDistance(const float* __restric
 
 __device__ __forceinline__ double Lerp(double a, double b, double t) { return a * (1.0 - t) + b * t; }
 
+// EstimateDistance in its three steps, so that a caller that evaluates it again and again near one place (the
+// projection loop) can keep the loaded corners while their indices stay the same.
+struct CellOfLocation
+{
+  double g[3];                 // the location in the grid frame
+  int ix, iy, iz;              // the cell it lies in
+  int lx, ux, ly, uy, lz, uz;  // GetAxisInterpolationIndices per axis
+};
+
+struct CornerDistances
+{
+  double mmm, mmp, mpm, mpp, pmm, pmp, ppm, ppp;  // GetCorrectedCenterDistance at (x, y, z) in {lower, upper}^3
+};
+
+// false: the location is not in the grid (also for NaN and infinite coordinates)
+__device__ __forceinline__ bool LocateCell(int nx, int ny, int nz, double resolution, const GridFromWorld& xf, double x,
+                                           double y, double z, CellOfLocation& c)
+{
+  c.g[0] = x;
+  c.g[1] = y;
+  c.g[2] = z;
+  if (xf.enabled)
+  {
+    const double* M = xf.m;
+    c.g[0] = M[0] * x + M[4] * y + M[8] * z + M[12];
+    c.g[1] = M[1] * x + M[5] * y + M[9] * z + M[13];
+    c.g[2] = M[2] * x + M[6] * y + M[10] * z + M[14];
+  }
+  const double inv = 1.0 / resolution;
+  const double fx = floor(c.g[0] * inv), fy = floor(c.g[1] * inv), fz = floor(c.g[2] * inv);
+  if (!(fx >= 0.0 && fx < nx && fy >= 0.0 && fy < ny && fz >= 0.0 && fz < nz)) return false;  // also rejects NaN
+  c.ix = static_cast<int>(fx);
+  c.iy = static_cast<int>(fy);
+  c.iz = static_cast<int>(fz);
+  const double cx = (static_cast<double>(c.ix) + 0.5) * resolution;
+  const double cy = (static_cast<double>(c.iy) + 0.5) * resolution;
+  const double cz = (static_cast<double>(c.iz) + 0.5) * resolution;
+  AxisInterpolationIndices(c.ix, nx, c.g[0] - cx, c.lx, c.ux);
+  AxisInterpolationIndices(c.iy, ny, c.g[1] - cy, c.ly, c.uy);
+  AxisInterpolationIndices(c.iz, nz, c.g[2] - cz, c.lz, c.uz);
+  return true;
+}
+
+__device__ __forceinline__ CornerDistances LoadCorners(const float* __restrict__ sdf, int ny, int nz, double resolution,
+                                                       const CellOfLocation& c)
+{
+  const int64_t sx = static_cast<int64_t>(ny) * nz, sy = nz;
+  auto at = [&](int a, int b, int d) { return CorrectedCenterDistance(sdf, a * sx + b * sy + d, resolution); };
+  CornerDistances k;
+  k.mmm = at(c.lx, c.ly, c.lz), k.mmp = at(c.lx, c.ly, c.uz), k.mpm = at(c.lx, c.uy, c.lz), k.mpp = at(c.lx, c.uy, c.uz);
+  k.pmm = at(c.ux, c.ly, c.lz), k.pmp = at(c.ux, c.ly, c.uz), k.ppm = at(c.ux, c.uy, c.lz), k.ppp = at(c.ux, c.uy, c.uz);
+  return k;
+}
+
+__device__ __forceinline__ double InterpolateCorners(const CellOfLocation& c, const CornerDistances& k, double resolution)
+{
+  const double low_x = (static_cast<double>(c.lx) + 0.5) * resolution;
+  const double low_y = (static_cast<double>(c.ly) + 0.5) * resolution;
+  const double low_z = (static_cast<double>(c.lz) + 0.5) * resolution;
+  const double tx = (c.g[0] - low_x) / ((low_x + resolution) - low_x);
+  const double ty = (c.g[1] - low_y) / ((low_y + resolution) - low_y);
+  const double tz = (c.g[2] - low_z) / ((low_z + resolution) - low_z);
+  const double mm = Lerp(k.mmm, k.pmm, tx), mp = Lerp(k.mmp, k.pmp, tx), pm = Lerp(k.mpm, k.ppm, tx),
+               pp = Lerp(k.mpp, k.ppp, tx);
+  const double lo = Lerp(mm, pm, ty), hi = Lerp(mp, pp, ty);
+  return Lerp(lo, hi, tz);
+}
+
 __device__ EstimateResult EstimateDistance(const float* __restrict__ sdf, int nx, int ny, int nz, double resolution,
                                            const GridFromWorld& xf, double x, double y, double z)
 {
   EstimateResult r{0.0, false};
-  double g[3] = {x, y, z};
-  if (xf.enabled)
-  {
-    const double* M = xf.m;
-    g[0] = M[0] * x + M[4] * y + M[8] * z + M[12];
-    g[1] = M[1] * x + M[5] * y + M[9] * z + M[13];
-    g[2] = M[2] * x + M[6] * y + M[10] * z + M[14];
-  }
-  const double inv = 1.0 / resolution;
-  const double fx = floor(g[0] * inv), fy = floor(g[1] * inv), fz = floor(g[2] * inv);
-  if (!(fx >= 0.0 && fx < nx && fy >= 0.0 && fy < ny && fz >= 0.0 && fz < nz)) return r;  // also rejects NaN
-  const int ix = static_cast<int>(fx), iy = static_cast<int>(fy), iz = static_cast<int>(fz);
-  const double cx = (static_cast<double>(ix) + 0.5) * resolution;
-  const double cy = (static_cast<double>(iy) + 0.5) * resolution;
-  const double cz = (static_cast<double>(iz) + 0.5) * resolution;
-  int lx, ux, ly, uy, lz, uz;
-  AxisInterpolationIndices(ix, nx, g[0] - cx, lx, ux);
-  AxisInterpolationIndices(iy, ny, g[1] - cy, ly, uy);
-  AxisInterpolationIndices(iz, nz, g[2] - cz, lz, uz);
-  const int64_t sx = static_cast<int64_t>(ny) * nz, sy = nz;
-  auto at = [&](int a, int b, int c) { return CorrectedCenterDistance(sdf, a * sx + b * sy + c, resolution); };
-  const double mmm = at(lx, ly, lz), mmp = at(lx, ly, uz), mpm = at(lx, uy, lz), mpp = at(lx, uy, uz);
-  const double pmm = at(ux, ly, lz), pmp = at(ux, ly, uz), ppm = at(ux, uy, lz), ppp = at(ux, uy, uz);
-  const double low_x = (static_cast<double>(lx) + 0.5) * resolution;
-  const double low_y = (static_cast<double>(ly) + 0.5) * resolution;
-  const double low_z = (static_cast<double>(lz) + 0.5) * resolution;
-  const double tx = (g[0] - low_x) / ((low_x + resolution) - low_x);
-  const double ty = (g[1] - low_y) / ((low_y + resolution) - low_y);
-  const double tz = (g[2] - low_z) / ((low_z + resolution) - low_z);
-  const double mm = Lerp(mmm, pmm, tx), mp = Lerp(mmp, pmp, tx), pm = Lerp(mpm, ppm, tx), pp = Lerp(mpp, ppp, tx);
-  const double lo = Lerp(mm, pm, ty), hi = Lerp(mp, pp, ty);
-  r.value = Lerp(lo, hi, tz);
+  CellOfLocation c;
+  if (!LocateCell(nx, ny, nz, resolution, xf, x, y, z, c)) return r;
+  r.value = InterpolateCorners(c, LoadCorners(sdf, ny, nz, resolution, c), resolution);
   r.has_value = true;
   return r;
 }
@@ -518,6 +571,14 @@ GridFromWorld MakeGridFromWorld(const double* grid_from_world_host)
   for (int k = 0; k < 16; k++) xf.m[k] = grid_from_world_host ? grid_from_world_host[k] : 0.0;
   return xf;
 }
+
+Rotation MakeRotation(const double* rotation_host)
+{
+  Rotation rot;
+  rot.enabled = rotation_host ? 1 : 0;
+  for (int k = 0; k < 9; k++) rot.m[k] = rotation_host ? rotation_host[k] : 0.0;
+  return rot;
+}
 }  // namespace
 
 hipError_t LaunchEstimateDistance(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
@@ -548,12 +609,130 @@ hipError_t LaunchCoarseGradient(const float* sdf_dev, int64_t nx, int64_t ny, in
                                 int enable_edge_gradients, const double* rotation_host, double* gradient_dev,
                                 uint8_t* has_value_dev, hipStream_t stream)
 {
-  Rotation rot;
-  rot.enabled = rotation_host ? 1 : 0;
-  for (int k = 0; k < 9; k++) rot.m[k] = rotation_host ? rotation_host[k] : 0.0;
+  const Rotation rot = MakeRotation(rotation_host);
   hipLaunchKernelGGL(CoarseGradientKernel, dim3(CellGrid(nx * ny * nz)), dim3(256), 0, stream, sdf_dev,
                      static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz), resolution,
                      enable_edge_gradients, rot, gradient_dev, has_value_dev);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// SDF consumer, batched queries: SignedDistanceField::ProjectLocationOutOfCollisionToMinimumDistance
+// (signed_distance_field.hpp:1111-1203).  One lane per query walks its point up the coarse gradient (edge gradients
+// on, rotated into the query frame) of the cell it is in, by at most resolution * stepsize_multiplier per step, until
+// the trilinear estimate exceeds minimum_distance.  All in double, no contraction; the order of the one step whose
+// order the reference takes from Eigen is
+//   norm = sqrt((gx*gx + gy*gy) + gz*gz);  n_a = g_a / norm;  loc_a = loc_a + n_a * step.
+// Two things the reference leaves open are closed here: the loop ends after max_iterations steps (the reference's
+// does not end where neighbouring cells' gradients point at each other), and a step that leaves the grid is a status
+// (the reference throws).  Statuses: include/vgt_hip.h.
+//
+// The loop is a chain of dependent gathers, and with the default multiplier a point spends about ten steps in one
+// cell: the cell's gradient (keyed by the cell) and the eight corrected corner distances (keyed by the lower / upper
+// indices) stay in registers and are loaded again only when their key changes.  The values are the ones a reload
+// would give, so the cache changes no bit of the output.
+// ---------------------------------------------------------------------------------------------
+namespace
+{
+constexpr uint8_t kProjectOk = 0, kProjectOutside = 1, kProjectFlatGradient = 2, kProjectLeftGrid = 3,
+                  kProjectIterationLimit = 4;
+
+__global__ __launch_bounds__(256) void ProjectOutOfCollisionKernel(
+    const float* __restrict__ sdf, int nx, int ny, int nz, double resolution, const GridFromWorld xf, const Rotation rot,
+    const double* __restrict__ queries, int64_t num_queries, double minimum_distance, double stepsize_multiplier,
+    int max_iterations, double* __restrict__ position, uint8_t* __restrict__ has_value, uint8_t* __restrict__ status,
+    int32_t* __restrict__ iterations)
+{
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const int64_t sx = static_cast<int64_t>(ny) * nz, sy = nz;
+  const double max_step = resolution * stepsize_multiplier;
+  const double margin = minimum_distance + resolution * stepsize_multiplier * 1e-3;
+  const double flat = resolution * 0.25;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < num_queries;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x)
+  {
+    double x = queries[3 * i], y = queries[3 * i + 1], z = queries[3 * i + 2];
+    uint8_t result = kProjectOutside;
+    int steps = 0;
+    CellOfLocation c;
+    if (LocateCell(nx, ny, nz, resolution, xf, x, y, z, c))
+    {
+      CornerDistances corners = LoadCorners(sdf, ny, nz, resolution, c);
+      int klx = c.lx, kux = c.ux, kly = c.ly, kuy = c.uy, klz = c.lz, kuz = c.uz;  // key of `corners`
+      double d = InterpolateCorners(c, corners, resolution);
+      int64_t gradient_cell = -1;  // key of (gx, gy, gz, gradient_ok)
+      double gx = 0.0, gy = 0.0, gz = 0.0;
+      bool gradient_ok = false;
+      result = kProjectOk;
+      while (d <= minimum_distance)
+      {
+        if (steps >= max_iterations)
+        {
+          result = kProjectIterationLimit;
+          break;
+        }
+        const int64_t cell = c.ix * sx + c.iy * sy + c.iz;
+        if (cell != gradient_cell)
+        {
+          gradient_ok = CoarseGradientAt(sdf, nx, ny, nz, sx, sy, resolution, 1, rot, cell, c.ix, c.iy, c.iz, gx, gy, gz);
+          gradient_cell = cell;
+        }
+        const double norm = sqrt((gx * gx + gy * gy) + gz * gz);
+        if (!gradient_ok || norm <= flat)
+        {
+          result = kProjectFlatGradient;
+          break;
+        }
+        const double to_margin = margin - d;
+        const double step = (to_margin < max_step) ? to_margin : max_step;  // std::min(max_step, margin - d)
+        x = x + (gx / norm) * step;
+        y = y + (gy / norm) * step;
+        z = z + (gz / norm) * step;
+        steps++;
+        if (!LocateCell(nx, ny, nz, resolution, xf, x, y, z, c))
+        {
+          result = kProjectLeftGrid;
+          break;
+        }
+        if (c.lx != klx || c.ux != kux || c.ly != kly || c.uy != kuy || c.lz != klz || c.uz != kuz)
+        {
+          corners = LoadCorners(sdf, ny, nz, resolution, c);
+          klx = c.lx, kux = c.ux, kly = c.ly, kuy = c.uy, klz = c.lz, kuz = c.uz;
+        }
+        d = InterpolateCorners(c, corners, resolution);
+      }
+    }
+    const bool valued = result == kProjectOk || result == kProjectOutside;
+    position[3 * i] = valued ? x : nan;
+    position[3 * i + 1] = valued ? y : nan;
+    position[3 * i + 2] = valued ? z : nan;
+    if (has_value) has_value[i] = valued ? 1 : 0;
+    if (status) status[i] = result;
+    if (iterations) iterations[i] = steps;
+  }
+}
+}  // namespace
+
+int32_t DefaultProjectionIterations(int64_t nx, int64_t ny, int64_t nz, double stepsize_multiplier)
+{
+  const double limit = ceil(2.0 * static_cast<double>(nx + ny + nz) / stepsize_multiplier);
+  return limit < 2147483647.0 ? static_cast<int32_t>(limit) : 2147483647;
+}
+
+hipError_t LaunchProjectOutOfCollision(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                       const double* grid_from_world_host, const double* rotation_host,
+                                       const double* queries_dev, int64_t num_queries, double minimum_distance,
+                                       double stepsize_multiplier, int32_t max_iterations, double* position_dev,
+                                       uint8_t* has_value_dev, uint8_t* status_dev, int32_t* iterations_dev,
+                                       hipStream_t stream)
+{
+  if (num_queries <= 0) return hipSuccess;
+  if (max_iterations == 0) max_iterations = DefaultProjectionIterations(nx, ny, nz, stepsize_multiplier);
+  hipLaunchKernelGGL(ProjectOutOfCollisionKernel, dim3(CellGrid(num_queries)), dim3(256), 0, stream, sdf_dev,
+                     static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz), resolution,
+                     MakeGridFromWorld(grid_from_world_host), MakeRotation(rotation_host), queries_dev, num_queries,
+                     minimum_distance, stepsize_multiplier, max_iterations, position_dev, has_value_dev, status_dev,
+                     iterations_dev);
   return hipGetLastError();
 }
 
@@ -770,9 +949,7 @@ hipError_t LaunchLocalExtremaMap(const float* sdf_dev, int64_t nx, int64_t ny, i
   int32_t* cycle_id = jump + total;
   int32_t* basin_min = cycle_id + total;
   int32_t* entry = basin_min + total;
-  Rotation rot;
-  rot.enabled = rotation_host ? 1 : 0;
-  for (int k = 0; k < 9; k++) rot.m[k] = rotation_host ? rotation_host[k] : 0.0;
+  const Rotation rot = MakeRotation(rotation_host);
   const dim3 grid(CellGrid(total)), block(256);
   hipLaunchKernelGGL(ExtremaSuccessorKernel, grid, block, 0, stream, sdf_dev, static_cast<int>(nx),
                      static_cast<int>(ny), static_cast<int>(nz), resolution, rot, next);

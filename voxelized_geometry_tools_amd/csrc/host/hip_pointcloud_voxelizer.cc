@@ -423,6 +423,28 @@ DistanceEstimates EstimateLocationDistances(const SignedDistanceField& sdf, cons
   return out;
 }
 
+ProjectedPositions ProjectLocationsOutOfCollision(const SignedDistanceField& sdf, const std::vector<double>& locations_xyz,
+                                                  double minimum_distance, double stepsize_multiplier,
+                                                  int32_t max_iterations, int hip_device)
+{
+  if (locations_xyz.size() % 3 != 0) throw std::invalid_argument("locations_xyz must hold 3 doubles per point");
+  const int64_t n = static_cast<int64_t>(locations_xyz.size() / 3);
+  ProjectedPositions out;
+  out.position.resize(static_cast<size_t>(3 * n));
+  out.has_value.resize(static_cast<size_t>(n));
+  out.status.resize(static_cast<size_t>(n));
+  out.iterations.resize(static_cast<size_t>(n));
+  const DenseGrid& g = sdf.grid;
+  const std::array<double, 9> rotation = RotationOf(g.OriginTransform());
+  const int rc = vgt_hip_sdf_project_out_of_collision(
+      SharedSdfContext(hip_device), g.GetImmutableRawData().data(), g.NumXVoxels(), g.NumYVoxels(), g.NumZVoxels(),
+      g.Resolution(), g.InverseOriginTransform().m.data(), rotation.data(), locations_xyz.data(), n, minimum_distance,
+      stepsize_multiplier, max_iterations, out.position.data(), out.has_value.data(), out.status.data(),
+      out.iterations.data());
+  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
+  return out;
+}
+
 Gradients GetLocationFineGradients(const SignedDistanceField& sdf, const std::vector<double>& locations_xyz,
                                    double nominal_window_size, int hip_device)
 {

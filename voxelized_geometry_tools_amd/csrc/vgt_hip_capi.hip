@@ -436,6 +436,21 @@ int CheckSdfShape(int64_t nx, int64_t ny, int64_t nz, double resolution)
   return VGT_HIP_OK;
 }
 
+// The checks both projection entry points make before any device work.
+int CheckProjectionArguments(int64_t nx, int64_t ny, int64_t nz, double resolution, double minimum_distance,
+                             double stepsize_multiplier, int32_t max_iterations)
+{
+  const int rc = CheckSdfShape(nx, ny, nz, resolution);
+  if (rc != VGT_HIP_OK) return rc;
+  if (nx * ny * nz >= 0x7fffffffLL)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the projection out of collision supports grids below 2^31 cells");
+  if (std::isnan(minimum_distance)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "minimum_distance must not be NaN");
+  if (!(stepsize_multiplier > 0.0) || !std::isfinite(stepsize_multiplier))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "stepsize_multiplier must be positive and finite");
+  if (max_iterations < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "max_iterations must not be negative");
+  return VGT_HIP_OK;
+}
+
 // Events of the current timing slot (nullptr when no session is active or it is full).
 hipEvent_t* TimingSlot(vgt_hip_ctx* ctx)
 {
@@ -2452,6 +2467,67 @@ int vgt_hip_sdf_fine_gradient(vgt_hip_ctx* ctx, const float* sdf_host, int64_t n
                                                          num_queries, nominal_window_size, out_dev, has_dev, flag_dev,
                                                          s);
                         });
+}
+
+int vgt_hip_sdf_project_out_of_collision_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                                             double resolution, const double* grid_from_world, const double* rotation,
+                                             const double* query_xyz_dev, int64_t num_queries, double minimum_distance,
+                                             double stepsize_multiplier, int32_t max_iterations, double* position_dev,
+                                             uint8_t* has_value_dev, uint8_t* status_dev, int32_t* iterations_dev)
+{
+  if (!ctx || !sdf_dev || !position_dev || num_queries < 0 || (num_queries > 0 && !query_xyz_dev))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckProjectionArguments(nx, ny, nz, resolution, minimum_distance, stepsize_multiplier, max_iterations);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(vgt::LaunchProjectOutOfCollision(sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, query_xyz_dev,
+                                               num_queries, minimum_distance, stepsize_multiplier, max_iterations,
+                                               position_dev, has_value_dev, status_dev, iterations_dev, ctx->stream),
+              "project out of collision");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_sdf_project_out_of_collision(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz,
+                                         double resolution, const double* grid_from_world, const double* rotation,
+                                         const double* query_xyz_host, int64_t num_queries, double minimum_distance,
+                                         double stepsize_multiplier, int32_t max_iterations, double* position_host,
+                                         uint8_t* has_value_host, uint8_t* status_host, int32_t* iterations_host)
+{
+  if (!ctx || !sdf_host || !position_host || num_queries < 0 || (num_queries > 0 && !query_xyz_host))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckProjectionArguments(nx, ny, nz, resolution, minimum_distance, stepsize_multiplier, max_iterations);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_queries == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "project out of collision";
+  const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_queries);
+  vgt::DeviceTemp sdf, queries, position, has, status, iterations;
+  VGT_TRY_HIP(sdf.Allocate(n * sizeof(float)), what);
+  VGT_TRY_HIP(queries.Allocate(q * 3 * sizeof(double)), what);
+  VGT_TRY_HIP(position.Allocate(q * 3 * sizeof(double)), what);
+  if (has_value_host) VGT_TRY_HIP(has.Allocate(q), what);
+  if (status_host) VGT_TRY_HIP(status.Allocate(q), what);
+  if (iterations_host) VGT_TRY_HIP(iterations.Allocate(q * sizeof(int32_t)), what);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipStream_t s = ctx->stream;
+  hipError_t err = hipMemcpyAsync(sdf.as<float>(), sdf_host, n * sizeof(float), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(queries.as<double>(), query_xyz_host, q * 3 * sizeof(double), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess)
+    err = vgt::LaunchProjectOutOfCollision(sdf.as<float>(), nx, ny, nz, resolution, grid_from_world, rotation,
+                                           queries.as<double>(), num_queries, minimum_distance, stepsize_multiplier,
+                                           max_iterations, position.as<double>(), has.as<uint8_t>(), status.as<uint8_t>(),
+                                           iterations.as<int32_t>(), s);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(position_host, position.as<double>(), q * 3 * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (err == hipSuccess && has_value_host)
+    err = hipMemcpyAsync(has_value_host, has.as<uint8_t>(), q, hipMemcpyDeviceToHost, s);
+  if (err == hipSuccess && status_host) err = hipMemcpyAsync(status_host, status.as<uint8_t>(), q, hipMemcpyDeviceToHost, s);
+  if (err == hipSuccess && iterations_host)
+    err = hipMemcpyAsync(iterations_host, iterations.as<int32_t>(), q * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
+  return VGT_HIP_OK;
 }
 
 int vgt_hip_sdf_local_extrema_map_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,

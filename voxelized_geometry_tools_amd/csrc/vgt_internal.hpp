@@ -222,6 +222,17 @@ hipError_t LaunchFineGradient(const float* sdf_dev, int64_t nx, int64_t ny, int6
                               double nominal_window_size, double* gradient_dev, uint8_t* has_value_dev,
                               uint32_t* window_too_large_dev, hipStream_t stream);
 
+// SignedDistanceField::ProjectLocationOutOfCollisionToMinimumDistance for a batch of points, one lane per point
+// (statuses and outputs: include/vgt_hip.h).  rotation_host: 9 doubles row-major or nullptr.  has_value_dev, status_dev
+// and iterations_dev may be nullptr.  max_iterations == 0 selects DefaultProjectionIterations.
+int32_t DefaultProjectionIterations(int64_t nx, int64_t ny, int64_t nz, double stepsize_multiplier);
+hipError_t LaunchProjectOutOfCollision(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                       const double* grid_from_world_host, const double* rotation_host,
+                                       const double* queries_dev, int64_t num_queries, double minimum_distance,
+                                       double stepsize_multiplier, int32_t max_iterations, double* position_dev,
+                                       uint8_t* has_value_dev, uint8_t* status_dev, int32_t* iterations_dev,
+                                       hipStream_t stream);
+
 // SignedDistanceField::ComputeLocalExtremaMap: 3 doubles per voxel (grid-frame location of the extremum the
 // voxel's gradient chain ends at, +inf when it leaves the grid).  scratch_dev: LocalExtremaScratchBytes bytes.
 size_t LocalExtremaScratchBytes(int64_t num_cells);
