@@ -575,6 +575,40 @@ int vgt_hip_rasterize_mesh_dev(vgt_hip_ctx* ctx, const double* vertices_xyz_dev,
 int vgt_hip_mesh_grid_for(const double* vertices_xyz_host, int64_t num_vertices, double resolution, int64_t* nx,
                           int64_t* ny, int64_t* nz, double* origin_xyz);
 
+/* ---- enclosed space: fill what a shell encloses (scipy.ndimage.binary_fill_holes under face connectivity), in place;
+ * csrc/component_kernels.hip.  An extension: the reference has no such operation, its rasterized meshes stay hollow
+ * shells and their signed distance fields are positive inside the body.
+ * `cells` as for vgt_hip_rasterize_mesh: records of cell_bytes = 4 (OccupancyCell) or 8 (OccupancyComponentCell) bytes,
+ * the float occupancy at offset 0, X-major / Z fastest.
+ *   filled(c)    occupancy > 0.5f || (unknown_is_filled && occupancy == 0.5f): the predicate of the SDF entry points.
+ *                passable = !filled, so a NaN cell is passable.
+ *   border cell  a cell whose index is 0 or n - 1 on some axis.
+ *   outside      every passable cell that a chain of face-adjacent passable cells joins to a passable border cell, the
+ *                border cells themselves included.
+ * Every passable cell that is not outside gets occupancy 1.0f.  NO OTHER BYTE IS WRITTEN: filled cells and outside cells
+ * keep their bit patterns (0.7f, -0.0f, NaN stay what they are), and so do the other four bytes of an 8-byte record.
+ * *num_filled receives the number of cells written.  The call is idempotent (a second call writes 0 cells), and the
+ * result depends on the input alone, never on the order in which the device's atomics land.  A grid with an extent of 1
+ * on some axis consists of border cells: nothing is filled.
+ * Which shells are sealed: a closed mesh rasterized under VGT_HIP_MESH_RULE_NEAREST separates inside from outside under
+ * face connectivity (every cell the surface passes through has its centre within resolution * sqrt(3) / 2 of it, and a
+ * face-connected path from inside to outside crosses the surface inside one of these cells).
+ * VGT_HIP_MESH_RULE_REFERENCE can miss cells along slanted edges; such a shell leaks and its interior is filled only
+ * where it happens to be sealed.  This call does not repair leaks.
+ * Device memory: the labelling scratch the context keeps (4 bytes per voxel + 256, shared with
+ * vgt_hip_connected_components*), NOTHING beyond it -- "outside" is a virtual root of the union-find, not a flag array --;
+ * the host form adds the device copy of the map.  Grids below 2^31 cells.
+ *   vgt_hip_fill_enclosed      host map; blocking; the host map is written only when the call succeeds.
+ *   vgt_hip_fill_enclosed_dev  device map.  num_filled == NULL: the work is left enqueued on the context's stream (it can
+ *                              stand between vgt_hip_rasterize_mesh_dev and vgt_hip_sdf_dev without a host round trip);
+ *                              otherwise the call waits for the count.
+ * Errors (VGT_HIP_ERR_INVALID_ARGUMENT, before any HIP call): a null context or map, cell_bytes other than 4 or 8, an
+ * extent <= 0, 2^31 cells or more. */
+int vgt_hip_fill_enclosed(vgt_hip_ctx* ctx, void* cells_host, int cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                          int unknown_is_filled, int64_t* num_filled);
+int vgt_hip_fill_enclosed_dev(vgt_hip_ctx* ctx, void* cells_dev, int cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                              int unknown_is_filled, int64_t* num_filled /* host, may be NULL */);
+
 /* ---- multi-GPU: the grid is cut into Z slabs, one device per slab (BASELINE.json config 5).
  * Lines along Y and X are local to a slab; only the first pass (nearest voxel of the other class
  * along Z) crosses slabs, and all it needs from the other slabs is, per (x, y) line, the nearest

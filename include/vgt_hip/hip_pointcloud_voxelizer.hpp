@@ -227,6 +227,15 @@ private:
 uint32_t UpdateConnectedComponents(OccupancyComponentMap& map, int hip_device = 0);
 uint32_t UpdateConnectedComponents(TaggedObjectOccupancyComponentMap& map, bool connect_across_objects,
                                    int hip_device = 0);
+// Enclosed space (an extension; include/vgt_hip.h, vgt_hip_fill_enclosed): every cell that is not filled -- occupancy
+// > 0.5, or == 0.5 when unknown_is_filled -- and that no chain of face-adjacent such cells joins to a face of the grid
+// gets occupancy 1.0f, in place; nothing else of the map is written.  Returns the number of cells filled.
+// The OccupancyComponentMap overload leaves the cells' `component` members as they are: they describe the map before
+// the fill and are invalid after a fill that returns more than 0 (this layer's map types keep no validity flag of
+// their own to clear: call UpdateConnectedComponents again, as after any other change of an occupancy).
+// std::invalid_argument for an uninitialised map or one of 2^31 cells and more.
+int64_t FillEnclosedSpace(OccupancyMap& map, bool unknown_is_filled = true, int hip_device = 0);
+int64_t FillEnclosedSpace(OccupancyComponentMap& map, bool unknown_is_filled = true, int hip_device = 0);
 // TaggedObjectOccupancyComponentMap::UpdateSpatialSegments (:775-868) as one device chain (SDF -> local extrema map,
 // rotated by the map's origin transform -> segments); writes the cells' `spatial_segment` members.  Runs on
 // sdf_parameters.hip_device.

@@ -91,6 +91,8 @@ SIGNATURES = {
     "vgt_hip_rasterize_mesh": (_int, [_p, _p, _i64, _p, _i64, _p, _int, _i64, _i64, _i64, _f64, _p, _p, _int, _int]),
     "vgt_hip_rasterize_mesh_dev": (_int, [_p, _p, _i64, _p, _i64, _p, _int, _i64, _i64, _i64, _f64, _p, _p, _int, _int]),
     "vgt_hip_mesh_grid_for": (_int, [_p, _i64, _f64, _p, _p, _p, _p]),
+    "vgt_hip_fill_enclosed": (_int, [_p, _p, _int, _i64, _i64, _i64, _int, _p]),
+    "vgt_hip_fill_enclosed_dev": (_int, [_p, _p, _int, _i64, _i64, _i64, _int, _p]),
     "vgt_hipx_sdf_multi": (_int, [_p, _int, _p, _i64, _i64, _i64, _f64, _int, _int, _p, _p, _p]),
     "vgt_hipx_release": (None, []),
     "vgt_hipx_last_timing": (_int, [_p]),
@@ -459,11 +461,35 @@ class Context:
                                                    int(cell_bytes), *[int(c) for c in shape], float(resolution),
                                                    _ptr(wfg), _ptr(gfw), int(bool(enforce_contains)), int(rule)))
 
+    def fill_enclosed(self, cells, unknown_is_filled=True):
+        """vgt_hip_fill_enclosed on a host map, in place: every passable cell that no chain of face-adjacent passable
+        cells joins to the grid's border gets occupancy 1.0 (scipy.ndimage.binary_fill_holes, face connectivity).
+        `cells` as for rasterize_mesh.  Returns the number of cells filled."""
+        if not isinstance(cells, np.ndarray) or cells.ndim != 3 or not cells.flags.c_contiguous or \
+                not cells.flags.writeable:
+            raise ValueError("cells must be a writeable C-contiguous (nx, ny, nz) array")
+        count = _i64(0)
+        check(self._lib.vgt_hip_fill_enclosed(self.handle, _ptr(cells), cells.dtype.itemsize, *cells.shape,
+                                              int(bool(unknown_is_filled)), ctypes.byref(count)))
+        return int(count.value)
+
+    def fill_enclosed_dev(self, cells_ptr, cell_bytes, shape, unknown_is_filled=True, want_count=True):
+        """vgt_hip_fill_enclosed_dev: the map on the device, filled in place.  want_count=True waits and returns the
+        number of cells filled; want_count=False leaves the work enqueued on the context's stream and returns None."""
+        count = _i64(0)
+        check(self._lib.vgt_hip_fill_enclosed_dev(self.handle, _ptr(cells_ptr), int(cell_bytes),
+                                                  *[int(c) for c in shape], int(bool(unknown_is_filled)),
+                                                  ctypes.byref(count) if want_count else None))
+        return int(count.value) if want_count else None
+
     def mesh_sdf(self, vertices, triangles, resolution, rule=MESH_RULE_REFERENCE, unknown_is_filled=True,
-                 add_virtual_border=False, with_occupancy=False):
+                 add_virtual_border=False, with_occupancy=False, solid=False):
         """Mesh -> SDF: mesh_grid_for -> a zeroed device map -> rasterize_mesh_dev -> sdf_dev; the grid never visits the
         host in between.  Returns (sdf float32 (nx, ny, nz), minimum, maximum, origin xyz) -- the map's transform is the
-        translation to `origin` -- and, with_occupancy=True, the rasterized occupancy as a fifth item."""
+        translation to `origin` -- and, with_occupancy=True, the rasterized occupancy as a fifth item.
+        solid=True puts fill_enclosed_dev (no count, nothing waited for) between the two: the field is negative inside
+        the body and the occupancy handed back is the filled one.  Only MESH_RULE_NEAREST guarantees a sealed shell for
+        a closed mesh; under MESH_RULE_REFERENCE the interior is filled only where the shell happens to be sealed."""
         import torch
         v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
@@ -483,6 +509,8 @@ class Context:
         torch.cuda.synchronize(device)
         self.rasterize_mesh_dev(v_dev.data_ptr(), len(v), t_dev.data_ptr(), len(t), occ_dev.data_ptr(), 4, shape,
                                 resolution, wfg.T.reshape(16), gfw.T.reshape(16), True, rule)
+        if solid:
+            self.fill_enclosed_dev(occ_dev.data_ptr(), 4, shape, unknown_is_filled, want_count=False)
         self.sdf_dev(occ_dev.data_ptr(), shape, resolution, sdf_dev.data_ptr(), ws_dev.data_ptr(), ws_bytes,
                      minmax_dev.data_ptr(), unknown_is_filled, add_virtual_border)
         self.synchronize()

@@ -22,6 +22,15 @@
 //   5. RankRoots   rank of every root inside its block + the block's offset -> out[root] = rank + 1.
 //   6. Relabel     out[i] = out[root(i)], 0 for inactive cells.
 // (The issue that asked for this suggested an LDS tile merge between 1 and 2; it is not here: see DESIGN.md.)
+//
+// Enclosed space (vgt_hip_fill_enclosed) is the same union-find under a fourth predicate, kComponentFill:
+// filled cells are inactive, two passable face neighbours are always connected.  "Outside" is a VIRTUAL ROOT, index -1 --
+// smaller than every cell, so "a parent is smaller than its child" still holds and Union needs no change: label[-1]
+// exists (the labels start 256 bytes into the scratch) and holds -1.  MergeEdges unites every passable border cell with
+// it, so after the unions a set is outside iff its root is -1: no flag array, no pass over the faces.  Stages 3-6 do
+// not run; instead
+//   3'. FillEnclosed  every active cell -> its root (in place, as FlattenCount does); a root other than -1 is an
+//                     enclosed set: the cell's occupancy becomes 1.0f.  One ballot and one atomic add per wave count them.
 #include "union_find_device.hpp"
 #include "vgt_internal.hpp"
 
@@ -38,6 +47,7 @@ constexpr int kScanThreads = 1024;
 //  occupancy classes (kClasses / kClassesAndIds): cls 0 = > 0.5, 1 = < 0.5, 2 = == 0.5, 3 = none of them (NaN: connects
 //  to nothing); id = the object id (0 when the predicate ignores ids)
 //  spatial segments: cls 1 = active, 0 = not; id = object id; e = the cell's entry of the local-extrema map
+//  enclosed space: cls 1 = passable (active), 0 = filled; id = 0
 struct CellKey
 {
   uint32_t cls, id;
@@ -55,7 +65,13 @@ struct View
   int id_offset;         // < 0: ids are not looked at
   const double* extrema; // spatial segments only: 3 doubles per cell
   double threshold;
+  int unknown_is_filled;  // enclosed space only: == 0.5f counts as filled
+  int nx;                 // enclosed space only: which cells are border cells
 };
+
+// Enclosed space: the labels of the virtual root "outside" and of a filled cell (which takes part in nothing).
+constexpr int32_t kFillOutside = -1;
+constexpr int32_t kFillInactive = INT32_MIN;
 
 template <int kMode>
 __device__ __forceinline__ CellKey LoadKey(const View& v, int64_t i, double e[3])
@@ -64,7 +80,10 @@ __device__ __forceinline__ CellKey LoadKey(const View& v, int64_t i, double e[3]
   const float occupancy = *reinterpret_cast<const float*>(rec);
   CellKey k;
   k.id = v.id_offset >= 0 ? *reinterpret_cast<const uint32_t*>(rec + v.id_offset) : 0u;
-  if (kMode == kComponentSegments)
+  if (kMode == kComponentFill)
+    // the SDF's predicate (include/vgt_hip.h); a NaN is neither: passable
+    k.cls = (occupancy > 0.5f || (v.unknown_is_filled && occupancy == 0.5f)) ? 0u : 1u;
+  else if (kMode == kComponentSegments)
   {
     e[0] = v.extrema[3 * i];
     e[1] = v.extrema[3 * i + 1];
@@ -90,6 +109,7 @@ __device__ __forceinline__ bool Connected(const View& v, const CellKey& a, const
     const double dx = ea[0] - eb[0], dy = ea[1] - eb[1], dz = ea[2] - eb[2];
     return sqrt((dx * dx + dy * dy) + dz * dz) < v.threshold;
   }
+  if (kMode == kComponentFill) return (a.cls & b.cls) != 0u;
   return a.cls == b.cls && a.cls != 3u && a.id == b.id;
 }
 
@@ -131,8 +151,10 @@ __global__ __launch_bounds__(kBlock) void InitRunsKernel(View v, int64_t total, 
   // start of the lane's run: the highest start bit at or below the lane (lane 0 always starts one)
   const unsigned long long at_or_below = starts & (~0ull >> (63 - lane));
   const int start_lane = 63 - __clzll(static_cast<long long>(at_or_below));
-  const bool active = kMode != kComponentSegments || k.cls != 0u;
-  label[i] = active ? static_cast<int32_t>(i - lane + start_lane) : -1;
+  const bool active = (kMode != kComponentSegments && kMode != kComponentFill) || k.cls != 0u;
+  const int32_t inactive = kMode == kComponentFill ? kFillInactive : -1;
+  label[i] = active ? static_cast<int32_t>(i - lane + start_lane) : inactive;
+  if (kMode == kComponentFill && i == 0) label[kFillOutside] = kFillOutside;  // the virtual root
 }
 
 template <int kMode>
@@ -154,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void MergeEdgesKernel(View v, int64_t total
   if (has_x) kx = LoadKey<kMode>(v, ix, ex);
   const bool join_y = has_y && Connected<kMode>(v, ky, ey, k, e);
   const bool join_x = has_x && Connected<kMode>(v, kx, ex, k, e);
-  bool skip_y = false, skip_x = false;
+  bool skip_y = false, skip_x = false, continues = false;
   if (kMode != kComponentSegments)
   {
     // the edge one cell below (same lines: z > 0, same wave: lane > 0) joins the same two runs when it is connected too
@@ -164,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void MergeEdgesKernel(View v, int64_t total
     const bool below_join_y = __shfl_up(static_cast<int>(join_y), 1) != 0;
     const bool below_join_x = __shfl_up(static_cast<int>(join_x), 1) != 0;
     const bool same_wave_line = lane > 0 && z > 0;
-    const bool continues = same_wave_line && Connected<kMode>(v, pk, eb, k, e);
+    continues = same_wave_line && Connected<kMode>(v, pk, eb, k, e);
     skip_y = continues && below_join_y && Connected<kMode>(v, pky, eb, ky, ey);
     skip_x = continues && below_join_x && Connected<kMode>(v, pkx, eb, kx, ex);
   }
@@ -178,6 +200,38 @@ __global__ __launch_bounds__(kBlock) void MergeEdgesKernel(View v, int64_t total
   }
   if (join_y && !skip_y) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(iy));
   if (join_x && !skip_x) Union(label, static_cast<int32_t>(i), static_cast<int32_t>(ix));
+  if (kMode == kComponentFill && k.cls != 0u)
+  {
+    // a passable border cell is outside.  On the X and Y faces the cell below is a border cell too: when this cell
+    // continues its run, that run is united already
+    const bool xy_border = x == 0 || x == v.nx - 1 || y == 0 || y == ny - 1;
+    if (xy_border ? !continues : (z == 0 || z == nz - 1)) Union(label, static_cast<int32_t>(i), kFillOutside);
+  }
+}
+
+// Enclosed space, after the unions: every active cell -> its root; a root other than the virtual one is an enclosed
+// set, whose cells become 1.0f (nothing else of a record is written, and no cell's occupancy is read here: the labels
+// say which cells are active).  *count += the cells written.
+__global__ __launch_bounds__(kBlock) void FillEnclosedKernel(int64_t total, int32_t* label, uint8_t* cells,
+                                                             int cell_bytes, unsigned long long* __restrict__ count)
+{
+  // (whole waves run: the ballot needs every lane)
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  bool fill = false;
+  if (i < total)
+  {
+    const int32_t parent = LoadLabel(label, static_cast<int32_t>(i));
+    if (parent != kFillInactive && parent != kFillOutside)
+    {
+      // (roots do not move in this kernel; writing a root over a parent keeps every concurrent walk valid)
+      const int32_t root = FindRoot(label, parent);
+      if (root != parent) label[i] = root;
+      fill = root != kFillOutside;
+    }
+  }
+  if (fill) *reinterpret_cast<float*>(cells + i * cell_bytes) = 1.0f;
+  const unsigned long long filled = __ballot(fill);
+  if ((threadIdx.x & 63) == 0 && filled != 0ull) atomicAdd(count, static_cast<unsigned long long>(__popcll(filled)));
 }
 
 // every cell -> its root; block_roots[b] = roots among the kScanBlockCells cells of block b
@@ -345,6 +399,46 @@ hipError_t Label(const View& v, int64_t nx, int64_t ny, int64_t nz, uint32_t* la
 }
 }  // namespace
 
+// Enclosed space carves the labelling scratch its own way: [0, 8) the count, [252, 256) label[-1], the labels from 256.
+constexpr size_t kFillLabelsOffset = 256;
+static_assert(kFillOutside == -1 && kFillLabelsOffset >= sizeof(unsigned long long) + sizeof(int32_t),
+              "label[-1] lies inside the scratch, behind the count");
+
+size_t FillScratchBytes(int64_t num_cells)
+{
+  return num_cells > 0 ? kFillLabelsOffset + static_cast<size_t>(num_cells) * sizeof(int32_t) : 0;
+}
+
+const unsigned long long* FillCountPtr(const void* scratch_dev)
+{
+  return static_cast<const unsigned long long*>(scratch_dev);
+}
+
+hipError_t LaunchFillEnclosed(void* cells_dev, int cell_bytes, int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz,
+                              void* scratch_dev, hipStream_t stream)
+{
+  View v;
+  v.cells = static_cast<const uint8_t*>(cells_dev);
+  v.cell_bytes = cell_bytes;
+  v.id_offset = -1;
+  v.extrema = nullptr;
+  v.threshold = 0.0;
+  v.unknown_is_filled = unknown_is_filled ? 1 : 0;
+  v.nx = static_cast<int>(nx);
+  const int64_t total = nx * ny * nz;
+  unsigned long long* const count = static_cast<unsigned long long*>(scratch_dev);
+  int32_t* const label = reinterpret_cast<int32_t*>(static_cast<char*>(scratch_dev) + kFillLabelsOffset);
+  const hipError_t err = hipMemsetAsync(count, 0, sizeof(*count), stream);
+  if (err != hipSuccess) return err;
+  const unsigned cell_blocks = Blocks(total, kBlock);
+  InitRunsKernel<kComponentFill><<<cell_blocks, kBlock, 0, stream>>>(v, total, static_cast<int>(nz), label);
+  MergeEdgesKernel<kComponentFill><<<cell_blocks, kBlock, 0, stream>>>(v, total, static_cast<int>(ny),
+                                                                       static_cast<int>(nz), label);
+  FillEnclosedKernel<<<cell_blocks, kBlock, 0, stream>>>(total, label, static_cast<uint8_t*>(cells_dev), cell_bytes,
+                                                         count);
+  return hipGetLastError();
+}
+
 size_t ComponentScratchBytes(int64_t num_cells) { return num_cells > 0 ? CarveScratch(num_cells).bytes : 0; }
 
 const uint32_t* ComponentCountPtr(const void* scratch_dev, int64_t num_cells)
@@ -362,6 +456,8 @@ hipError_t LaunchLabelComponents(const void* cells_dev, int cell_bytes, int obje
   v.id_offset = mode == kComponentClasses ? -1 : object_id_offset;
   v.extrema = extrema_dev;
   v.threshold = connected_threshold;
+  v.unknown_is_filled = 0;
+  v.nx = static_cast<int>(nx);
   switch (mode)
   {
     case kComponentClasses:

@@ -124,5 +124,35 @@ SignedDistanceField MeshToSignedDistanceField(const std::vector<Vector3d>& verti
   const OccupancyMap occupancy_map = RasterizeMeshIntoOccupancyMap(vertices, triangles, resolution, parameters.hip_device, rule);
   return ExtractSignedDistanceField(occupancy_map, parameters);
 }
+
+OccupancyMap RasterizeSolidMeshIntoOccupancyMap(const std::vector<Vector3d>& vertices,
+                                                const std::vector<Vector3i>& triangles, double resolution,
+                                                int hip_device, ClosestPointRule rule)
+{
+  OccupancyMap occupancy_map = RasterizeMeshIntoOccupancyMap(vertices, triangles, resolution, hip_device, rule);
+  FillEnclosedSpace(occupancy_map, true, hip_device);
+  return occupancy_map;
+}
+
+OccupancyComponentMap RasterizeSolidMeshIntoOccupancyComponentMap(const std::vector<Vector3d>& vertices,
+                                                                  const std::vector<Vector3i>& triangles,
+                                                                  double resolution, int hip_device,
+                                                                  ClosestPointRule rule)
+{
+  OccupancyComponentMap occupancy_map =
+      RasterizeMeshIntoOccupancyComponentMap(vertices, triangles, resolution, hip_device, rule);
+  FillEnclosedSpace(occupancy_map, true, hip_device);
+  return occupancy_map;
+}
+
+SignedDistanceField SolidMeshToSignedDistanceField(const std::vector<Vector3d>& vertices,
+                                                   const std::vector<Vector3i>& triangles, double resolution,
+                                                   const SignedDistanceFieldGenerationParameters& parameters,
+                                                   ClosestPointRule rule)
+{
+  const OccupancyMap occupancy_map =
+      RasterizeSolidMeshIntoOccupancyMap(vertices, triangles, resolution, parameters.hip_device, rule);
+  return ExtractSignedDistanceField(occupancy_map, parameters);
+}
 }  // namespace mesh_rasterizer
 }  // namespace vgt_hip

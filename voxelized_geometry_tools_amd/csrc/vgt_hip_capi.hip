@@ -2689,6 +2689,85 @@ int vgt_hip_connected_components(vgt_hip_ctx* ctx, const float* occupancy_host, 
   return result;
 }
 
+/* --------------------------------- enclosed space --------------------------------- */
+
+namespace
+{
+// Everything that can be said about the arguments of the two entry points before any HIP call.
+int CheckFillArguments(const vgt_hip_ctx* ctx, const void* cells, int cell_bytes, int64_t nx, int64_t ny, int64_t nz)
+{
+  if (!ctx || !cells) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (cell_bytes != 4 && cell_bytes != 8)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "cell_bytes must be 4 (OccupancyCell) or 8 (OccupancyComponentCell)");
+  return CheckComponentGrid(nx, ny, nz);
+}
+
+// Enqueues the fill on the context's stream; with `num_filled` it waits for the count.  Caller holds the context mutex
+// and has set the device.
+int RunFillEnclosed(vgt_hip_ctx* ctx, void* cells_dev, int cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                    int unknown_is_filled, int64_t* num_filled)
+{
+  const size_t need = vgt::FillScratchBytes(nx * ny * nz);
+  if (need > ctx->component_ws.bytes())
+  {
+    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the labelling scratch");
+    VGT_TRY_HIP(ctx->component_ws.Reserve(need), "allocate labelling scratch");
+  }
+  void* const scratch = ctx->component_ws.data();
+  hipError_t err = vgt::LaunchFillEnclosed(cells_dev, cell_bytes, unknown_is_filled, nx, ny, nz, scratch, ctx->stream);
+  if (!num_filled)
+  {
+    VGT_TRY_HIP(err, "fill enclosed space");
+    return VGT_HIP_OK;
+  }
+  unsigned long long count = 0;
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&count, vgt::FillCountPtr(scratch), sizeof(count), hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "fill enclosed space");  // (`count` is on this stack)
+  *num_filled = static_cast<int64_t>(count);
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+int vgt_hip_fill_enclosed_dev(vgt_hip_ctx* ctx, void* cells_dev, int cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                              int unknown_is_filled, int64_t* num_filled)
+{
+  const int rc = CheckFillArguments(ctx, cells_dev, cell_bytes, nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunFillEnclosed(ctx, cells_dev, cell_bytes, nx, ny, nz, unknown_is_filled, num_filled);
+}
+
+int vgt_hip_fill_enclosed(vgt_hip_ctx* ctx, void* cells_host, int cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                          int unknown_is_filled, int64_t* num_filled)
+{
+  const int rc = CheckFillArguments(ctx, cells_host, cell_bytes, nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t map_bytes = static_cast<size_t>(nx * ny * nz) * static_cast<size_t>(cell_bytes);
+  vgt::DeviceTemp map_dev;
+  VGT_TRY_HIP(map_dev.Allocate(map_bytes), "allocate the map");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipError_t err = hipMemcpyAsync(map_dev.as<void>(), cells_host, map_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (err != hipSuccess)
+  {
+    (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
+    return FailHip("upload the map", err);
+  }
+  int64_t count = 0;
+  const int result = RunFillEnclosed(ctx, map_dev.as<void>(), cell_bytes, nx, ny, nz, unknown_is_filled, &count);
+  if (result != VGT_HIP_OK)
+  {
+    (void)hipStreamSynchronize(ctx->stream);  // the host map stays as it was
+    return result;
+  }
+  err = hipMemcpyAsync(cells_host, map_dev.as<void>(), map_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "download the map");
+  if (num_filled) *num_filled = count;
+  return VGT_HIP_OK;
+}
+
 int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
                                        uint32_t* labels_host, uint32_t* num_components)
 {

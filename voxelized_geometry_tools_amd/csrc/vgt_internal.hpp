@@ -249,6 +249,9 @@ hipError_t LaunchLocalExtremaMap(const float* sdf_dev, int64_t nx, int64_t ny, i
 constexpr int kComponentClasses = 0;
 constexpr int kComponentClassesAndIds = 1;
 constexpr int kComponentSegments = 2;
+//   kComponentFill           enclosed space (LaunchFillEnclosed only): filled cells take no part, two passable cells are
+//                            always connected, and passable border cells are united with a virtual root "outside"
+constexpr int kComponentFill = 3;
 // scratch_dev: ComponentScratchBytes bytes (the int32 union-find labels and the scan's block counts).  labels_dev
 // receives 0 for a cell outside the labelling, else the number of its component: 1, 2, 3 ... in ascending order of the
 // smallest linear index of the component.  The number of components lies at ComponentCountPtr(scratch_dev) afterwards
@@ -259,6 +262,14 @@ const uint32_t* ComponentCountPtr(const void* scratch_dev, int64_t num_cells);
 hipError_t LaunchLabelComponents(const void* cells_dev, int cell_bytes, int object_id_offset, int mode,
                                  const double* extrema_dev, double connected_threshold, int64_t nx, int64_t ny,
                                  int64_t nz, uint32_t* labels_dev, void* scratch_dev, hipStream_t stream);
+// Enclosed space (include/vgt_hip.h, vgt_hip_fill_enclosed): every passable cell that no chain of face-adjacent passable
+// cells joins to a passable border cell gets occupancy 1.0f, in place; the number of cells written lies at
+// FillCountPtr(scratch_dev) afterwards (stream-ordered).  scratch_dev: FillScratchBytes bytes (the int32 union-find
+// labels + 256; never more than ComponentScratchBytes).  Grids below 2^31 cells.
+size_t FillScratchBytes(int64_t num_cells);
+const unsigned long long* FillCountPtr(const void* scratch_dev);
+hipError_t LaunchFillEnclosed(void* cells_dev, int cell_bytes, int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz,
+                              void* scratch_dev, hipStream_t stream);
 // mask_dev[i] = 1 when cell i's occupancy class is selected by component_types (1 filled | 2 empty | 4 unknown) and the
 // cell lies on a face of the grid or has a face neighbour with another label.
 hipError_t LaunchComponentSurfaceMask(const float* occupancy_dev, const uint32_t* labels_dev, int64_t nx, int64_t ny,

@@ -79,6 +79,31 @@ def occupancy_spheres(shape, seed=42, num_spheres=64):
     return occ
 
 
+def hollow_spheres(shape, seed=42, num_spheres=64, thickness=2.0):
+    """The D1 spheres with their interiors removed: every cell within radius - thickness of a centre is free again, which
+    leaves shells `thickness` voxels thick round sealed pockets (what fill_enclosed closes)."""
+    nx, ny, nz = shape
+    occ = occupancy_spheres(shape, seed, num_spheres)
+    centres, r2 = sphere_list(shape, seed, num_spheres)
+    for (cx, cy, cz), rr in zip(centres, r2):
+        inner = np.sqrt(rr) - thickness
+        if inner < 0.0:
+            continue
+        r = int(np.ceil(inner))
+        x0, x1 = max(cx - r, 0), min(cx + r + 1, nx)
+        y0, y1 = max(cy - r, 0), min(cy + r + 1, ny)
+        z0, z1 = max(cz - r, 0), min(cz + r + 1, nz)
+        if x0 >= x1 or y0 >= y1 or z0 >= z1:
+            continue
+        dx = (np.arange(x0, x1, dtype=np.int64) - cx) ** 2
+        dy = (np.arange(y0, y1, dtype=np.int64) - cy) ** 2
+        dz = (np.arange(z0, z1, dtype=np.int64) - cz) ** 2
+        d2 = dx[:, None, None] + dy[None, :, None] + dz[None, None, :]
+        sub = occ[x0:x1, y0:y1, z0:z1]
+        sub[d2.astype(np.float64) <= inner * inner] = 0.0
+    return occ
+
+
 def occupancy_salt(shape, seed=42, p=0.01):
     """D2 "salt": i.i.d. Bernoulli(p) filled voxels."""
     n = int(np.prod(shape))
