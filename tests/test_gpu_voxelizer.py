@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import check_empty_voxelization, check_voxelization, scene_clouds
+from filter_cases import hip_memcpy_htod as _hip_memcpy_htod
 from voxelized_geometry_tools_amd import capi, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -282,16 +283,6 @@ def test_concurrent_raycasts_from_host_threads(ctx, oracle):
     for i in range(6):
         want = oracle.raycast_f32(clouds[i], 1.5, xfs[i], vs, ivs, sizes, counts)
         assert np.array_equal(grids.retrieve(i, counts), want), i
-
-
-def _hip_memcpy_htod(dev_ptr, array):
-    """Test helper: writes a host array into library-owned device memory via the HIP runtime."""
-    import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    a = np.ascontiguousarray(array)
-    rc = hip.hipMemcpy(dev_ptr, a.ctypes.data_as(ctypes.c_void_p), a.nbytes, 1)
-    assert rc == 0, "hipMemcpy failed: %d" % rc
 
 
 def test_filter_options(ctx, oracle):
