@@ -51,6 +51,7 @@ def load(path=None):
                                                  ctypes.c_int, _p]
     lib.vgt_oracle_combine_free_and_named.argtypes = [_p, _p, _i64, _p, _p, _p]
     lib.vgt_oracle_coarse_gradient.argtypes = [_p, _i64, _i64, _i64, _f64, ctypes.c_int, _p, _p]
+    lib.vgt_oracle_index_coarse_gradient.argtypes = [_p, _i64, _i64, _i64, _f64, ctypes.c_int, _p, _p, _p]
     lib.vgt_oracle_local_extrema_map.argtypes = [_p, _i64, _i64, _i64, _f64, _p, _p]
     lib.vgt_oracle_estimate_distance.argtypes = [_p, _i64, _i64, _i64, _f64, _p, _p, _i64, _p, _p]
     lib.vgt_oracle_fine_gradient.argtypes = [_p, _i64, _i64, _i64, _f64, _p, _p, _i64, _f64, _p, _p]
@@ -149,14 +150,16 @@ def free_and_named_objects_sdf(records, shape, resolution, unknown_is_filled=Tru
     return out, float(lo.value), float(hi.value)
 
 
-def coarse_gradient(sdf, resolution, enable_edge_gradients=False):
-    """GetGridAlignedIndexCoarseGradient at every voxel: (gradient [nx, ny, nz, 3] float64, has_value bool)."""
+def coarse_gradient(sdf, resolution, enable_edge_gradients=False, rotation=None):
+    """GetGridAlignedIndexCoarseGradient at every voxel: (gradient [nx, ny, nz, 3] float64, has_value bool); with a
+    rotation (3x3 row-major), GetIndexCoarseGradient."""
     field = np.ascontiguousarray(sdf, dtype=np.float32)
     nx, ny, nz = field.shape
     grad = np.empty((nx, ny, nz, 3), dtype=np.float64)
     has = np.empty((nx, ny, nz), dtype=np.uint8)
-    load().vgt_oracle_coarse_gradient(_ptr(field), nx, ny, nz, float(resolution), int(bool(enable_edge_gradients)),
-                                      _ptr(grad), _ptr(has))
+    rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+    load().vgt_oracle_index_coarse_gradient(_ptr(field), nx, ny, nz, float(resolution), int(bool(enable_edge_gradients)),
+                                            _ptr(rot) if rot is not None else None, _ptr(grad), _ptr(has))
     return grad, has.astype(bool)
 
 

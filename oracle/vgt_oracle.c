@@ -815,6 +815,25 @@ void vgt_oracle_coarse_gradient(const float* sdf, int64_t nx, int64_t ny, int64_
 #undef SDF_AT
 }
 
+/* GetIndexCoarseGradient (:903-920): the grid-aligned gradient, where it has a value, times the origin
+ * transform's rotation (9 doubles row-major, or NULL for none), rows left to right. */
+void vgt_oracle_index_coarse_gradient(const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                      int enable_edge_gradients, const double* rotation, double* gradient,
+                                      uint8_t* has_value)
+{
+  vgt_oracle_coarse_gradient(sdf, nx, ny, nz, resolution, enable_edge_gradients, gradient, has_value);
+  if (!rotation) return;
+  const int64_t total = nx * ny * nz;
+  for (int64_t i = 0; i < total; i++)
+  {
+    if (!has_value[i]) continue;
+    const double gx = gradient[3 * i], gy = gradient[3 * i + 1], gz = gradient[3 * i + 2];
+    gradient[3 * i] = rotation[0] * gx + rotation[1] * gy + rotation[2] * gz;
+    gradient[3 * i + 1] = rotation[3] * gx + rotation[4] * gy + rotation[5] * gz;
+    gradient[3 * i + 2] = rotation[6] * gx + rotation[7] * gy + rotation[8] * gz;
+  }
+}
+
 /* ------------------------------------------------------------------------- */
 
 /* float -> int32 as the DEVICE kernels' cast behaves (cuda_voxelization_helpers.cu:140-144, :229-240 run as CUDA

@@ -368,6 +368,31 @@ class Context:
             _ptr(queries_ptr), int(num_queries), float(minimum_distance), float(stepsize_multiplier),
             int(max_iterations), _ptr(position_ptr), _ptr(has_value_ptr), _ptr(status_ptr), _ptr(iterations_ptr)))
 
+    def sdf_coarse_gradient_dev(self, sdf_ptr, shape, resolution, gradient_ptr, has_value_ptr=None,
+                                enable_edge_gradients=False, rotation=None):
+        """vgt_hip_sdf_coarse_gradient_dev: field and outputs (3 doubles and, optionally, a byte per voxel) on the
+        device; enqueued on the context's stream."""
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        check(self._lib.vgt_hip_sdf_coarse_gradient_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), int(bool(enable_edge_gradients)),
+            _ptr(rot), _ptr(gradient_ptr), _ptr(has_value_ptr)))
+
+    def sdf_estimate_distance_dev(self, sdf_ptr, shape, resolution, queries_ptr, num_queries, distance_ptr,
+                                  has_value_ptr=None, grid_from_world=None):
+        """vgt_hip_sdf_estimate_distance_dev: field, queries and outputs on the device (the transform is a host array);
+        enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        check(self._lib.vgt_hip_sdf_estimate_distance_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(queries_ptr),
+            int(num_queries), _ptr(distance_ptr), _ptr(has_value_ptr)))
+
+    def sdf_local_extrema_map_dev(self, sdf_ptr, shape, resolution, extrema_ptr, rotation=None):
+        """vgt_hip_sdf_local_extrema_map_dev: field and the 3 doubles per voxel on the device; runs on the context's
+        stream and returns when it is done (its scratch goes with the call)."""
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        check(self._lib.vgt_hip_sdf_local_extrema_map_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(rot), _ptr(extrema_ptr)))
+
     def sdf_local_extrema_map(self, sdf, resolution, rotation=None):
         """ComputeLocalExtremaMap: [nx, ny, nz, 3] float64 (grid-frame extremum location per voxel, +inf = off the grid)."""
         field = np.ascontiguousarray(sdf, dtype=np.float32)
