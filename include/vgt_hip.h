@@ -486,6 +486,59 @@ int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host
 int vgt_hip_component_surface_mask_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, const uint32_t* labels_dev,
                                        int64_t nx, int64_t ny, int64_t nz, int component_types, uint8_t* mask_dev);
 
+/* ---- selected cells as compact ordered lists (csrc/select_kernels.hip) ----
+ * A per-cell predicate, then the selected cells in ascending linear index (X-major, Z fastest: the order of the
+ * reference's loops), with the cell's value and one uint32 per cell on request.  What the reference obtains with a host
+ * loop over every voxel: IsSurfaceIndex (S/occupancy_map.cpp:201-246 and the same text in the other map types),
+ * the display exports of I/ros_interface.hpp:92-148, the lists of ExtractComponentSurfaces.
+ * The class of a value v against `threshold` t (0.5 for occupancy, 0.0 for a signed distance) is one of four bits:
+ *   VGT_HIP_CLASS_ABOVE 0x01  v > t      VGT_HIP_CLASS_EQUAL     0x04  v == t
+ *   VGT_HIP_CLASS_BELOW 0x02  v < t      VGT_HIP_CLASS_UNORDERED 0x08  none of them (NaN)
+ * (The "unknown" bit 0x04 of vgt_hip_component_surface_mask and of the topology is 0x04 | 0x08 here.)
+ * A cell is selected when its class is in class_mask (1 .. 15) and the rule holds:
+ *   VGT_HIP_SELECT_ALL                no further condition.
+ *   VGT_HIP_SELECT_SURFACE_26         IsSurfaceIndex, literally; threshold must be 0.5f.  A cell < 0.5 is a surface cell
+ *                                     when one of its (up to 26) neighbours inside the grid is >= 0.5; a cell > 0.5 when
+ *                                     one is <= 0.5; a cell == 0.5 when one is != 0.5.  A NaN cell never is one; a NaN
+ *                                     neighbour satisfies != 0.5 only.  Cells outside the grid do not exist: a face of
+ *                                     the grid is no surface by itself.
+ *   VGT_HIP_SELECT_COMPONENT_SURFACE  the rule of vgt_hip_component_surface_mask: the cell lies on a face of the grid or
+ *                                     one of its six face neighbours has another label.  Needs `labels`.
+ * *count always receives the number of selected cells.  indices_out == NULL with capacity == 0 only counts.  When the
+ * number exceeds `capacity` the call fails with VGT_HIP_ERR_INVALID_ARGUMENT (the message names both numbers) and writes
+ * nothing to the outputs.  values_out / labels_out may be NULL; labels_out needs `labels`.  Grids below 2^31 cells
+ * (indices are int32).  Blocking: the count is read back.  The _dev form takes device pointers for the grids and the
+ * outputs and runs on the context's stream.  Scratch the context keeps: 1 bit per voxel + 4 bytes per 1024 voxels. */
+#define VGT_HIP_CLASS_ABOVE 0x01
+#define VGT_HIP_CLASS_BELOW 0x02
+#define VGT_HIP_CLASS_EQUAL 0x04
+#define VGT_HIP_CLASS_UNORDERED 0x08
+#define VGT_HIP_SELECT_ALL 0
+#define VGT_HIP_SELECT_SURFACE_26 1
+#define VGT_HIP_SELECT_COMPONENT_SURFACE 2
+int vgt_hip_select_cells(vgt_hip_ctx* ctx, const float* values_host, const uint32_t* labels_host, int64_t nx, int64_t ny,
+                         int64_t nz, int rule, int class_mask, float threshold, int32_t* indices_out, float* values_out,
+                         uint32_t* labels_out, int64_t capacity, int64_t* count);
+int vgt_hip_select_cells_dev(vgt_hip_ctx* ctx, const float* values_dev, const uint32_t* labels_dev, int64_t nx,
+                             int64_t ny, int64_t nz, int rule, int class_mask, float threshold, int32_t* indices_out,
+                             float* values_out, uint32_t* labels_out, int64_t capacity, int64_t* count);
+/* The same for uploaded cells, threshold 0.5f, lists to HOST memory.  labels_dev_or_null: the labels of
+ * VGT_HIP_SELECT_COMPONENT_SURFACE on the device (e.g. of vgt_hip_cells_spatial_segments_dev); NULL: the cells' own
+ * `component` member, for the layouts that have one.  payload_host (may be NULL) receives the member payload_member of
+ * the selected cells, as the cell layout has them:
+ *   VGT_HIP_CELL_MEMBER_OBJECT_ID        at object_id_offset (cells created with one)
+ *   VGT_HIP_CELL_MEMBER_COMPONENT        at 4 of 8-byte cells without object id (OccupancyComponentCell), at 8 of 16-byte
+ *                                        cells (TaggedObjectOccupancyComponentCell)
+ *   VGT_HIP_CELL_MEMBER_SPATIAL_SEGMENT  at 12 of 16-byte cells
+ * occupancy_host may be NULL. */
+#define VGT_HIP_CELL_MEMBER_NONE 0
+#define VGT_HIP_CELL_MEMBER_OBJECT_ID 1
+#define VGT_HIP_CELL_MEMBER_COMPONENT 2
+#define VGT_HIP_CELL_MEMBER_SPATIAL_SEGMENT 3
+int vgt_hip_cells_select(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* labels_dev_or_null, int rule,
+                         int class_mask, int32_t* indices_host, float* occupancy_host, uint32_t* payload_host,
+                         int payload_member, int64_t capacity, int64_t* count);
+
 /* ---- holes and voids per component: ComputeComponentTopology (I/topology_computation.hpp:331-670, called from
  * S/occupancy_component_map.cpp:594-653 and S/tagged_object_occupancy_component_map.cpp:566-625).
  * The reference walks hash sets per component; its result is this closed form, computed by csrc/topology_kernels.hip.

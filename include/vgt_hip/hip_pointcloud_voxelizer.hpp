@@ -242,8 +242,9 @@ int64_t FillEnclosedSpace(OccupancyComponentMap& map, bool unknown_is_filled = t
 uint32_t UpdateSpatialSegments(TaggedObjectOccupancyComponentMap& map, double connected_threshold,
                                const SignedDistanceFieldGenerationParameters& sdf_parameters);
 // ExtractComponentSurfaces (occupancy_component_map.cpp:511-571, tagged variant :485-541) from the cells' current
-// `component` members: the device computes the dense mask (vgt_hip_component_surface_mask), the host sorts it into
-// per-component index lists.
+// `component` members: the device selects the surface cells into one compact ordered list with their components
+// (vgt_hip_cells_select, VGT_HIP_SELECT_COMPONENT_SURFACE), the host splits that list by component.  No dense mask
+// comes back.
 ComponentSurfaces ExtractComponentSurfaces(const OccupancyComponentMap& map, uint8_t component_types,
                                            int hip_device = 0);
 ComponentSurfaces ExtractComponentSurfaces(const TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
@@ -257,4 +258,74 @@ ComponentSurfaces ExtractComponentSurfaces(const TaggedObjectOccupancyComponentM
 TopologicalInvariants ComputeComponentTopology(OccupancyComponentMap& map, uint8_t component_types, int hip_device = 0);
 TopologicalInvariants ComputeComponentTopology(TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
                                                bool connect_across_objects, int hip_device = 0);
+// ---- surface cells and display exports as compact lists (csrc/host/hip_display.cc) ----
+// IsSurfaceIndex (occupancy_map.cpp:201-246 and the same text in the other three map types) as a list: the grid indices
+// (x, y, z) of every cell for which it is true, in ascending linear order.  The device selects
+// (VGT_HIP_SELECT_SURFACE_26, include/vgt_hip.h); std::invalid_argument for an uninitialised map or one of 2^31 cells
+// and more.
+using GridIndices = std::vector<std::array<int64_t, 3>>;
+GridIndices SurfaceIndices(const OccupancyMap& map, int hip_device = 0);
+GridIndices SurfaceIndices(const OccupancyComponentMap& map, int hip_device = 0);
+GridIndices SurfaceIndices(const TaggedObjectOccupancyMap& map, int hip_device = 0);
+GridIndices SurfaceIndices(const TaggedObjectOccupancyComponentMap& map, int hip_device = 0);
+
+// What ros_interface::ExportVoxelGridToRViz (ros_interface.hpp:92-148) puts into a CUBE_LIST marker: the cells whose
+// colour has alpha > 0, in X, Y, Z loop order; points[i] is the cell's centre in the grid frame, colors[i] its colour.
+// The marker's pose is the map's OriginTransform(), its scale the voxel size, its frame the map's Frame().
+// NOT PINNED by the reference's sources available here: the centre is (index + 0.5) * voxel size per axis,
+// in double (GridIndexToLocationInGridFrame lives in common_robotics_utilities).
+using ColorRGBA = std::array<float, 4>;  // r, g, b, a
+struct DisplayCubes
+{
+  std::vector<std::array<double, 3>> points;
+  std::vector<ColorRGBA> colors;
+};
+// ros_interface.cpp's ExportForDisplay / ExportForSeparateDisplay / ExportSurfacesForDisplay: > 0.5 collision_color,
+// < 0.5 free_color, everything else unknown_color; the surface variant keeps IsSurfaceIndex cells only.  A class whose
+// colour has alpha <= 0 is left out of the device's selection.  ExportForSeparateDisplay: {collision only, free only,
+// unknown only}.
+DisplayCubes ExportForDisplay(const OccupancyMap& map, const ColorRGBA& collision_color, const ColorRGBA& free_color,
+                              const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportForDisplay(const OccupancyComponentMap& map, const ColorRGBA& collision_color,
+                              const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportForDisplay(const TaggedObjectOccupancyMap& map, const ColorRGBA& collision_color,
+                              const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportForDisplay(const TaggedObjectOccupancyComponentMap& map, const ColorRGBA& collision_color,
+                              const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+std::array<DisplayCubes, 3> ExportForSeparateDisplay(const OccupancyMap& map, const ColorRGBA& collision_color,
+                                                     const ColorRGBA& free_color, const ColorRGBA& unknown_color,
+                                                     int hip_device = 0);
+std::array<DisplayCubes, 3> ExportForSeparateDisplay(const OccupancyComponentMap& map, const ColorRGBA& collision_color,
+                                                     const ColorRGBA& free_color, const ColorRGBA& unknown_color,
+                                                     int hip_device = 0);
+std::array<DisplayCubes, 3> ExportForSeparateDisplay(const TaggedObjectOccupancyMap& map,
+                                                     const ColorRGBA& collision_color, const ColorRGBA& free_color,
+                                                     const ColorRGBA& unknown_color, int hip_device = 0);
+std::array<DisplayCubes, 3> ExportForSeparateDisplay(const TaggedObjectOccupancyComponentMap& map,
+                                                     const ColorRGBA& collision_color, const ColorRGBA& free_color,
+                                                     const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportSurfacesForDisplay(const OccupancyMap& map, const ColorRGBA& collision_color,
+                                      const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportSurfacesForDisplay(const OccupancyComponentMap& map, const ColorRGBA& collision_color,
+                                      const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportSurfacesForDisplay(const TaggedObjectOccupancyMap& map, const ColorRGBA& collision_color,
+                                      const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+DisplayCubes ExportSurfacesForDisplay(const TaggedObjectOccupancyComponentMap& map, const ColorRGBA& collision_color,
+                                      const ColorRGBA& free_color, const ColorRGBA& unknown_color, int hip_device = 0);
+// ExportConnectedComponentsForDisplay (ros_interface.cpp:356-389, 1030-1063): a cell whose occupancy != 0.5 (a NaN too)
+// gets palette_fn(component); a cell == 0.5 the same with color_unknown_components, else grey (0.5, 0.5, 0.5, 1).
+// NOT PINNED: the reference's palette is common_robotics_utilities' LookupUniqueColor, which is not available here; the
+// palette is the caller's function.  It is called once per listed cell, on the host.
+using ComponentPalette = std::function<ColorRGBA(uint32_t component)>;
+DisplayCubes ExportConnectedComponentsForDisplay(const OccupancyComponentMap& map, bool color_unknown_components,
+                                                 const ComponentPalette& palette_fn, int hip_device = 0);
+DisplayCubes ExportConnectedComponentsForDisplay(const TaggedObjectOccupancyComponentMap& map,
+                                                 bool color_unknown_components, const ComponentPalette& palette_fn,
+                                                 int hip_device = 0);
+// ExportSDFForDisplay (ros_interface.hpp:332-381): alpha clamped to [0, 1]; distance > 0 green, < 0 red, each
+// |distance / extremum| * 0.8f + 0.2f in float, else blue.  The extrema are the field's cached minimum / maximum when it
+// is locked, else those of its values.  ExportSDFForDisplayCollisionOnly (:383-411): the cells with distance <= 0 in
+// (1, 0, 0, alpha).
+DisplayCubes ExportSDFForDisplay(const SignedDistanceField& sdf, float alpha = 0.01f, int hip_device = 0);
+DisplayCubes ExportSDFForDisplayCollisionOnly(const SignedDistanceField& sdf, float alpha = 0.01f, int hip_device = 0);
 }  // namespace vgt_hip

@@ -85,6 +85,9 @@ SIGNATURES = {
     "vgt_hip_cells_update_spatial_segments": (_int, [_p, _p, _f64, _f64, _int, _int, _p, _p, _p]),
     "vgt_hip_component_surface_mask": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
     "vgt_hip_component_surface_mask_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
+    "vgt_hip_select_cells": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _int, _f32, _p, _p, _p, _i64, _p]),
+    "vgt_hip_select_cells_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _int, _f32, _p, _p, _p, _i64, _p]),
+    "vgt_hip_cells_select": (_int, [_p, _p, _p, _int, _int, _p, _p, _p, _int, _i64, _p]),
     "vgt_hip_component_topology_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint32, _p]),
     "vgt_hip_component_topology": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_uint64]),
     "vgt_hip_cells_component_topology": (_int, [_p, _p, _int, _int, _p, _p, _p, ctypes.c_uint64]),
@@ -149,6 +152,20 @@ PROJECT_OUTSIDE = 1
 PROJECT_FLAT_GRADIENT = 2
 PROJECT_LEFT_GRID = 3
 PROJECT_ITERATION_LIMIT = 4
+
+# selection rules, value classes and cell members of select_cells / Cells.select (VGT_HIP_SELECT_*, VGT_HIP_CLASS_*,
+# VGT_HIP_CELL_MEMBER_*)
+SELECT_ALL = 0
+SELECT_SURFACE_26 = 1
+SELECT_COMPONENT_SURFACE = 2
+CLASS_ABOVE = 0x01
+CLASS_BELOW = 0x02
+CLASS_EQUAL = 0x04
+CLASS_UNORDERED = 0x08
+CELL_MEMBER_NONE = 0
+CELL_MEMBER_OBJECT_ID = 1
+CELL_MEMBER_COMPONENT = 2
+CELL_MEMBER_SPATIAL_SEGMENT = 3
 
 # vgt_hip_component_topology_t
 COMPONENT_TOPOLOGY = np.dtype([(name, np.int32) for name in (
@@ -437,6 +454,48 @@ class Context:
         check(self._lib.vgt_hip_component_surface_mask_dev(self.handle, _ptr(occ_ptr), _ptr(labels_ptr),
                                                            *[int(v) for v in shape], int(component_types),
                                                            _ptr(mask_ptr)))
+
+    def select_cells(self, values, rule, class_mask, threshold=0.5, labels=None, with_values=False,
+                     with_labels=False):
+        """The cells of a float grid that `rule` (SELECT_*) selects among the classes of class_mask (CLASS_* against
+        `threshold`), as int32 linear indices in ascending order; with_values / with_labels add float32 values and
+        uint32 labels of those cells: indices, or (indices[, values][, labels]).  One call counts, a second one fetches."""
+        val = np.ascontiguousarray(values, dtype=np.float32)
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.uint32)
+        if val.ndim != 3 or (lab is not None and lab.shape != val.shape):
+            raise ValueError("values and labels must be (nx, ny, nz) grids of one shape")
+        count = ctypes.c_int64(0)
+
+        def call(indices, vals, labs, capacity):
+            check(self._lib.vgt_hip_select_cells(self.handle, _ptr(val), _ptr(lab), *val.shape, int(rule),
+                                                 int(class_mask), float(threshold), _ptr(indices), _ptr(vals),
+                                                 _ptr(labs), capacity, ctypes.byref(count)))
+
+        call(None, None, None, 0)
+        n = int(count.value)
+        indices = np.empty(n, dtype=np.int32)
+        vals = np.empty(n, dtype=np.float32) if with_values else None
+        labs = np.empty(n, dtype=np.uint32) if with_labels else None
+        if n:
+            call(indices, vals, labs, n)
+        out = (indices,) + ((vals,) if with_values else ()) + ((labs,) if with_labels else ())
+        return out if len(out) > 1 else indices
+
+    def select_cells_dev(self, values_ptr, shape, rule, class_mask, threshold=0.5, labels_ptr=None, indices_ptr=None,
+                         values_out_ptr=None, labels_out_ptr=None, capacity=0):
+        """vgt_hip_select_cells_dev: device buffers in and out -> the number of selected cells (indices_ptr=None with
+        capacity=0 only counts)."""
+        count = ctypes.c_int64(0)
+        check(self._lib.vgt_hip_select_cells_dev(self.handle, _ptr(values_ptr), _ptr(labels_ptr),
+                                                 *[int(v) for v in shape], int(rule), int(class_mask), float(threshold),
+                                                 _ptr(indices_ptr), _ptr(values_out_ptr), _ptr(labels_out_ptr),
+                                                 int(capacity), ctypes.byref(count)))
+        return int(count.value)
+
+    def cells_select(self, cells, rule, class_mask, payload_member=CELL_MEMBER_NONE, labels_ptr=None,
+                     with_occupancy=False):
+        """vgt_hip_cells_select on a Cells handle of this context: see Cells.select."""
+        return cells.select(rule, class_mask, payload_member, labels_ptr, with_occupancy)
 
     def component_topology(self, occupancy, component_types, with_labels=False):
         """ComputeComponentTopology of an occupancy grid (it labels the grid first): a COMPONENT_TOPOLOGY array with one
@@ -995,6 +1054,28 @@ class Cells:
                                                            int(bool(connect_across_objects)), _ptr(labels),
                                                            ctypes.byref(count)))
         return labels, int(count.value)
+
+    def select(self, rule, class_mask, payload_member=CELL_MEMBER_NONE, labels_ptr=None, with_occupancy=False):
+        """The uploaded cells that `rule` selects among the occupancy classes of class_mask (threshold 0.5): int32 linear
+        indices in ascending order, or (indices[, occupancy][, payload]) with with_occupancy and a payload_member
+        (CELL_MEMBER_*).  labels_ptr: device labels for SELECT_COMPONENT_SURFACE; None: the cells' `component` member."""
+        count = ctypes.c_int64(0)
+
+        def call(indices, occ, payload, capacity):
+            check(self._lib.vgt_hip_cells_select(self.ctx.handle, self.handle, _ptr(labels_ptr), int(rule),
+                                                 int(class_mask), _ptr(indices), _ptr(occ), _ptr(payload),
+                                                 int(payload_member), capacity, ctypes.byref(count)))
+
+        call(None, None, None, 0)
+        n = int(count.value)
+        want_payload = int(payload_member) != CELL_MEMBER_NONE
+        indices = np.empty(n, dtype=np.int32)
+        occ = np.empty(n, dtype=np.float32) if with_occupancy else None
+        payload = np.empty(n, dtype=np.uint32) if want_payload else None
+        if n:
+            call(indices, occ, payload, n)
+        out = (indices,) + ((occ,) if with_occupancy else ()) + ((payload,) if want_payload else ())
+        return out if len(out) > 1 else indices
 
     def component_topology(self, component_types, connect_across_objects=False, with_labels=False):
         """ComputeComponentTopology of the uploaded cells: the COMPONENT_TOPOLOGY table of Context.component_topology;

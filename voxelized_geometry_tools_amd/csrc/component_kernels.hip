@@ -439,6 +439,12 @@ hipError_t LaunchFillEnclosed(void* cells_dev, int cell_bytes, int unknown_is_fi
   return hipGetLastError();
 }
 
+hipError_t LaunchScanBlocks(int32_t* block_counts_dev, int64_t blocks, uint32_t* total_dev, hipStream_t stream)
+{
+  ScanBlocksKernel<<<1, kScanThreads, 0, stream>>>(block_counts_dev, blocks, total_dev);
+  return hipGetLastError();
+}
+
 size_t ComponentScratchBytes(int64_t num_cells) { return num_cells > 0 ? CarveScratch(num_cells).bytes : 0; }
 
 const uint32_t* ComponentCountPtr(const void* scratch_dev, int64_t num_cells)

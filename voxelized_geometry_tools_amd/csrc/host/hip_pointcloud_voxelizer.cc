@@ -805,47 +805,4 @@ uint32_t UpdateSpatialSegments(TaggedObjectOccupancyComponentMap& map, double co
   return result.count;
 }
 
-namespace
-{
-template <typename Cell>
-ComponentSurfaces ExtractSurfaces(const CellGrid<Cell>& map, uint8_t component_types, int hip_device)
-{
-  if (!map.IsInitialized()) throw std::invalid_argument("Grid must be initialized");
-  if (component_types < 1 || component_types > 7)
-    throw std::invalid_argument("component types must be a combination of FILLED_, EMPTY_ and UNKNOWN_COMPONENTS");
-  const std::vector<Cell>& data = map.GetImmutableRawData();
-  std::vector<float> occupancy(data.size());
-  std::vector<uint32_t> labels(data.size());
-  for (size_t i = 0; i < data.size(); i++)
-  {
-    occupancy[i] = data[i].occupancy;
-    labels[i] = data[i].component;
-  }
-  std::vector<uint8_t> mask(data.size());
-  const int rc = vgt_hip_component_surface_mask(SharedSdfContext(hip_device), occupancy.data(), labels.data(),
-                                                map.NumXVoxels(), map.NumYVoxels(), map.NumZVoxels(), component_types,
-                                                mask.data());
-  if (rc != VGT_HIP_OK) ThrowForCode(rc, vgt_hip_last_error());
-  ComponentSurfaces surfaces;
-  const int64_t ny = map.NumYVoxels(), nz = map.NumZVoxels();
-  for (size_t i = 0; i < mask.size(); i++)
-    if (mask[i])
-    {
-      const int64_t index = static_cast<int64_t>(i);
-      surfaces[labels[i]].push_back({index / (ny * nz), (index / nz) % ny, index % nz});
-    }
-  return surfaces;
-}
-}  // namespace
-
-ComponentSurfaces ExtractComponentSurfaces(const OccupancyComponentMap& map, uint8_t component_types, int hip_device)
-{
-  return ExtractSurfaces(map, component_types, hip_device);
-}
-
-ComponentSurfaces ExtractComponentSurfaces(const TaggedObjectOccupancyComponentMap& map, uint8_t component_types,
-                                           int hip_device)
-{
-  return ExtractSurfaces(map, component_types, hip_device);
-}
 }  // namespace vgt_hip

@@ -70,6 +70,8 @@ struct vgt_hip_ctx
   vgt::DeviceCache sdf_in, sdf_out, sdf_ws;
   // Scratch of the component labelling (union-find labels + scan counts), kept like the buffers above
   vgt::DeviceCache component_ws;
+  // Scratch of the cell selection (bit grid + scan counts), kept likewise
+  vgt::DeviceCache select_ws;
   // Scratch of the mesh rasterizer (triangle records, work-list offsets, totals and status), kept likewise
   vgt::DeviceCache mesh_ws;
   // Page-locked staging ring of the batched downloads (DownloadToHostArrays): kStagingSlots slots of kStagingSlotBytes,
@@ -244,7 +246,7 @@ hipError_t DrainKeepingFirst(hipStream_t s, hipError_t err)
 void FreeCachedSdfBuffers(vgt_hip_ctx* ctx)
 {
   for (vgt::DeviceCache* b : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws,
-                             &ctx->mesh_ws})
+                             &ctx->select_ws, &ctx->mesh_ws})
     (void)b->Release();
   if (ctx->host_staging) (void)hipHostFree(ctx->host_staging);
   ctx->host_staging = nullptr;
@@ -2912,6 +2914,216 @@ int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host
   if (err == hipSuccess) err = hipMemcpyAsync(mask_host, mask_dev, n, hipMemcpyDeviceToHost, ctx->stream);
   VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "component surface mask");
   return VGT_HIP_OK;
+}
+
+/* ------------------------- selected cells as compact ordered lists ------------------------- */
+
+namespace
+{
+// Everything that can be said about a selection before any HIP call (the context is not looked into).
+int CheckSelectArguments(const vgt_hip_ctx* ctx, const void* values, bool has_labels, int64_t nx, int64_t ny, int64_t nz,
+                         int rule, int class_mask, float threshold, const void* indices_out, const void* labels_out,
+                         int64_t capacity, const int64_t* count)
+{
+  if (!ctx || !values || !count) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckComponentGrid(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  if (rule != VGT_HIP_SELECT_ALL && rule != VGT_HIP_SELECT_SURFACE_26 && rule != VGT_HIP_SELECT_COMPONENT_SURFACE)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown selection rule " + std::to_string(rule));
+  if (class_mask < 1 || class_mask > 15)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "the class mask must be a combination of 1 (above), 2 (below), 4 (equal), 8 (unordered)");
+  if (rule == VGT_HIP_SELECT_SURFACE_26 && threshold != 0.5f)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the 26-neighbour surface rule is defined for the threshold 0.5 only");
+  if (threshold != threshold) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the threshold must be a number");
+  if (rule == VGT_HIP_SELECT_COMPONENT_SURFACE && !has_labels)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the component surface rule needs labels");
+  if (labels_out && !has_labels) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a label list needs labels");
+  if (capacity < 0 || (capacity > 0 && !indices_out))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "invalid index buffer (capacity without a buffer, or a negative one)");
+  return VGT_HIP_OK;
+}
+
+// Marks and counts on the context's stream and waits for the count (*count); with room for it, the lists go to the
+// DEVICE buffers of `out` (out.capacity as the caller gave it; nothing is written when the count exceeds it) and the
+// stream is drained.  Caller holds the context mutex and has set the device.
+int RunSelect(vgt_hip_ctx* ctx, const vgt::SelectGrid& grid, const vgt::SelectOutput& out, int64_t* count)
+{
+  const int64_t n = static_cast<int64_t>(grid.nx) * grid.ny * grid.nz;
+  const size_t need = vgt::SelectScratchBytes(n);
+  if (need > ctx->select_ws.bytes())
+  {
+    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the selection scratch");
+    VGT_TRY_HIP(ctx->select_ws.Reserve(need), "allocate selection scratch");
+  }
+  void* const scratch = ctx->select_ws.data();
+  hipError_t err = vgt::LaunchSelectMark(grid, scratch, ctx->stream);
+  uint32_t selected = 0;
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&selected, vgt::SelectCountPtr(scratch, n), sizeof(selected), hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "select cells");  // (`selected` is on this stack)
+  *count = static_cast<int64_t>(selected);
+  if (!out.indices_dev) return VGT_HIP_OK;  // count only
+  if (*count > out.capacity)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the selection holds " + std::to_string(*count) +
+                                                  " cells, the output buffers " + std::to_string(out.capacity));
+  if (*count == 0) return VGT_HIP_OK;
+  err = vgt::LaunchSelectEmit(grid, out, scratch, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "select cells");
+  return VGT_HIP_OK;
+}
+
+// RunSelect with lists in HOST memory: counts, then emits into device buffers of exactly the count and downloads them.
+// payload_source_dev / payload_stride: where payload_host's uint32 come from.  Caller holds the context mutex.
+int RunSelectToHost(vgt_hip_ctx* ctx, const vgt::SelectGrid& grid, const void* payload_source_dev, int payload_stride,
+                    int32_t* indices_host, float* values_host, uint32_t* payload_host, int64_t capacity, int64_t* count)
+{
+  vgt::SelectOutput none{};
+  int rc = RunSelect(ctx, grid, none, count);
+  if (rc != VGT_HIP_OK || !indices_host) return rc;
+  if (*count > capacity)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the selection holds " + std::to_string(*count) +
+                                                  " cells, the output buffers " + std::to_string(capacity));
+  if (*count == 0) return VGT_HIP_OK;
+  const size_t list_bytes = static_cast<size_t>(*count) * 4;
+  const size_t lists = 1 + (values_host ? 1 : 0) + (payload_host ? 1 : 0);
+  vgt::DeviceTemp buffer;  // indices, values, payload
+  VGT_TRY_HIP(buffer.Allocate(list_bytes * lists), "allocate selection lists");
+  char* next = buffer.as<char>();
+  vgt::SelectOutput out{};
+  out.indices_dev = reinterpret_cast<int32_t*>(next);
+  next += list_bytes;
+  if (values_host)
+  {
+    out.values_dev = reinterpret_cast<float*>(next);
+    next += list_bytes;
+  }
+  if (payload_host) out.payload_dev = reinterpret_cast<uint32_t*>(next);
+  out.payload_source_dev = payload_source_dev;
+  out.payload_stride = payload_stride;
+  out.capacity = *count;
+  // (the scratch still holds the marks of the count above: same grid, same stream, nothing enqueued in between)
+  hipError_t err = vgt::LaunchSelectEmit(grid, out, ctx->select_ws.data(), ctx->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(indices_host, out.indices_dev, list_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (err == hipSuccess && values_host)
+    err = hipMemcpyAsync(values_host, out.values_dev, list_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (err == hipSuccess && payload_host)
+    err = hipMemcpyAsync(payload_host, out.payload_dev, list_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "select cells");
+  return VGT_HIP_OK;
+}
+
+vgt::SelectGrid MakeSelectGrid(const void* cells_dev, int cell_bytes, const void* labels_dev, int label_stride, int64_t nx,
+                               int64_t ny, int64_t nz, int rule, int class_mask, float threshold)
+{
+  vgt::SelectGrid g;
+  g.cells_dev = cells_dev;
+  g.cell_bytes = cell_bytes;
+  g.labels_dev = labels_dev;
+  g.label_stride = label_stride;
+  g.nx = static_cast<int>(nx);
+  g.ny = static_cast<int>(ny);
+  g.nz = static_cast<int>(nz);
+  g.rule = rule;
+  g.class_mask = class_mask;
+  g.threshold = threshold;
+  return g;
+}
+}  // namespace
+
+int vgt_hip_select_cells_dev(vgt_hip_ctx* ctx, const float* values_dev, const uint32_t* labels_dev, int64_t nx,
+                             int64_t ny, int64_t nz, int rule, int class_mask, float threshold, int32_t* indices_out,
+                             float* values_out, uint32_t* labels_out, int64_t capacity, int64_t* count)
+{
+  const int rc = CheckSelectArguments(ctx, values_dev, labels_dev != nullptr, nx, ny, nz, rule, class_mask, threshold,
+                                      indices_out, labels_out, capacity, count);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const vgt::SelectGrid grid = MakeSelectGrid(values_dev, 4, labels_dev, 4, nx, ny, nz, rule, class_mask, threshold);
+  vgt::SelectOutput out{};
+  out.indices_dev = indices_out;
+  out.values_dev = values_out;
+  out.payload_dev = labels_out;
+  out.payload_source_dev = labels_dev;
+  out.payload_stride = 4;
+  out.capacity = capacity;
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunSelect(ctx, grid, out, count);
+}
+
+int vgt_hip_select_cells(vgt_hip_ctx* ctx, const float* values_host, const uint32_t* labels_host, int64_t nx, int64_t ny,
+                         int64_t nz, int rule, int class_mask, float threshold, int32_t* indices_out, float* values_out,
+                         uint32_t* labels_out, int64_t capacity, int64_t* count)
+{
+  const int rc = CheckSelectArguments(ctx, values_host, labels_host != nullptr, nx, ny, nz, rule, class_mask, threshold,
+                                      indices_out, labels_out, capacity, count);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t n = static_cast<size_t>(nx * ny * nz);
+  // (labels that neither the rule nor a list needs stay on the host)
+  const bool use_labels = labels_host && (rule == VGT_HIP_SELECT_COMPONENT_SURFACE || labels_out);
+  vgt::DeviceTemp buffer;  // values, labels
+  VGT_TRY_HIP(buffer.Allocate(n * (use_labels ? 8 : 4)), "allocate selection inputs");
+  float* const values_dev = buffer.as<float>();
+  uint32_t* const labels_dev = use_labels ? reinterpret_cast<uint32_t*>(buffer.as<char>() + n * 4) : nullptr;
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipError_t err = hipMemcpyAsync(values_dev, values_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (err == hipSuccess && use_labels)
+    err = hipMemcpyAsync(labels_dev, labels_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (err != hipSuccess)
+  {
+    (void)hipStreamSynchronize(ctx->stream);  // (an upload may still be in flight)
+    return FailHip("upload selection inputs", err);
+  }
+  const vgt::SelectGrid grid = MakeSelectGrid(values_dev, 4, labels_dev, 4, nx, ny, nz, rule, class_mask, threshold);
+  const int result = RunSelectToHost(ctx, grid, labels_dev, 4, indices_out, values_out, labels_out, capacity, count);
+  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
+  return result;
+}
+
+int vgt_hip_cells_select(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* labels_dev_or_null, int rule,
+                         int class_mask, int32_t* indices_host, float* occupancy_host, uint32_t* payload_host,
+                         int payload_member, int64_t capacity, int64_t* count)
+{
+  int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  // where the layout keeps its members (include/vgt_hip.h)
+  const int object_id_at = cells->object_id_offset;
+  const int component_at = cells->cell_bytes == 16 ? 8 : (cells->cell_bytes == 8 && object_id_at < 0 ? 4 : -1);
+  const int segment_at = cells->cell_bytes == 16 ? 12 : -1;
+  int payload_at = -1;
+  switch (payload_member)
+  {
+    case VGT_HIP_CELL_MEMBER_NONE:
+      if (payload_host) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a payload buffer without a payload member");
+      break;
+    case VGT_HIP_CELL_MEMBER_OBJECT_ID:
+      payload_at = object_id_at;
+      break;
+    case VGT_HIP_CELL_MEMBER_COMPONENT:
+      payload_at = component_at;
+      break;
+    case VGT_HIP_CELL_MEMBER_SPATIAL_SEGMENT:
+      payload_at = segment_at;
+      break;
+    default:
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown payload member " + std::to_string(payload_member));
+  }
+  if (payload_member != VGT_HIP_CELL_MEMBER_NONE && payload_at < 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "this cell layout does not have the payload member asked for");
+  const bool own_labels = !labels_dev_or_null && component_at >= 0;
+  rc = CheckSelectArguments(ctx, cells, labels_dev_or_null || own_labels, cells->nx, cells->ny, cells->nz, rule,
+                            class_mask, 0.5f, indices_host, nullptr, capacity, count);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* const records = cells->records.as<char>();
+  const vgt::SelectGrid grid =
+      MakeSelectGrid(records, cells->cell_bytes, own_labels ? static_cast<const void*>(records + component_at) : labels_dev_or_null,
+                     own_labels ? cells->cell_bytes : 4, cells->nx, cells->ny, cells->nz, rule, class_mask, 0.5f);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunSelectToHost(ctx, grid, payload_at >= 0 ? records + payload_at : nullptr, cells->cell_bytes, indices_host,
+                         occupancy_host, payload_at >= 0 ? payload_host : nullptr, capacity, count);
 }
 
 /* ------------------------- holes and voids per component ------------------------- */

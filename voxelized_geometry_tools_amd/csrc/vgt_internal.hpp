@@ -275,6 +275,51 @@ hipError_t LaunchFillEnclosed(void* cells_dev, int cell_bytes, int unknown_is_fi
 hipError_t LaunchComponentSurfaceMask(const float* occupancy_dev, const uint32_t* labels_dev, int64_t nx, int64_t ny,
                                       int64_t nz, int component_types, uint8_t* mask_dev, hipStream_t stream);
 
+// block_counts[b] -> exclusive prefix sum in place, *total_dev = the sum (below 2^31): one workgroup, no waiting between
+// workgroups.  The scan of the labelling's root counts, shared with the cell selection.
+hipError_t LaunchScanBlocks(int32_t* block_counts_dev, int64_t blocks, uint32_t* total_dev, hipStream_t stream);
+
+// --- launchers (select_kernels.hip): selected cells as compact ordered lists ---
+// The rules and class bits of include/vgt_hip.h (VGT_HIP_SELECT_*, VGT_HIP_CLASS_*).
+constexpr int kSelectAll = 0;
+constexpr int kSelectSurface26 = 1;
+constexpr int kSelectComponentSurface = 2;
+constexpr int kSelectClassAbove = 1, kSelectClassBelow = 2, kSelectClassEqual = 4, kSelectClassUnordered = 8;
+// cells_dev: records of cell_bytes bytes with the float value first (a plain float grid: 4).  labels_dev: one uint32
+// every label_stride bytes (a plain label grid: 4; a member of the records: cell_bytes), kSelectComponentSurface only.
+// Grids below 2^31 cells.
+struct SelectGrid
+{
+  const void* cells_dev;
+  int cell_bytes;
+  const void* labels_dev;
+  int label_stride;
+  int nx, ny, nz;
+  int rule, class_mask;
+  float threshold;
+};
+// indices_dev receives the linear indices of the selected cells in ascending order; values_dev (or nullptr) their values;
+// payload_dev (or nullptr) the uint32 found every payload_stride bytes from payload_source_dev, at the selected cells.
+struct SelectOutput
+{
+  int32_t* indices_dev;
+  float* values_dev;
+  uint32_t* payload_dev;
+  const void* payload_source_dev;
+  int payload_stride;
+  int64_t capacity;  // entries of each output: at least the number of selected cells
+};
+// Two steps, because the outputs are sized by what the first one counts:
+//   LaunchSelectMark  the bit grid, its block counts and their scan into scratch_dev (SelectScratchBytes bytes: 1 bit per
+//                     voxel + 4 bytes per 1024 voxels); the number of selected cells lies at SelectCountPtr afterwards
+//                     (stream-ordered);
+//   LaunchSelectEmit  the lists, from the scratch of a LaunchSelectMark of the same grid.
+size_t SelectScratchBytes(int64_t num_cells);
+const uint32_t* SelectCountPtr(const void* scratch_dev, int64_t num_cells);
+hipError_t LaunchSelectMark(const SelectGrid& grid, void* scratch_dev, hipStream_t stream);
+hipError_t LaunchSelectEmit(const SelectGrid& grid, const SelectOutput& out, const void* scratch_dev,
+                            hipStream_t stream);
+
 // --- launchers (topology_kernels.hip): holes and voids per component ---
 // One entry per label, the layout of vgt_hip_component_topology_t (include/vgt_hip.h).
 struct ComponentTopologyEntry
