@@ -26,7 +26,10 @@
 //   * Sweep 2 walks the line backwards: the owner of a row is found by comparing the two topmost members at that
 //     row (values along the envelope are unimodal), (Gs - Gt) + 2 q (rt - rs) <= 0 pops.  The distances to the
 //     bounding rows of the other class are running counters fed by the line's sign bits (one word per 32 rows, kept
-//     in the scratch buffer between the sweeps); waves whose 64 lines hold one class only skip that part.
+//     in the scratch buffer between the sweeps); waves whose 64 lines hold one class only skip that part, and a wave with
+//     class changes skips it band by band: where no change touches a band in any lane and the top entry's parabola stays
+//     below the squared distance to the nearest change at both ends of the band, the candidates can decide nothing
+//     (two votes per band; profiles/r7/class_band_skip.md).
 //   * X pass: fused sqrt / resolution / sign / virtual border / min-max; on bands whose inputs are all below 512 the
 //     conversion comes from an exact table in LDS (dense scenes).
 //   * The Y pass of the default pipeline does not read a distance field: its rows come as CLASS RECORDS (pass 1,
@@ -97,6 +100,11 @@ struct RingShape
 };
 constexpr int kFar = 32768;              // "no row of the other class": kFar^2 is above every real squared distance
 static_assert(kWord % kBand == 0 && kBand % 2 == 0, "sizes");
+#ifdef VGT_HOST_EMULATION
+// Full bands of lines with class changes, by the copy of sweep 2's band code they ran (the emulation's drivers read them;
+// product builds count nothing): [0] with candidates after the second vote, [1] without, [2] with candidates after the first.
+uint64_t class_band_tally[3] = {0, 0, 0};
+#endif
 
 
 template <bool kPacked>
@@ -922,10 +930,10 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   // =====================================================================================================
   const bool classes = __builtin_amdgcn_ballot_w64(any_transition != 0u) != 0ull;
   const bool any_empty = __builtin_amdgcn_ballot_w64(D == (4u << kShift)) != 0ull;  // a line without any site
-  // No site on any of the wave's 64 lines and no class change along them (more than half of the Y pass's items on a sparse
-  // scene: the slice holds no voxel whose Z line changes class): every row's result is "no voxel of the other class",
-  // +-infinity by the line's class, and the evaluation is a fill from the sign words.  (The virtual border turns "none" into a finite distance: then the
-  // general evaluation runs.)
+  // No site on any of the wave's 64 lines and no class change along them (a plane of the grid that holds one class: 1.4 % of
+  // the planes of the sparse benchmark scene, every item of an empty or full grid): every row's result is "no voxel of the
+  // other class", +-infinity by the line's class, and the evaluation is a fill from the sign words.  (The virtual border turns
+  // "none" into a finite distance: then the general evaluation runs.)
   bool all_empty = !classes && __builtin_amdgcn_ballot_w64(D != (4u << kShift)) == 0ull;
   if constexpr (kFinal && !kPlain) all_empty = all_empty && !g.add_virtual_border;
   if (all_empty)
@@ -1226,6 +1234,46 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
       };
       bool small_band = false;
       if constexpr (kUseTable) small_band = ((small_bands >> (r0 / kBand)) & 1ull) != 0ull;
+      // A full band of an item with class changes runs the copy WITHOUT the candidates when no lane needs them here:
+      //   * no class change touches the lane's rows of the band or the two rows next to it, so every row's candidate is at
+      //     least delta = min(distance from the band's top row to the other class above, from row r0 to the one below) away;
+      //   * B = max(P(r0), P(r0 + kBand - 1)) <= delta^2, P the parabola of the entry that is the top now.  P is convex and,
+      //     like every entry that is or was on the stack, bounds the envelope from above on the rows still to come:
+      //     best(q) <= B <= delta^2 <= dm(q)^2 on every row of the band, so the candidate changes no result;
+      //   * B < kLimit: the line has a site (a line without any gets its "none" from the candidates copy alone).
+      // Two votes: on a dense scene nearly every band fails the first, which costs a few instructions per BAND.
+      bool without_candidates = false;
+      if (classes && !any_empty && r0 + kBand <= n)
+      {
+        constexpr uint32_t kBandMask = kBand >= 32 ? ~0u : ((1u << (kBand % 32)) - 1u);
+        // bit k: row r0 + k differs from a neighbour (xdn: from the row below it, xup: from the row above it)
+        const uint32_t touched = ((xdn_word | xup_word) >> sub) & kBandMask;
+#ifdef VGT_HOST_EMULATION
+        int ran = 2;
+#endif
+        if (__builtin_amdgcn_ballot_w64(touched != 0u) == 0ull)
+        {
+          // (the group code's start value at row r0 - 1, and dn as it stands: the distance from row r0 + kBand upwards)
+          const uint32_t below = xdn_word & LowBits(sub);
+          const int d = below ? (sub - (31 - __clz(static_cast<int>(below)))) : static_cast<int>(info.y) + sub;
+          const uint32_t delta = static_cast<uint32_t>(min(d, dn) + 1);
+          __builtin_assume(rt >= 0 && rt < 16384);
+          const int qt = r0 + kBand - 1;
+          const int32_t p_first = Mad24Uniform(rt, -2 * r0, Gt) + r0 * r0;
+          const int32_t p_last = Mad24Uniform(rt, -2 * qt, Gt) + qt * qt;
+          const uint32_t B = static_cast<uint32_t>(max(p_first, p_last));
+          const bool needed = static_cast<int>(B >= static_cast<uint32_t>(kLimit)) | static_cast<int>(B > delta * delta);
+          without_candidates = __builtin_amdgcn_ballot_w64(needed) == 0ull;
+          if (without_candidates) dn += kBand;  // (capped below, like the candidates copy's)
+#ifdef VGT_HOST_EMULATION
+          ran = without_candidates ? 1 : 0;
+#endif
+        }
+#ifdef VGT_HOST_EMULATION
+        if (any_transition != 0u) class_band_tally[ran]++;
+#endif
+      }
+      const bool class_rows = classes && !without_candidates;
       if (r0 + kBand > n)
         rows(std::true_type{}, std::true_type{}, std::false_type{});  // (the partial band: one copy, the candidates are "far" without classes)
       else if (small_band)
@@ -1233,13 +1281,13 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
         // (a band of small results has sites in every lane: `any_empty` does not concern it)
         if constexpr (kUseTable)
         {
-          if (classes)
+          if (class_rows)
             rows(std::false_type{}, std::true_type{}, std::true_type{});
           else
             rows(std::false_type{}, std::false_type{}, std::true_type{});
         }
       }
-      else if (classes || any_empty)
+      else if (class_rows || any_empty)
         rows(std::false_type{}, std::true_type{}, std::false_type{});
       else
         rows(std::false_type{}, std::false_type{}, std::false_type{});
