@@ -426,6 +426,70 @@ int vgt_hip_sdf_project_out_of_collision_dev(vgt_hip_ctx* ctx, const float* sdf_
                                              double stepsize_multiplier, int32_t max_iterations, double* position_dev,
                                              uint8_t* has_value_dev, uint8_t* status_dev, int32_t* iterations_dev);
 
+/* N segments a -> b cast through a float occupancy map or a float SDF, one lane per segment: is the segment free, and
+ * if not, which voxel does it hit first and how far along; for an SDF also how close it comes to an obstacle.  The edge
+ * check of a sampling planner, a line-of-sight test, a depth image of a map.  Read-only.
+ * A segment is 6 doubles (a, b) in the frame `grid_from_world` maps from (16 doubles column-major; NULL = the grid
+ * frame: the coordinates are then used as they are, without a multiplication by an identity).  With a transform X,
+ * A = X a and B = X b, each row evaluated as ((m0*x + m4*y) + m8*z) + m12.  Everything is done in double without
+ * contraction, inverse_voxel_size = 1.0 / resolution, grid_size[a] = n[a] * resolution.
+ * Cells examined, in order: the cells the reference's f64 voxelizer walk (S/cpu_pointcloud_voxelization.cpp:208-436,
+ * the walk of vgt_hip_raycast_points_f64) visits for origin A, point B and max_range = +infinity -- the ray is never
+ * clipped and tmax of the slab test starts at +infinity; the origin's index and the in-grid test are taken per
+ * segment; the slab entry with its `t2 > tmax` quirk, the 1e-10 nudge, the walk's index conversion, the tie order
+ * X, then Y, then Z, the `cur[a] == end[a]` break and leaving the walk at the first out-of-grid cell are the walk's.
+ * The in-grid cells of the walk come first, in walk order; the final cell (which the reference marks first) comes
+ * last, if it is in the grid.  No cell appears twice.  So a segment cast through a map that the voxelizer carved sees
+ * exactly the cells the voxelizer would have marked free.
+ * One divergence from the reference's walk: when the origin is outside the grid and tmin + 1e-10 > length (tmin of the
+ * slab test, length = the norm the walk computes), the segment ends before it reaches the grid and examines nothing.
+ * (The reference there walks backwards from the grid's entry point, over cells that are not on the segment.)  A
+ * segment of length zero outside the grid (direction 0 / 0) examines nothing by the same rule.
+ * Predicate (`mode`):
+ *   VGT_HIP_SEGMENT_OCCUPANCY  the field is float occupancy; a cell is a hit when occ > 0.5f || (unknown_is_filled &&
+ *                              occ == 0.5f), the SDF's own predicate.  NaN is never a hit.
+ *   VGT_HIP_SEGMENT_SDF_BELOW  the field is a float SDF; a cell is a hit when (double)value <= threshold, the
+ *                              projection's comparison.  NaN is never a hit, +-infinity compare as they are.
+ * Examination stops at the first hit, unless flags & VGT_HIP_SEGMENT_WALK_THROUGH: then all cells are examined, and
+ * the hit outputs still describe the first hit.
+ * Outputs per segment (`status` is required, every other output may be NULL):
+ *   status (uint8)          0 CLEAR: at least one cell examined, none a hit;  1 HIT;  2 MISSED_GRID: no cell examined;
+ *                           3 INVALID: one of the 6 coordinates is not finite, nothing is examined.  A segment of
+ *                           length zero inside the grid examines exactly its own cell.
+ *   hit_index (int32)       the linear index x*ny*nz + y*nz + z of the first hit, or -1
+ *   cells_examined (int32)  the number of cells examined; without WALK_THROUGH the hit cell is the last of them
+ *   hit_fraction (double)   where the segment A -> B enters the hit cell's box, as a fraction of the segment, in double:
+ *                             lo_a = idx_a * resolution, hi_a = (idx_a + 1) * resolution;
+ *                             for each axis with d_a = B_a - A_a != 0: ta = (lo_a - A_a) / d_a, tb = (hi_a - A_a) / d_a;
+ *                             enter = 0.0, raised by m = min(ta, tb) of each such axis in the order x, y, z
+ *                             (if (m > enter) enter = m);  the result is enter > 1.0 ? 1.0 : enter;  NaN without a hit
+ *   min_value (float), min_index (int32)   SDF mode only (with VGT_HIP_SEGMENT_OCCUPANCY either is an invalid
+ *                           argument): the least non-NaN value among the examined cells and its index, ties to the
+ *                           first cell in examination order; NaN and -1 when no non-NaN value was examined.  With
+ *                           WALK_THROUGH: the clearance of the whole segment at cell centres.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer, a resolution that is not positive and
+ * finite, an unknown mode or flag bit, a NaN threshold in SDF mode, a grid of 2^31 cells or more, a negative extent,
+ * num_segments < 0.  num_segments == 0 and an empty grid succeed and touch nothing. */
+#define VGT_HIP_SEGMENT_OCCUPANCY 0
+#define VGT_HIP_SEGMENT_SDF_BELOW 1
+#define VGT_HIP_SEGMENT_WALK_THROUGH 1u
+#define VGT_HIP_SEGMENT_CLEAR 0
+#define VGT_HIP_SEGMENT_HIT 1
+#define VGT_HIP_SEGMENT_MISSED_GRID 2
+#define VGT_HIP_SEGMENT_INVALID 3
+int vgt_hip_cast_segments(vgt_hip_ctx* ctx, const float* field_host, int64_t nx, int64_t ny, int64_t nz,
+                          double resolution, int32_t mode, int unknown_is_filled, double threshold, uint32_t flags,
+                          const double* grid_from_world, const double* segments_host, int64_t num_segments,
+                          uint8_t* status_host, int32_t* hit_index_host, double* hit_fraction_host,
+                          int32_t* cells_examined_host, float* min_value_host, int32_t* min_index_host);
+/* Same with the field, the segments and the outputs on the device (e.g. straight after vgt_hip_sdf_dev); enqueued on
+ * the context's stream, not blocking.  The transform is a host array. */
+int vgt_hip_cast_segments_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t nx, int64_t ny, int64_t nz,
+                              double resolution, int32_t mode, int unknown_is_filled, double threshold, uint32_t flags,
+                              const double* grid_from_world, const double* segments_dev, int64_t num_segments,
+                              uint8_t* status_dev, int32_t* hit_index_dev, double* hit_fraction_dev,
+                              int32_t* cells_examined_dev, float* min_value_dev, int32_t* min_index_dev);
+
 /* SignedDistanceField::ComputeLocalExtremaMap (I/signed_distance_field.hpp:1205-1231 over :385-541; consumed by
  * TaggedObjectOccupancyComponentMap::UpdateSpatialSegments, S/tagged_object_occupancy_component_map.cpp:775-868):
  * for every voxel the grid-frame location (3 doubles) of the cell its gradient chain ends at -- the chain follows

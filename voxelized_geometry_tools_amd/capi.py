@@ -4,6 +4,7 @@ This is test / bench plumbing: the product is the shared library and the C++ glu
 include/vgt_hip/.  There is no CPU fallback here -- if the library is missing, or no HIP
 device is usable, the calls raise.
 """
+import collections
 import ctypes
 import threading
 import weakref
@@ -75,6 +76,10 @@ SIGNATURES = {
                                                     _p, _p, _p, _p]),
     "vgt_hip_sdf_project_out_of_collision_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _f64, _f64,
                                                         _i32, _p, _p, _p, _p]),
+    "vgt_hip_cast_segments": (_int, [_p, _p, _i64, _i64, _i64, _f64, _i32, _int, _f64, ctypes.c_uint32, _p, _p, _i64,
+                                     _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_cast_segments_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _i32, _int, _f64, ctypes.c_uint32, _p, _p, _i64,
+                                         _p, _p, _p, _p, _p, _p]),
     "vgt_hip_sdf_local_extrema_map": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_sdf_local_extrema_map_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_connected_components": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
@@ -153,6 +158,15 @@ PROJECT_FLAT_GRADIENT = 2
 PROJECT_LEFT_GRID = 3
 PROJECT_ITERATION_LIMIT = 4
 
+# modes, flag and statuses of cast_segments (VGT_HIP_SEGMENT_*)
+SEGMENT_OCCUPANCY = 0
+SEGMENT_SDF_BELOW = 1
+SEGMENT_WALK_THROUGH = 1
+SEGMENT_CLEAR = 0
+SEGMENT_HIT = 1
+SEGMENT_MISSED_GRID = 2
+SEGMENT_INVALID = 3
+
 # selection rules, value classes and cell members of select_cells / Cells.select (VGT_HIP_SELECT_*, VGT_HIP_CLASS_*,
 # VGT_HIP_CELL_MEMBER_*)
 SELECT_ALL = 0
@@ -170,6 +184,10 @@ CELL_MEMBER_SPATIAL_SEGMENT = 3
 # vgt_hip_component_topology_t
 COMPONENT_TOPOLOGY = np.dtype([(name, np.int32) for name in (
     "present", "num_holes", "num_voids", "num_surfaces", "m3", "m5", "m6", "num_surface_vertices")])
+
+
+# what Context.cast_segments returns: one entry per segment; min_value / min_index are None unless asked for
+SegmentCasts = collections.namedtuple("SegmentCasts", "status hit_index hit_fraction cells_examined min_value min_index")
 
 
 class VgtHipError(RuntimeError):
@@ -384,6 +402,40 @@ class Context:
             self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
             _ptr(queries_ptr), int(num_queries), float(minimum_distance), float(stepsize_multiplier),
             int(max_iterations), _ptr(position_ptr), _ptr(has_value_ptr), _ptr(status_ptr), _ptr(iterations_ptr)))
+
+    def cast_segments(self, field, resolution, segments, mode=SEGMENT_OCCUPANCY, unknown_is_filled=True, threshold=0.0,
+                      walk_through=False, grid_from_world=None, with_min=False):
+        """vgt_hip_cast_segments: segments [N, 6] (a, b) through an occupancy map (SEGMENT_OCCUPANCY) or an SDF
+        (SEGMENT_SDF_BELOW, hit = value <= threshold) -> SegmentCasts(status uint8 (SEGMENT_*), hit_index int32,
+        hit_fraction float64, cells_examined int32, min_value float32, min_index int32); the last two only with_min."""
+        f = np.ascontiguousarray(field, dtype=np.float32)
+        seg = np.ascontiguousarray(segments, dtype=np.float64).reshape(-1, 6)
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        n = len(seg)
+        status = np.empty(n, dtype=np.uint8)
+        hit_index = np.empty(n, dtype=np.int32)
+        hit_fraction = np.empty(n, dtype=np.float64)
+        cells_examined = np.empty(n, dtype=np.int32)
+        min_value = np.empty(n, dtype=np.float32) if with_min else None
+        min_index = np.empty(n, dtype=np.int32) if with_min else None
+        check(self._lib.vgt_hip_cast_segments(
+            self.handle, _ptr(f), *f.shape, float(resolution), int(mode), int(bool(unknown_is_filled)), float(threshold),
+            SEGMENT_WALK_THROUGH if walk_through else 0, _ptr(xf), _ptr(seg), n, _ptr(status), _ptr(hit_index),
+            _ptr(hit_fraction), _ptr(cells_examined), _ptr(min_value), _ptr(min_index)))
+        return SegmentCasts(status, hit_index, hit_fraction, cells_examined, min_value, min_index)
+
+    def cast_segments_dev(self, field_ptr, shape, resolution, segments_ptr, num_segments, status_ptr, hit_index_ptr=None,
+                          hit_fraction_ptr=None, cells_examined_ptr=None, min_value_ptr=None, min_index_ptr=None,
+                          mode=SEGMENT_OCCUPANCY, unknown_is_filled=True, threshold=0.0, walk_through=False,
+                          grid_from_world=None):
+        """vgt_hip_cast_segments_dev: field, segments and outputs on the device (the transform is a host array);
+        enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        check(self._lib.vgt_hip_cast_segments_dev(
+            self.handle, _ptr(field_ptr), *[int(c) for c in shape], float(resolution), int(mode),
+            int(bool(unknown_is_filled)), float(threshold), SEGMENT_WALK_THROUGH if walk_through else 0, _ptr(xf),
+            _ptr(segments_ptr), int(num_segments), _ptr(status_ptr), _ptr(hit_index_ptr), _ptr(hit_fraction_ptr),
+            _ptr(cells_examined_ptr), _ptr(min_value_ptr), _ptr(min_index_ptr)))
 
     def sdf_coarse_gradient_dev(self, sdf_ptr, shape, resolution, gradient_ptr, has_value_ptr=None,
                                 enable_edge_gradients=False, rotation=None):

@@ -453,6 +453,46 @@ int CheckProjectionArguments(int64_t nx, int64_t ny, int64_t nz, double resoluti
   return VGT_HIP_OK;
 }
 
+// The checks both segment entry points make before any device work; fills in what the kernel is launched with.
+int CheckSegmentArguments(const vgt_hip_ctx* ctx, const float* field, int64_t nx, int64_t ny, int64_t nz,
+                          double resolution, int32_t mode, int unknown_is_filled, double threshold, uint32_t flags,
+                          const double* grid_from_world, const double* segments, int64_t num_segments,
+                          const uint8_t* status, const float* min_value, const int32_t* min_index,
+                          vgt::SegmentGrid* grid, vgt::SegmentQuery* query)
+{
+  if (!ctx || !field || !status || num_segments < 0 || (num_segments > 0 && !segments))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (nx < 0 || ny < 0 || nz < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must not be negative");
+  if (!(resolution > 0.0) || !std::isfinite(resolution))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Grid must have uniform, positive resolution");
+  // (extent by extent: the product of three int64 extents can overflow)
+  const int64_t most = 0x7fffffffLL;
+  if (nx > most || ny > most || nz > most || (nx > 0 && ny > 0 && nz > 0 && (nx * ny > most || nx * ny * nz > most)))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "segment casts support grids below 2^31 cells");
+  if (mode != VGT_HIP_SEGMENT_OCCUPANCY && mode != VGT_HIP_SEGMENT_SDF_BELOW)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown segment cast mode");
+  if (flags & ~VGT_HIP_SEGMENT_WALK_THROUGH) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown segment cast flag");
+  if (mode == VGT_HIP_SEGMENT_SDF_BELOW && std::isnan(threshold))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "threshold must not be NaN");
+  if (mode == VGT_HIP_SEGMENT_OCCUPANCY && (min_value || min_index))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "min_value and min_index are outputs of the SDF mode");
+  grid->has_xform = grid_from_world ? 1 : 0;
+  for (int k = 0; k < 16; k++) grid->xform[k] = grid_from_world ? grid_from_world[k] : 0.0;
+  grid->voxel_size = resolution;
+  grid->inverse_voxel_size = 1.0 / resolution;
+  const int64_t counts[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; a++)
+  {
+    grid->counts[a] = static_cast<int32_t>(counts[a]);
+    grid->grid_size[a] = static_cast<double>(counts[a]) * resolution;
+  }
+  query->mode = mode == VGT_HIP_SEGMENT_OCCUPANCY ? vgt::kSegmentOccupancy : vgt::kSegmentSdfBelow;
+  query->unknown_is_filled = unknown_is_filled ? 1 : 0;
+  query->threshold = threshold;
+  query->flags = flags;
+  return VGT_HIP_OK;
+}
+
 // Events of the current timing slot (nullptr when no session is active or it is full).
 hipEvent_t* TimingSlot(vgt_hip_ctx* ctx)
 {
@@ -2528,6 +2568,77 @@ int vgt_hip_sdf_project_out_of_collision(vgt_hip_ctx* ctx, const float* sdf_host
   if (err == hipSuccess && status_host) err = hipMemcpyAsync(status_host, status.as<uint8_t>(), q, hipMemcpyDeviceToHost, s);
   if (err == hipSuccess && iterations_host)
     err = hipMemcpyAsync(iterations_host, iterations.as<int32_t>(), q * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_cast_segments_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t nx, int64_t ny, int64_t nz,
+                              double resolution, int32_t mode, int unknown_is_filled, double threshold, uint32_t flags,
+                              const double* grid_from_world, const double* segments_dev, int64_t num_segments,
+                              uint8_t* status_dev, int32_t* hit_index_dev, double* hit_fraction_dev,
+                              int32_t* cells_examined_dev, float* min_value_dev, int32_t* min_index_dev)
+{
+  vgt::SegmentGrid grid;
+  vgt::SegmentQuery query;
+  const int rc = CheckSegmentArguments(ctx, field_dev, nx, ny, nz, resolution, mode, unknown_is_filled, threshold, flags,
+                                       grid_from_world, segments_dev, num_segments, status_dev, min_value_dev,
+                                       min_index_dev, &grid, &query);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_segments == 0 || nx * ny * nz == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  const vgt::SegmentOutputs out{status_dev, hit_index_dev, hit_fraction_dev, cells_examined_dev, min_value_dev,
+                                min_index_dev};
+  VGT_TRY_HIP(vgt::LaunchCastSegments(field_dev, grid, query, segments_dev, num_segments, out, ctx->stream),
+              "cast segments");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_cast_segments(vgt_hip_ctx* ctx, const float* field_host, int64_t nx, int64_t ny, int64_t nz,
+                          double resolution, int32_t mode, int unknown_is_filled, double threshold, uint32_t flags,
+                          const double* grid_from_world, const double* segments_host, int64_t num_segments,
+                          uint8_t* status_host, int32_t* hit_index_host, double* hit_fraction_host,
+                          int32_t* cells_examined_host, float* min_value_host, int32_t* min_index_host)
+{
+  vgt::SegmentGrid grid;
+  vgt::SegmentQuery query;
+  const int rc = CheckSegmentArguments(ctx, field_host, nx, ny, nz, resolution, mode, unknown_is_filled, threshold, flags,
+                                       grid_from_world, segments_host, num_segments, status_host, min_value_host,
+                                       min_index_host, &grid, &query);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_segments == 0 || nx * ny * nz == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "cast segments";
+  const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_segments);
+  vgt::DeviceTemp field, segments, status, hit_index, hit_fraction, cells_examined, min_value, min_index;
+  VGT_TRY_HIP(field.Allocate(n * sizeof(float)), what);
+  VGT_TRY_HIP(segments.Allocate(q * 6 * sizeof(double)), what);
+  VGT_TRY_HIP(status.Allocate(q), what);
+  if (hit_index_host) VGT_TRY_HIP(hit_index.Allocate(q * sizeof(int32_t)), what);
+  if (hit_fraction_host) VGT_TRY_HIP(hit_fraction.Allocate(q * sizeof(double)), what);
+  if (cells_examined_host) VGT_TRY_HIP(cells_examined.Allocate(q * sizeof(int32_t)), what);
+  if (min_value_host) VGT_TRY_HIP(min_value.Allocate(q * sizeof(float)), what);
+  if (min_index_host) VGT_TRY_HIP(min_index.Allocate(q * sizeof(int32_t)), what);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipStream_t s = ctx->stream;
+  hipError_t err = hipMemcpyAsync(field.as<float>(), field_host, n * sizeof(float), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(segments.as<double>(), segments_host, q * 6 * sizeof(double), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess)
+  {
+    const vgt::SegmentOutputs out{status.as<uint8_t>(),       hit_index.as<int32_t>(), hit_fraction.as<double>(),
+                                  cells_examined.as<int32_t>(), min_value.as<float>(),   min_index.as<int32_t>()};
+    err = vgt::LaunchCastSegments(field.as<float>(), grid, query, segments.as<double>(), num_segments, out, s);
+  }
+  const auto fetch = [&](void* host, const vgt::DeviceTemp& dev, size_t bytes) {
+    if (err == hipSuccess && host) err = hipMemcpyAsync(host, dev.as<void>(), bytes, hipMemcpyDeviceToHost, s);
+  };
+  fetch(status_host, status, q);
+  fetch(hit_index_host, hit_index, q * sizeof(int32_t));
+  fetch(hit_fraction_host, hit_fraction, q * sizeof(double));
+  fetch(cells_examined_host, cells_examined, q * sizeof(int32_t));
+  fetch(min_value_host, min_value, q * sizeof(float));
+  fetch(min_index_host, min_index, q * sizeof(int32_t));
   VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
   return VGT_HIP_OK;
 }

@@ -352,6 +352,39 @@ hipError_t LaunchTopologyCountNodes(const TopologyGrid& grid, void* vertex_scrat
 hipError_t LaunchTopologyFromNodes(const TopologyGrid& grid, void* vertex_scratch_dev, int64_t num_nodes,
                                    void* node_scratch_dev, ComponentTopologyEntry* table_dev, hipStream_t stream);
 
+// --- launcher (segment_kernels.hip): segments cast through an occupancy map or an SDF ---
+// Modes, flags, statuses and outputs: include/vgt_hip.h, vgt_hip_cast_segments.  Grids of 1 to 2^31 - 1 cells.
+constexpr int kSegmentOccupancy = 0;
+constexpr int kSegmentSdfBelow = 1;
+struct SegmentGrid
+{
+  double xform[16];  // grid_from_world, column-major; unused unless has_xform
+  int has_xform;     // 0: the segments are in the grid frame and are used as they are
+  double voxel_size, inverse_voxel_size;
+  double grid_size[3];
+  int32_t counts[3];
+};
+struct SegmentQuery
+{
+  int mode;
+  int unknown_is_filled;
+  double threshold;
+  uint32_t flags;
+};
+// status_dev is required, every other output may be nullptr (min_value_dev / min_index_dev: kSegmentSdfBelow only).
+struct SegmentOutputs
+{
+  uint8_t* status_dev;
+  int32_t* hit_index_dev;
+  double* hit_fraction_dev;
+  int32_t* cells_examined_dev;
+  float* min_value_dev;
+  int32_t* min_index_dev;
+};
+hipError_t LaunchCastSegments(const float* field_dev, const SegmentGrid& grid, const SegmentQuery& query,
+                              const double* segments_dev, int64_t num_segments, const SegmentOutputs& out,
+                              hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
