@@ -490,6 +490,46 @@ int vgt_hip_cast_segments_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t 
                               uint8_t* status_dev, int32_t* hit_index_dev, double* hit_fraction_dev,
                               int32_t* cells_examined_dev, float* min_value_dev, int32_t* min_index_dev);
 
+/* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
+ * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the
+ * vector to the obstacle surface, a contact cell for a penetrating point, the partition of free space by nearest object.
+ * The one definition (every entry point below, Python and the C++ layer refer to it):
+ *   filled      exactly the predicate of vgt_hip_sdf_dev: occupancy > 0.5f, or == 0.5f with unknown_is_filled; NaN is
+ *               free, +infinity filled, as that call classes them.  A mask byte is filled when non-zero.
+ *   nearest[c]  (int32) for the cell c = x*ny*nz + y*nz + z: the linear index of a cell of the OTHER class whose centre is
+ *               at minimal Euclidean distance from c's centre; -1 where the grid holds no cell of the other class.
+ *   d2[c]       (int32, optional output) that minimal squared distance in cells, an exact integer; 0x7fffffff goes with
+ *               -1.  sqrt(d2) * resolution, negated in filled cells, is the field of vgt_hip_sdf_dev without a border.
+ *   ties        among equidistant candidates any one may be returned, but the choice is a pure function of the input:
+ *               the same call on the same grid returns the same array (no atomics, nothing depends on launch order).
+ *               As built: the lower z wins on a Z line, then the lower y among the lines' winners, then the lower x.
+ *   border      there is NO virtual border (add_virtual_border of the SDF calls): a border cell has no index.
+ *   limits      1 .. 16384 cells per axis (the SDF entry points' limit) and fewer than 2^31 cells; beyond them, for an
+ *               empty grid, a NULL required pointer or a workspace that is too small: VGT_HIP_ERR_INVALID_ARGUMENT
+ *               before any device work, nothing launched, outputs untouched.
+ * Three separable passes Z, Y, X carry the site instead of the distance; everything that decides a winner is integer
+ * arithmetic (csrc/nearest_kernels.hip).  The workspace holds 6 bytes per voxel (2 after the Z pass, 4 after the Y
+ * pass) plus the line passes' hull stacks, which grow with the axis lengths, not with the volume (at most 131072
+ * lanes in flight and at most 1 GiB: 7 GiB in all at 1024^3).  vgt_hip_nearest_workspace_bytes returns 0 for an empty
+ * or over-limit grid.
+ * vgt_hip_nearest_dev: everything on the device, enqueued on the context's stream, copies nothing, not blocking.
+ * The host-pointer forms are blocking. */
+size_t vgt_hip_nearest_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int vgt_hip_nearest_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t nx, int64_t ny, int64_t nz,
+                        int unknown_is_filled, int32_t* nearest_dev, int32_t* d2_dev_or_null, void* workspace_dev,
+                        size_t workspace_bytes);
+int vgt_hip_nearest_from_occupancy_f32(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx, int64_t ny, int64_t nz,
+                                       int unknown_is_filled, int32_t* nearest_host, int32_t* d2_host_or_null);
+int vgt_hip_nearest_from_mask_u8(vgt_hip_ctx* ctx, const uint8_t* filled_mask_host, int64_t nx, int64_t ny, int64_t nz,
+                                 int32_t* nearest_host, int32_t* d2_host_or_null);
+/* The same for uploaded cell records, with the filled predicate of vgt_hip_cells_sdf: occupancy AND (num_objects == 0
+ * or the object id is listed).  object_host_or_null (uint32 per cell; tagged cell types only): the cell's own object id
+ * where it is filled, elsewhere the id stored at nearest[c], 0 where nearest[c] is -1 -- with every object listed, the
+ * partition of free space by nearest object in one extraction.  Blocking. */
+int vgt_hip_cells_nearest(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* objects_to_use, int64_t num_objects,
+                          int unknown_is_filled, int32_t* nearest_host, int32_t* d2_host_or_null,
+                          uint32_t* object_host_or_null);
+
 /* SignedDistanceField::ComputeLocalExtremaMap (I/signed_distance_field.hpp:1205-1231 over :385-541; consumed by
  * TaggedObjectOccupancyComponentMap::UpdateSpatialSegments, S/tagged_object_occupancy_component_map.cpp:775-868):
  * for every voxel the grid-frame location (3 doubles) of the cell its gradient chain ends at -- the chain follows

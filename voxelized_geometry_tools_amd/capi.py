@@ -80,6 +80,11 @@ SIGNATURES = {
                                      _p, _p, _p, _p, _p, _p]),
     "vgt_hip_cast_segments_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _i32, _int, _f64, ctypes.c_uint32, _p, _p, _i64,
                                          _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
+    "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
+    "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
+    "vgt_hip_nearest_from_mask_u8": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
+    "vgt_hip_cells_nearest": (_int, [_p, _p, _p, _i64, _int, _p, _p, _p]),
     "vgt_hip_sdf_local_extrema_map": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_sdf_local_extrema_map_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p]),
     "vgt_hip_connected_components": (_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
@@ -796,6 +801,35 @@ class Context:
                 int(bool(unknown_is_filled)), int(bool(add_virtual_border)), _ptr(sdf_ptr),
                 _ptr(ws_ptr), ws_bytes, _ptr(minmax_ptr), _ptr(kernel_ms)))
 
+    # ---- nearest cell of the other class (contract: include/vgt_hip.h, vgt_hip_nearest_dev) ----
+    def nearest_from_occupancy(self, occupancy, unknown_is_filled=True, with_d2=False):
+        """vgt_hip_nearest_from_occupancy_f32: int32 [nx, ny, nz] linear index of the nearest cell of the other class
+        (-1: none), or (nearest, d2) with_d2 (int32 squared distance in cells, 0x7fffffff with -1)."""
+        occ = np.ascontiguousarray(occupancy, dtype=np.float32)
+        if occ.ndim != 3:
+            raise ValueError("occupancy must be (nx, ny, nz)")
+        nearest = np.empty(occ.shape, dtype=np.int32)
+        d2 = np.empty(occ.shape, dtype=np.int32) if with_d2 else None
+        check(self._lib.vgt_hip_nearest_from_occupancy_f32(
+            self.handle, _ptr(occ), *occ.shape, int(bool(unknown_is_filled)), _ptr(nearest), _ptr(d2)))
+        return (nearest, d2) if with_d2 else nearest
+
+    def nearest_from_mask(self, mask, with_d2=False):
+        """vgt_hip_nearest_from_mask_u8: as nearest_from_occupancy for one byte per cell, filled = non-zero."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != 3:
+            raise ValueError("mask must be (nx, ny, nz)")
+        nearest = np.empty(m.shape, dtype=np.int32)
+        d2 = np.empty(m.shape, dtype=np.int32) if with_d2 else None
+        check(self._lib.vgt_hip_nearest_from_mask_u8(self.handle, _ptr(m), *m.shape, _ptr(nearest), _ptr(d2)))
+        return (nearest, d2) if with_d2 else nearest
+
+    def nearest_dev(self, occ_ptr, shape, nearest_ptr, ws_ptr, ws_bytes, d2_ptr=None, unknown_is_filled=True):
+        """vgt_hip_nearest_dev: everything on the device, enqueued on the context's stream."""
+        nx, ny, nz = (int(s) for s in shape)
+        check(self._lib.vgt_hip_nearest_dev(self.handle, _ptr(occ_ptr), nx, ny, nz, int(bool(unknown_is_filled)),
+                                            _ptr(nearest_ptr), _ptr(d2_ptr), _ptr(ws_ptr), int(ws_bytes)))
+
     # ---- multi-GPU Z slabs ----
     def sdf_slab_begin(self, occ_ptr, local_shape, z_offset, ws_ptr, ws_bytes, summary_ptr,
                        unknown_is_filled=True, kernel_ms=None):
@@ -863,6 +897,11 @@ def sdf_multi_last_timing():
 
 def sdf_batch_workspace_bytes(batch, shape):
     return int(load().vgt_hip_sdf_batch_workspace_bytes(int(batch), *[int(v) for v in shape]))
+
+
+def nearest_workspace_bytes(shape):
+    """Workspace of Context.nearest_dev; 0 for an empty or over-limit grid."""
+    return int(load().vgt_hip_nearest_workspace_bytes(*[int(s) for s in shape]))
 
 
 def sdf_workspace_bytes(shape, variant=0):
@@ -1066,6 +1105,19 @@ class Cells:
                                           int(bool(add_virtual_border)), _ptr(out), ctypes.byref(lo),
                                           ctypes.byref(hi)))
         return out, float(lo.value), float(hi.value)
+
+    def nearest(self, objects_to_use=(), unknown_is_filled=True, with_d2=False, with_object_ids=False):
+        """vgt_hip_cells_nearest: the nearest cell of the other class under the filled predicate of sdf() -> int32
+        nearest, or (nearest[, d2][, object]) -- object: uint32, the id of the cell itself where it is filled, else of
+        its nearest cell, 0 where there is none."""
+        objs = np.ascontiguousarray(np.asarray(list(objects_to_use), dtype=np.uint32))
+        nearest = np.empty(self.shape, dtype=np.int32)
+        d2 = np.empty(self.shape, dtype=np.int32) if with_d2 else None
+        obj = np.empty(self.shape, dtype=np.uint32) if with_object_ids else None
+        check(self._lib.vgt_hip_cells_nearest(self.ctx.handle, self.handle, _ptr(objs) if objs.size else None, objs.size,
+                                              int(bool(unknown_is_filled)), _ptr(nearest), _ptr(d2), _ptr(obj)))
+        out = (nearest,) + ((d2,) if with_d2 else ()) + ((obj,) if with_object_ids else ())
+        return out if len(out) > 1 else nearest
 
     def separate_object_sdfs(self, resolution, object_ids, unknown_is_filled=True, add_virtual_border=False):
         """MakeSeparateObjectSDFs: {object id: (sdf, min, max)}, all objects in one batched extraction

@@ -3,6 +3,7 @@
 #include "../../include/vgt_hip.h"
 
 #include "vgt_internal.hpp"
+#include "nearest_internal.hpp"
 #include "device_memory.hpp"
 #include "mesh_kernels.hpp"
 #include "edt_crosscheck.hpp"
@@ -1097,6 +1098,63 @@ int SdfQueriesHost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t 
   }
   VGT_TRY_HIP(err, what);
   if (flag) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Window size for fine gradient is too large for SDF");
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+// --- nearest cell of the other class: what the entry points share (templates: outside the C linkage block) ---
+namespace
+{
+// The limits of the nearest-cell transform: the SDF's extent per axis and fewer than 2^31 cells.
+bool NearestShapeWithinLimits(int64_t nx, int64_t ny, int64_t nz)
+{
+  if (nx <= 0 || ny <= 0 || nz <= 0 || nx > vgt::kMaxExtent || ny > vgt::kMaxExtent || nz > vgt::kMaxExtent) return false;
+  return nx * ny * nz <= 0x7fffffffLL;  // (each extent is at most 2^14: the product cannot overflow)
+}
+
+int CheckNearestShape(int64_t nx, int64_t ny, int64_t nz)
+{
+  if (nx <= 0 || ny <= 0 || nz <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must be positive");
+  if (nx > vgt::kMaxExtent || ny > vgt::kMaxExtent || nz > vgt::kMaxExtent)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extent exceeds 16384 voxels on an axis");
+  if (!NearestShapeWithinLimits(nx, ny, nz))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the nearest-cell transform supports grids below 2^31 cells");
+  return VGT_HIP_OK;
+}
+
+vgt::NearestGrid MakeNearestGrid(int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled)
+{
+  return vgt::NearestGrid{static_cast<int32_t>(nx), static_cast<int32_t>(ny), static_cast<int32_t>(nz),
+                          unknown_is_filled ? 1 : 0};
+}
+
+// Upload, the three passes, download: the blocking form of both host-pointer entry points.
+template <typename InT>
+int NearestFromHost(vgt_hip_ctx* ctx, const InT* input_host, int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled,
+                    int32_t* nearest_host, int32_t* d2_host)
+{
+  if (!ctx || !input_host || !nearest_host) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckNearestShape(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "nearest cells";
+  const size_t n = static_cast<size_t>(nx * ny * nz);
+  vgt::DeviceTemp input, nearest, d2, workspace;
+  VGT_TRY_HIP(input.Allocate(n * sizeof(InT)), what);
+  VGT_TRY_HIP(nearest.Allocate(n * sizeof(int32_t)), what);
+  if (d2_host) VGT_TRY_HIP(d2.Allocate(n * sizeof(int32_t)), what);
+  VGT_TRY_HIP(workspace.Allocate(vgt::CarveNearestWorkspace(nx, ny, nz).bytes), what);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipStream_t s = ctx->stream;
+  hipError_t err = hipMemcpyAsync(input.as<InT>(), input_host, n * sizeof(InT), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess)
+    err = vgt::LaunchNearest<InT>(input.as<InT>(), MakeNearestGrid(nx, ny, nz, unknown_is_filled), nearest.as<int32_t>(),
+                                  d2.as<int32_t>(), workspace.as<void>(), s);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(nearest_host, nearest.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  if (err == hipSuccess && d2_host)
+    err = hipMemcpyAsync(d2_host, d2.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
   return VGT_HIP_OK;
 }
 }  // namespace
@@ -2639,6 +2697,98 @@ int vgt_hip_cast_segments(vgt_hip_ctx* ctx, const float* field_host, int64_t nx,
   fetch(cells_examined_host, cells_examined, q * sizeof(int32_t));
   fetch(min_value_host, min_value, q * sizeof(float));
   fetch(min_index_host, min_index, q * sizeof(int32_t));
+  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
+  return VGT_HIP_OK;
+}
+
+/* ---------------------- nearest cell of the other class ---------------------- */
+
+size_t vgt_hip_nearest_workspace_bytes(int64_t nx, int64_t ny, int64_t nz)
+{
+  if (!NearestShapeWithinLimits(nx, ny, nz)) return 0;
+  return vgt::CarveNearestWorkspace(nx, ny, nz).bytes;
+}
+
+int vgt_hip_nearest_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t nx, int64_t ny, int64_t nz,
+                        int unknown_is_filled, int32_t* nearest_dev, int32_t* d2_dev_or_null, void* workspace_dev,
+                        size_t workspace_bytes)
+{
+  if (!ctx || !occupancy_dev || !nearest_dev || !workspace_dev) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckNearestShape(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  if (workspace_bytes < vgt::CarveNearestWorkspace(nx, ny, nz).bytes)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "nearest-cell workspace too small");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(vgt::LaunchNearest<float>(occupancy_dev, MakeNearestGrid(nx, ny, nz, unknown_is_filled), nearest_dev,
+                                        d2_dev_or_null, workspace_dev, ctx->stream),
+              "nearest cells");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_nearest_from_occupancy_f32(vgt_hip_ctx* ctx, const float* occupancy_host, int64_t nx, int64_t ny, int64_t nz,
+                                       int unknown_is_filled, int32_t* nearest_host, int32_t* d2_host_or_null)
+{
+  return NearestFromHost<float>(ctx, occupancy_host, nx, ny, nz, unknown_is_filled, nearest_host, d2_host_or_null);
+}
+
+int vgt_hip_nearest_from_mask_u8(vgt_hip_ctx* ctx, const uint8_t* filled_mask_host, int64_t nx, int64_t ny, int64_t nz,
+                                 int32_t* nearest_host, int32_t* d2_host_or_null)
+{
+  return NearestFromHost<uint8_t>(ctx, filled_mask_host, nx, ny, nz, 0, nearest_host, d2_host_or_null);
+}
+
+int vgt_hip_cells_nearest(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* objects_to_use, int64_t num_objects,
+                          int unknown_is_filled, int32_t* nearest_host, int32_t* d2_host_or_null,
+                          uint32_t* object_host_or_null)
+{
+  int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!nearest_host || num_objects < 0 || (num_objects > 0 && !objects_to_use))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if ((num_objects > 0 || object_host_or_null) && cells->object_id_offset < 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "this cell type carries no object id");
+  rc = CheckNearestShape(cells->nx, cells->ny, cells->nz);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "nearest cells of a tagged map";
+  // (sorted and distinct, as vgt_hip_cells_sdf hands the list to the same predicate kernel)
+  std::vector<uint32_t> objects(objects_to_use, objects_to_use + num_objects);
+  std::sort(objects.begin(), objects.end());
+  objects.erase(std::unique(objects.begin(), objects.end()), objects.end());
+  const int64_t cells_total = cells->nx * cells->ny * cells->nz;
+  const size_t n = static_cast<size_t>(cells_total);
+  vgt::DeviceTemp nearest, d2, object, workspace;
+  VGT_TRY_HIP(nearest.Allocate(n * sizeof(int32_t)), what);
+  if (d2_host_or_null) VGT_TRY_HIP(d2.Allocate(n * sizeof(int32_t)), what);
+  if (object_host_or_null) VGT_TRY_HIP(object.Allocate(n * sizeof(uint32_t)), what);
+  VGT_TRY_HIP(workspace.Allocate(vgt::CarveNearestWorkspace(cells->nx, cells->ny, cells->nz).bytes), what);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  hipStream_t s = ctx->stream;
+  if (objects.size() * sizeof(uint32_t) > cells->objects.bytes())
+  {
+    VGT_TRY_HIP(hipStreamSynchronize(s), "drain before regrowing object list");
+    VGT_TRY_HIP(cells->objects.Reserve(objects.size() * sizeof(uint32_t)), "allocate object list");
+  }
+  hipError_t err = hipSuccess;
+  if (!objects.empty())  // (pageable source: staged when the call returns)
+    err = hipMemcpyAsync(cells->objects.data(), objects.data(), objects.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess)
+    err = vgt::LaunchCellMask(cells->records.as<void>(), cells_total, cells->cell_bytes, cells->object_id_offset,
+                              objects.empty() ? 0 : 1, cells->objects.as<uint32_t>(), static_cast<int>(objects.size()),
+                              unknown_is_filled ? 1 : 0, cells->mask.as<uint8_t>(), s);
+  if (err == hipSuccess)
+    err = vgt::LaunchNearest<uint8_t>(cells->mask.as<uint8_t>(), MakeNearestGrid(cells->nx, cells->ny, cells->nz, 0),
+                                      nearest.as<int32_t>(), d2.as<int32_t>(), workspace.as<void>(), s);
+  if (err == hipSuccess && object_host_or_null)
+    err = vgt::LaunchNearestObjectId(cells->records.as<void>(), cells_total, cells->cell_bytes, cells->object_id_offset,
+                                     cells->mask.as<uint8_t>(), nearest.as<int32_t>(), object.as<uint32_t>(), s);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(nearest_host, nearest.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  if (err == hipSuccess && d2_host_or_null)
+    err = hipMemcpyAsync(d2_host_or_null, d2.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  if (err == hipSuccess && object_host_or_null)
+    err = hipMemcpyAsync(object_host_or_null, object.as<void>(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
   return VGT_HIP_OK;
 }
