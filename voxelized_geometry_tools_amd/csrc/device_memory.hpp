@@ -10,8 +10,8 @@
 
 namespace vgt
 {
-// One hipMalloc that lives as long as its scope: the temporaries of a host-pointer entry point (declared BEFORE the
-// context's mutex is taken, so that they are freed after it has been dropped) and the fixed buffers of a handle.
+// One hipMalloc that lives as long as its scope: the fixed buffers of a handle, the temporaries of vgt_hipx_multi.hip,
+// and the one block of a host-pointer entry point (host_staging.hpp, which frees it after the context's mutex is dropped).
 class DeviceTemp
 {
 public:

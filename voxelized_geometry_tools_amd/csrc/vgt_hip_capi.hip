@@ -5,6 +5,7 @@
 #include "vgt_internal.hpp"
 #include "nearest_internal.hpp"
 #include "device_memory.hpp"
+#include "host_staging.hpp"
 #include "mesh_kernels.hpp"
 #include "edt_crosscheck.hpp"
 #include "host_pages.hpp"
@@ -195,6 +196,8 @@ void ReleaseChild(vgt_hip_ctx* ctx, int device)
     if (vgt_err_ != hipSuccess) return FailHip(what, vgt_err_); \
   } while (0)
 
+int HipResult(const char* what, hipError_t err) { return err == hipSuccess ? VGT_HIP_OK : FailHip(what, err); }
+
 size_t AlignUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Handle buffers come from / go back to the context's pool (at most kPoolLimit bytes are kept).
@@ -242,6 +245,25 @@ hipError_t DrainKeepingFirst(hipStream_t s, hipError_t err)
 {
   const hipError_t sync = hipStreamSynchronize(s);
   return err == hipSuccess ? sync : err;
+}
+
+// Waits for `launched` and for one small value that it left on the device; *value is on the caller's stack.
+template <typename T>
+hipError_t ReadBack(hipStream_t s, hipError_t launched, T* value, const void* value_dev)
+{
+  if (launched == hipSuccess) launched = hipMemcpyAsync(value, value_dev, sizeof(T), hipMemcpyDeviceToHost, s);
+  return DrainKeepingFirst(s, launched);
+}
+
+// A cached buffer that is too small for `need` is regrown (to `grow_to` bytes where the caller wants headroom), once the
+// work on `s` that may still use it is done.
+int GrowCache(hipStream_t s, vgt::DeviceCache* cache, size_t need, const char* drain_what, const char* allocate_what,
+              size_t grow_to = 0)
+{
+  if (need <= cache->bytes()) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipStreamSynchronize(s), drain_what);
+  VGT_TRY_HIP(cache->Reserve(grow_to ? grow_to : need), allocate_what);
+  return VGT_HIP_OK;
 }
 
 void FreeCachedSdfBuffers(vgt_hip_ctx* ctx)
@@ -998,13 +1020,10 @@ int UploadAndRun(vgt_hip_ctx* ctx, const void* host, size_t bytes, size_t scratc
   }
   // staging copy of the cloud, followed by the kernel's scratch (256-byte aligned)
   const size_t scratch_at = AlignUp(bytes, 256);
-  if (lane.stage.bytes() < scratch_at + scratch_bytes)
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(lane.stream), "drain before regrowing staging buffer");
-    VGT_TRY_HIP(lane.stage.Release(), "free staging buffer");
-    const size_t total = scratch_at + scratch_bytes;
-    VGT_TRY_HIP(lane.stage.Reserve(AlignUp(total + total / 4, 1 << 20)), "allocate staging buffer");
-  }
+  const size_t total = scratch_at + scratch_bytes;
+  const int grown = GrowCache(lane.stream, &lane.stage, total, "drain before regrowing staging buffer",
+                              "allocate staging buffer", AlignUp(total + total / 4, 1 << 20));
+  if (grown != VGT_HIP_OK) return grown;
   char* const stage = lane.stage.as<char>();
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
@@ -1069,34 +1088,19 @@ int SdfQueriesHost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t 
   if (num_queries == 0) return VGT_HIP_OK;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_queries);
-  vgt::DeviceTemp sdf, queries, out, has, flag_word;
-  VGT_TRY_HIP(sdf.Allocate(n * sizeof(float)), what);
-  VGT_TRY_HIP(queries.Allocate(q * 3 * sizeof(double)), what);
-  VGT_TRY_HIP(out.Allocate(q * out_doubles * sizeof(double)), what);
-  VGT_TRY_HIP(has.Allocate(q), what);
-  VGT_TRY_HIP(flag_word.Allocate(256), what);
-  float* const sdf_dev = sdf.as<float>();
-  double* const queries_dev = queries.as<double>();
-  double* const out_dev = out.as<double>();
-  uint8_t* const has_dev = has.as<uint8_t>();
-  uint32_t* const flag_dev = flag_word.as<uint32_t>();
+  vgt::HostStaging staging;
+  const auto sdf = staging.In(sdf_host, n);
+  const auto queries = staging.In(query_xyz_host, q * 3);
+  const auto out = staging.Out(out_host, q * out_doubles);
+  const auto has = staging.Out(has_value_host, q);
+  const auto flag_word = staging.Scratch<uint32_t>(256);
   uint32_t flag = 0;
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    hipStream_t s = ctx->stream;
-    err = hipMemcpyAsync(sdf_dev, sdf_host, n * sizeof(float), hipMemcpyHostToDevice, s);
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(queries_dev, query_xyz_host, q * 3 * sizeof(double), hipMemcpyHostToDevice, s);
-    if (err == hipSuccess) err = hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), s);
-    if (err == hipSuccess) err = run(sdf_dev, queries_dev, out_dev, has_dev, flag_dev, s);
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(out_host, out_dev, q * out_doubles * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (err == hipSuccess && has_value_host) err = hipMemcpyAsync(has_value_host, has_dev, q, hipMemcpyDeviceToHost, s);
-    if (err == hipSuccess) err = hipMemcpyAsync(&flag, flag_dev, sizeof(flag), hipMemcpyDeviceToHost, s);
-    err = DrainKeepingFirst(s, err);
-  }
-  VGT_TRY_HIP(err, what);
+  const int result = staging.Run(*ctx, what, FailHip, [&](hipStream_t s) {
+    VGT_TRY_HIP(hipMemsetAsync(flag_word.dev(), 0, sizeof(uint32_t), s), what);
+    VGT_TRY_HIP(run(sdf.dev(), queries.dev(), out.dev(), has.dev(), flag_word.dev(), s), what);
+    return HipResult(what, hipMemcpyAsync(&flag, flag_word.dev(), sizeof(flag), hipMemcpyDeviceToHost, s));
+  });
+  if (result != VGT_HIP_OK) return result;
   if (flag) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Window size for fine gradient is too large for SDF");
   return VGT_HIP_OK;
 }
@@ -1139,23 +1143,15 @@ int NearestFromHost(vgt_hip_ctx* ctx, const InT* input_host, int64_t nx, int64_t
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const char* what = "nearest cells";
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  vgt::DeviceTemp input, nearest, d2, workspace;
-  VGT_TRY_HIP(input.Allocate(n * sizeof(InT)), what);
-  VGT_TRY_HIP(nearest.Allocate(n * sizeof(int32_t)), what);
-  if (d2_host) VGT_TRY_HIP(d2.Allocate(n * sizeof(int32_t)), what);
-  VGT_TRY_HIP(workspace.Allocate(vgt::CarveNearestWorkspace(nx, ny, nz).bytes), what);
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipStream_t s = ctx->stream;
-  hipError_t err = hipMemcpyAsync(input.as<InT>(), input_host, n * sizeof(InT), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess)
-    err = vgt::LaunchNearest<InT>(input.as<InT>(), MakeNearestGrid(nx, ny, nz, unknown_is_filled), nearest.as<int32_t>(),
-                                  d2.as<int32_t>(), workspace.as<void>(), s);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(nearest_host, nearest.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  if (err == hipSuccess && d2_host)
-    err = hipMemcpyAsync(d2_host, d2.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto input = staging.In(input_host, n);
+  const auto nearest = staging.Out(nearest_host, n);
+  const auto d2 = staging.Out(d2_host, n);
+  const auto workspace = staging.Scratch(vgt::CarveNearestWorkspace(nx, ny, nz).bytes);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t s) {
+    return HipResult(what, vgt::LaunchNearest<InT>(input.dev(), MakeNearestGrid(nx, ny, nz, unknown_is_filled),
+                                                   nearest.dev(), d2.dev(), workspace.dev(), s));
+  });
 }
 }  // namespace
 
@@ -1325,16 +1321,13 @@ int vgt_hip_debug_finalize_check(vgt_hip_ctx* ctx, int64_t first_d2, int64_t cou
       first_d2 + count > (int64_t{1} << 31))
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "invalid finalize-check range");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  vgt::DeviceTemp result_dev;
-  VGT_TRY_HIP(result_dev.Allocate(2 * sizeof(unsigned long long)), "allocate check result");
-  unsigned long long* const result = result_dev.as<unsigned long long>();
-  const unsigned long long init[2] = {0ull, ~0ull};
-  hipError_t err = hipMemcpyAsync(result, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess) err = vgt::LaunchFinalizeCheck(first_d2, count, resolution, result, ctx->stream);
   unsigned long long host[2] = {0ull, ~0ull};
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(host, result, sizeof(host), hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "finalize check");
+  vgt::HostStaging staging;
+  const auto result = staging.InOut(host, 2);
+  const int rc = staging.Run(*ctx, "finalize check", FailHip, [&](hipStream_t s) {
+    return HipResult("finalize check", vgt::LaunchFinalizeCheck(first_d2, count, resolution, result.dev(), s));
+  });
+  if (rc != VGT_HIP_OK) return rc;
   *mismatches = host[0];
   *first_mismatch = host[1];
   return VGT_HIP_OK;
@@ -1486,11 +1479,9 @@ int vgt_hip_raycast_points_f32_dev(vgt_hip_ctx* ctx, vgt_hip_grids* grids, size_
   std::lock_guard<std::mutex> lock(ctx->mutex);
   // stream order protects the scratch: the next call's kernels queue behind this one's
   const size_t scratch_bytes = vgt::RaycastScratchBytes(num_points);
-  if (scratch_bytes > ctx->ray_scratch.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing raycast scratch");
-    VGT_TRY_HIP(ctx->ray_scratch.Reserve(scratch_bytes + scratch_bytes / 4), "allocate raycast scratch");
-  }
+  const int grown = GrowCache(ctx->stream, &ctx->ray_scratch, scratch_bytes, "drain before regrowing raycast scratch",
+                              "allocate raycast scratch", scratch_bytes + scratch_bytes / 4);
+  if (grown != VGT_HIP_OK) return grown;
   VGT_TRY_HIP(vgt::LaunchRaycastF32(points_xyz_dev, num_points, 3, g, tracking, ctx->raycast_threads,
                                     ctx->ray_scratch.data(), ctx->ray_scratch.bytes(), ctx->stream),
               "Failed to dispatch raycast kernel");
@@ -2245,11 +2236,9 @@ int vgt_hip_cells_sdf(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* ob
   std::sort(objects.begin(), objects.end());
   objects.erase(std::unique(objects.begin(), objects.end()), objects.end());
   std::lock_guard<std::mutex> lock(ctx->mutex);
-  if (objects.size() * sizeof(uint32_t) > cells->objects.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing object list");
-    VGT_TRY_HIP(cells->objects.Reserve(objects.size() * sizeof(uint32_t)), "allocate object list");
-  }
+  rc = GrowCache(ctx->stream, &cells->objects, objects.size() * sizeof(uint32_t), "drain before regrowing object list",
+                 "allocate object list");
+  if (rc != VGT_HIP_OK) return rc;
   if (!objects.empty())
   {
     VGT_TRY_HIP(hipMemcpyAsync(cells->objects.data(), objects.data(), objects.size() * sizeof(uint32_t),
@@ -2506,21 +2495,15 @@ int vgt_hip_sdf_coarse_gradient(vgt_hip_ctx* ctx, const float* sdf_host, int64_t
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  vgt::DeviceTemp sdf_dev, grad_dev, has_dev;
-  VGT_TRY_HIP(sdf_dev.Allocate(n * sizeof(float)), "coarse gradient");
-  VGT_TRY_HIP(grad_dev.Allocate(n * 3 * sizeof(double)), "coarse gradient");
-  if (has_value_host) VGT_TRY_HIP(has_dev.Allocate(n), "coarse gradient");
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipError_t err = hipMemcpyAsync(sdf_dev.as<float>(), sdf_host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess)
-    err = vgt::LaunchCoarseGradient(sdf_dev.as<float>(), nx, ny, nz, resolution, enable_edge_gradients ? 1 : 0, rotation,
-                                    grad_dev.as<double>(), has_dev.as<uint8_t>(), ctx->stream);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(gradient_host, grad_dev.as<void>(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (err == hipSuccess && has_value_host)
-    err = hipMemcpyAsync(has_value_host, has_dev.as<uint8_t>(), n, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "coarse gradient");
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto sdf = staging.In(sdf_host, n);
+  const auto gradient = staging.Out(gradient_host, n * 3);
+  const auto has = staging.Out(has_value_host, n);
+  return staging.Run(*ctx, "coarse gradient", FailHip, [&](hipStream_t s) {
+    return HipResult("coarse gradient",
+                     vgt::LaunchCoarseGradient(sdf.dev(), nx, ny, nz, resolution, enable_edge_gradients ? 1 : 0, rotation,
+                                               gradient.dev(), has.dev(), s));
+  });
 }
 
 int vgt_hip_sdf_estimate_distance_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
@@ -2602,32 +2585,19 @@ int vgt_hip_sdf_project_out_of_collision(vgt_hip_ctx* ctx, const float* sdf_host
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const char* what = "project out of collision";
   const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_queries);
-  vgt::DeviceTemp sdf, queries, position, has, status, iterations;
-  VGT_TRY_HIP(sdf.Allocate(n * sizeof(float)), what);
-  VGT_TRY_HIP(queries.Allocate(q * 3 * sizeof(double)), what);
-  VGT_TRY_HIP(position.Allocate(q * 3 * sizeof(double)), what);
-  if (has_value_host) VGT_TRY_HIP(has.Allocate(q), what);
-  if (status_host) VGT_TRY_HIP(status.Allocate(q), what);
-  if (iterations_host) VGT_TRY_HIP(iterations.Allocate(q * sizeof(int32_t)), what);
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipStream_t s = ctx->stream;
-  hipError_t err = hipMemcpyAsync(sdf.as<float>(), sdf_host, n * sizeof(float), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(queries.as<double>(), query_xyz_host, q * 3 * sizeof(double), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess)
-    err = vgt::LaunchProjectOutOfCollision(sdf.as<float>(), nx, ny, nz, resolution, grid_from_world, rotation,
-                                           queries.as<double>(), num_queries, minimum_distance, stepsize_multiplier,
-                                           max_iterations, position.as<double>(), has.as<uint8_t>(), status.as<uint8_t>(),
-                                           iterations.as<int32_t>(), s);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(position_host, position.as<double>(), q * 3 * sizeof(double), hipMemcpyDeviceToHost, s);
-  if (err == hipSuccess && has_value_host)
-    err = hipMemcpyAsync(has_value_host, has.as<uint8_t>(), q, hipMemcpyDeviceToHost, s);
-  if (err == hipSuccess && status_host) err = hipMemcpyAsync(status_host, status.as<uint8_t>(), q, hipMemcpyDeviceToHost, s);
-  if (err == hipSuccess && iterations_host)
-    err = hipMemcpyAsync(iterations_host, iterations.as<int32_t>(), q * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto sdf = staging.In(sdf_host, n);
+  const auto queries = staging.In(query_xyz_host, q * 3);
+  const auto position = staging.Out(position_host, q * 3);
+  const auto has = staging.Out(has_value_host, q);
+  const auto status = staging.Out(status_host, q);
+  const auto iterations = staging.Out(iterations_host, q);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t s) {
+    return HipResult(what, vgt::LaunchProjectOutOfCollision(
+                               sdf.dev(), nx, ny, nz, resolution, grid_from_world, rotation, queries.dev(), num_queries,
+                               minimum_distance, stepsize_multiplier, max_iterations, position.dev(), has.dev(),
+                               status.dev(), iterations.dev(), s));
+  });
 }
 
 int vgt_hip_cast_segments_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t nx, int64_t ny, int64_t nz,
@@ -2668,37 +2638,20 @@ int vgt_hip_cast_segments(vgt_hip_ctx* ctx, const float* field_host, int64_t nx,
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const char* what = "cast segments";
   const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_segments);
-  vgt::DeviceTemp field, segments, status, hit_index, hit_fraction, cells_examined, min_value, min_index;
-  VGT_TRY_HIP(field.Allocate(n * sizeof(float)), what);
-  VGT_TRY_HIP(segments.Allocate(q * 6 * sizeof(double)), what);
-  VGT_TRY_HIP(status.Allocate(q), what);
-  if (hit_index_host) VGT_TRY_HIP(hit_index.Allocate(q * sizeof(int32_t)), what);
-  if (hit_fraction_host) VGT_TRY_HIP(hit_fraction.Allocate(q * sizeof(double)), what);
-  if (cells_examined_host) VGT_TRY_HIP(cells_examined.Allocate(q * sizeof(int32_t)), what);
-  if (min_value_host) VGT_TRY_HIP(min_value.Allocate(q * sizeof(float)), what);
-  if (min_index_host) VGT_TRY_HIP(min_index.Allocate(q * sizeof(int32_t)), what);
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipStream_t s = ctx->stream;
-  hipError_t err = hipMemcpyAsync(field.as<float>(), field_host, n * sizeof(float), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(segments.as<double>(), segments_host, q * 6 * sizeof(double), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess)
-  {
-    const vgt::SegmentOutputs out{status.as<uint8_t>(),       hit_index.as<int32_t>(), hit_fraction.as<double>(),
-                                  cells_examined.as<int32_t>(), min_value.as<float>(),   min_index.as<int32_t>()};
-    err = vgt::LaunchCastSegments(field.as<float>(), grid, query, segments.as<double>(), num_segments, out, s);
-  }
-  const auto fetch = [&](void* host, const vgt::DeviceTemp& dev, size_t bytes) {
-    if (err == hipSuccess && host) err = hipMemcpyAsync(host, dev.as<void>(), bytes, hipMemcpyDeviceToHost, s);
-  };
-  fetch(status_host, status, q);
-  fetch(hit_index_host, hit_index, q * sizeof(int32_t));
-  fetch(hit_fraction_host, hit_fraction, q * sizeof(double));
-  fetch(cells_examined_host, cells_examined, q * sizeof(int32_t));
-  fetch(min_value_host, min_value, q * sizeof(float));
-  fetch(min_index_host, min_index, q * sizeof(int32_t));
-  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto field = staging.In(field_host, n);
+  const auto segments = staging.In(segments_host, q * 6);
+  const auto status = staging.Out(status_host, q);
+  const auto hit_index = staging.Out(hit_index_host, q);
+  const auto hit_fraction = staging.Out(hit_fraction_host, q);
+  const auto cells_examined = staging.Out(cells_examined_host, q);
+  const auto min_value = staging.Out(min_value_host, q);
+  const auto min_index = staging.Out(min_index_host, q);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t s) {
+    const vgt::SegmentOutputs out{status.dev(),         hit_index.dev(), hit_fraction.dev(),
+                                  cells_examined.dev(), min_value.dev(), min_index.dev()};
+    return HipResult(what, vgt::LaunchCastSegments(field.dev(), grid, query, segments.dev(), num_segments, out, s));
+  });
 }
 
 /* ---------------------- nearest cell of the other class ---------------------- */
@@ -2758,39 +2711,32 @@ int vgt_hip_cells_nearest(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t
   objects.erase(std::unique(objects.begin(), objects.end()), objects.end());
   const int64_t cells_total = cells->nx * cells->ny * cells->nz;
   const size_t n = static_cast<size_t>(cells_total);
-  vgt::DeviceTemp nearest, d2, object, workspace;
-  VGT_TRY_HIP(nearest.Allocate(n * sizeof(int32_t)), what);
-  if (d2_host_or_null) VGT_TRY_HIP(d2.Allocate(n * sizeof(int32_t)), what);
-  if (object_host_or_null) VGT_TRY_HIP(object.Allocate(n * sizeof(uint32_t)), what);
-  VGT_TRY_HIP(workspace.Allocate(vgt::CarveNearestWorkspace(cells->nx, cells->ny, cells->nz).bytes), what);
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipStream_t s = ctx->stream;
-  if (objects.size() * sizeof(uint32_t) > cells->objects.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(s), "drain before regrowing object list");
-    VGT_TRY_HIP(cells->objects.Reserve(objects.size() * sizeof(uint32_t)), "allocate object list");
-  }
-  hipError_t err = hipSuccess;
-  if (!objects.empty())  // (pageable source: staged when the call returns)
-    err = hipMemcpyAsync(cells->objects.data(), objects.data(), objects.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess)
-    err = vgt::LaunchCellMask(cells->records.as<void>(), cells_total, cells->cell_bytes, cells->object_id_offset,
-                              objects.empty() ? 0 : 1, cells->objects.as<uint32_t>(), static_cast<int>(objects.size()),
-                              unknown_is_filled ? 1 : 0, cells->mask.as<uint8_t>(), s);
-  if (err == hipSuccess)
-    err = vgt::LaunchNearest<uint8_t>(cells->mask.as<uint8_t>(), MakeNearestGrid(cells->nx, cells->ny, cells->nz, 0),
-                                      nearest.as<int32_t>(), d2.as<int32_t>(), workspace.as<void>(), s);
-  if (err == hipSuccess && object_host_or_null)
-    err = vgt::LaunchNearestObjectId(cells->records.as<void>(), cells_total, cells->cell_bytes, cells->object_id_offset,
-                                     cells->mask.as<uint8_t>(), nearest.as<int32_t>(), object.as<uint32_t>(), s);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(nearest_host, nearest.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  if (err == hipSuccess && d2_host_or_null)
-    err = hipMemcpyAsync(d2_host_or_null, d2.as<void>(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  if (err == hipSuccess && object_host_or_null)
-    err = hipMemcpyAsync(object_host_or_null, object.as<void>(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-  VGT_TRY_HIP(DrainKeepingFirst(s, err), what);
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto nearest = staging.Out(nearest_host, n);
+  const auto d2 = staging.Out(d2_host_or_null, n);
+  const auto object = staging.Out(object_host_or_null, n);
+  const auto workspace = staging.Scratch(vgt::CarveNearestWorkspace(cells->nx, cells->ny, cells->nz).bytes);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t s) -> int {
+    const int grown = GrowCache(s, &cells->objects, objects.size() * sizeof(uint32_t),
+                                "drain before regrowing object list", "allocate object list");
+    if (grown != VGT_HIP_OK) return grown;
+    if (!objects.empty())  // (pageable source: staged when the call returns)
+      VGT_TRY_HIP(hipMemcpyAsync(cells->objects.data(), objects.data(), objects.size() * sizeof(uint32_t),
+                                 hipMemcpyHostToDevice, s),
+                  what);
+    VGT_TRY_HIP(vgt::LaunchCellMask(cells->records.as<void>(), cells_total, cells->cell_bytes, cells->object_id_offset,
+                                    objects.empty() ? 0 : 1, cells->objects.as<uint32_t>(),
+                                    static_cast<int>(objects.size()), unknown_is_filled ? 1 : 0,
+                                    cells->mask.as<uint8_t>(), s),
+                what);
+    VGT_TRY_HIP(vgt::LaunchNearest<uint8_t>(cells->mask.as<uint8_t>(), MakeNearestGrid(cells->nx, cells->ny, cells->nz, 0),
+                                            nearest.dev(), d2.dev(), workspace.dev(), s),
+                what);
+    if (!object_host_or_null) return VGT_HIP_OK;
+    return HipResult(what, vgt::LaunchNearestObjectId(cells->records.as<void>(), cells_total, cells->cell_bytes,
+                                                      cells->object_id_offset, cells->mask.as<uint8_t>(),
+                                                      nearest.dev(), object.dev(), s));
+  });
 }
 
 int vgt_hip_sdf_local_extrema_map_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
@@ -2817,29 +2763,18 @@ int vgt_hip_sdf_local_extrema_map(vgt_hip_ctx* ctx, const float* sdf_host, int64
   if (!ctx || !sdf_host || !extrema_host) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const int rc = CheckSdfShape(nx, ny, nz, resolution);
   if (rc != VGT_HIP_OK) return rc;
+  if (nx * ny * nz >= 0x7fffffffLL)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the local extrema map supports grids below 2^31 cells");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  vgt::DeviceTemp sdf_dev, out_dev;
-  VGT_TRY_HIP(sdf_dev.Allocate(n * sizeof(float)), "local extrema map");
-  VGT_TRY_HIP(out_dev.Allocate(n * 3 * sizeof(double)), "local extrema map");
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(sdf_dev.as<float>(), sdf_host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-  }
-  int result = VGT_HIP_OK;
-  if (err == hipSuccess)
-    result = vgt_hip_sdf_local_extrema_map_dev(ctx, sdf_dev.as<float>(), nx, ny, nz, resolution, rotation,
-                                               out_dev.as<double>());
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    if (err == hipSuccess && result == VGT_HIP_OK)
-      err = hipMemcpyAsync(extrema_host, out_dev.as<void>(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    err = DrainKeepingFirst(ctx->stream, err);  // (whatever happened: the upload may still be in flight)
-  }
-  if (result != VGT_HIP_OK) return result;
-  VGT_TRY_HIP(err, "local extrema map");
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto sdf = staging.In(sdf_host, n);
+  const auto extrema = staging.Out(extrema_host, n * 3);
+  const auto scratch = staging.Scratch(vgt::LocalExtremaScratchBytes(nx * ny * nz));
+  return staging.Run(*ctx, "local extrema map", FailHip, [&](hipStream_t s) {
+    return HipResult("local extrema map", vgt::LaunchLocalExtremaMap(sdf.dev(), nx, ny, nz, resolution, rotation,
+                                                                     extrema.dev(), scratch.dev(), s));
+  });
 }
 
 /* ------------------- connected components and spatial segments ------------------- */
@@ -2879,38 +2814,18 @@ int RunLabelling(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int ob
 {
   const int64_t n = nx * ny * nz;
   const size_t need = vgt::ComponentScratchBytes(n);
-  if (need > ctx->component_ws.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the labelling scratch");
-    VGT_TRY_HIP(ctx->component_ws.Reserve(need), "allocate labelling scratch");
-  }
+  const int grown = GrowCache(ctx->stream, &ctx->component_ws, need, "drain before regrowing the labelling scratch",
+                              "allocate labelling scratch");
+  if (grown != VGT_HIP_OK) return grown;
   void* const scratch = ctx->component_ws.data();
-  hipError_t err = vgt::LaunchLabelComponents(cells_dev, cell_bytes, object_id_offset, mode, extrema_dev,
-                                              connected_threshold, nx, ny, nz, labels_dev, scratch, ctx->stream);
+  const hipError_t err = vgt::LaunchLabelComponents(cells_dev, cell_bytes, object_id_offset, mode, extrema_dev,
+                                                    connected_threshold, nx, ny, nz, labels_dev, scratch, ctx->stream);
   uint32_t count = 0;
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(&count, vgt::ComponentCountPtr(scratch, n), sizeof(count), hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "label components");  // (`count` is on this stack)
+  VGT_TRY_HIP(ReadBack(ctx->stream, err, &count, vgt::ComponentCountPtr(scratch, n)), "label components");
   *num_components = count;
   return VGT_HIP_OK;
 }
 
-// RunLabelling into a temporary device grid, then the labels to the host.
-int LabelToHost(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int object_id_offset, int mode,
-                const double* extrema_dev, double connected_threshold, int64_t nx, int64_t ny, int64_t nz,
-                uint32_t* labels_host, uint32_t* num_components)
-{
-  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(uint32_t);
-  vgt::DeviceTemp labels_dev;
-  VGT_TRY_HIP(labels_dev.Allocate(bytes), "allocate labels");
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  const int rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, extrema_dev, connected_threshold, nx,
-                              ny, nz, labels_dev.as<uint32_t>(), num_components);
-  if (rc != VGT_HIP_OK) return rc;  // (it has waited for whatever it enqueued)
-  const hipError_t err = hipMemcpyAsync(labels_host, labels_dev.as<void>(), bytes, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "copy labels to the host");
-  return VGT_HIP_OK;
-}
 }  // namespace
 
 int vgt_hip_connected_components_dev(vgt_hip_ctx* ctx, const float* occupancy_dev, int64_t nx, int64_t ny, int64_t nz,
@@ -2934,22 +2849,14 @@ int vgt_hip_connected_components(vgt_hip_ctx* ctx, const float* occupancy_host, 
   if (!ctx || !occupancy_host || !labels_host || !num_components)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(float);
-  vgt::DeviceTemp occupancy_dev;
-  VGT_TRY_HIP(occupancy_dev.Allocate(bytes), "allocate occupancy");
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(occupancy_dev.as<void>(), occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
-  }
-  int result;
-  if (err == hipSuccess)
-    result = LabelToHost(ctx, occupancy_dev.as<void>(), 4, -1, vgt::kComponentClasses, nullptr, 0.0, nx, ny, nz,
-                         labels_host, num_components);
-  else
-    result = FailHip("upload occupancy", err);
-  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
-  return result;
+  const size_t n = static_cast<size_t>(nx * ny * nz);
+  vgt::HostStaging staging;
+  const auto occupancy = staging.In(occupancy_host, n);
+  const auto labels = staging.Out(labels_host, n);
+  return staging.Run(*ctx, "connected components", FailHip, [&](hipStream_t) {
+    return RunLabelling(ctx, occupancy.dev(), 4, -1, vgt::kComponentClasses, nullptr, 0.0, nx, ny, nz, labels.dev(),
+                        num_components);
+  });
 }
 
 /* --------------------------------- enclosed space --------------------------------- */
@@ -2971,22 +2878,18 @@ int RunFillEnclosed(vgt_hip_ctx* ctx, void* cells_dev, int cell_bytes, int64_t n
                     int unknown_is_filled, int64_t* num_filled)
 {
   const size_t need = vgt::FillScratchBytes(nx * ny * nz);
-  if (need > ctx->component_ws.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the labelling scratch");
-    VGT_TRY_HIP(ctx->component_ws.Reserve(need), "allocate labelling scratch");
-  }
+  const int grown = GrowCache(ctx->stream, &ctx->component_ws, need, "drain before regrowing the labelling scratch",
+                              "allocate labelling scratch");
+  if (grown != VGT_HIP_OK) return grown;
   void* const scratch = ctx->component_ws.data();
-  hipError_t err = vgt::LaunchFillEnclosed(cells_dev, cell_bytes, unknown_is_filled, nx, ny, nz, scratch, ctx->stream);
+  const hipError_t err = vgt::LaunchFillEnclosed(cells_dev, cell_bytes, unknown_is_filled, nx, ny, nz, scratch, ctx->stream);
   if (!num_filled)
   {
     VGT_TRY_HIP(err, "fill enclosed space");
     return VGT_HIP_OK;
   }
   unsigned long long count = 0;
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(&count, vgt::FillCountPtr(scratch), sizeof(count), hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "fill enclosed space");  // (`count` is on this stack)
+  VGT_TRY_HIP(ReadBack(ctx->stream, err, &count, vgt::FillCountPtr(scratch)), "fill enclosed space");
   *num_filled = static_cast<int64_t>(count);
   return VGT_HIP_OK;
 }
@@ -3009,26 +2912,14 @@ int vgt_hip_fill_enclosed(vgt_hip_ctx* ctx, void* cells_host, int cell_bytes, in
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t map_bytes = static_cast<size_t>(nx * ny * nz) * static_cast<size_t>(cell_bytes);
-  vgt::DeviceTemp map_dev;
-  VGT_TRY_HIP(map_dev.Allocate(map_bytes), "allocate the map");
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipError_t err = hipMemcpyAsync(map_dev.as<void>(), cells_host, map_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (err != hipSuccess)
-  {
-    (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
-    return FailHip("upload the map", err);
-  }
+  vgt::HostStaging staging;
+  const auto map = staging.InOut(static_cast<char*>(cells_host), map_bytes);
   int64_t count = 0;
-  const int result = RunFillEnclosed(ctx, map_dev.as<void>(), cell_bytes, nx, ny, nz, unknown_is_filled, &count);
-  if (result != VGT_HIP_OK)
-  {
-    (void)hipStreamSynchronize(ctx->stream);  // the host map stays as it was
-    return result;
-  }
-  err = hipMemcpyAsync(cells_host, map_dev.as<void>(), map_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "download the map");
-  if (num_filled) *num_filled = count;
-  return VGT_HIP_OK;
+  const int result = staging.Run(*ctx, "fill enclosed space", FailHip, [&](hipStream_t) {
+    return RunFillEnclosed(ctx, map.dev(), cell_bytes, nx, ny, nz, unknown_is_filled, &count);
+  });
+  if (result == VGT_HIP_OK && num_filled) *num_filled = count;
+  return result;
 }
 
 int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
@@ -3041,9 +2932,13 @@ int vgt_hip_cells_connected_components(vgt_hip_ctx* ctx, vgt_hip_cells* cells, i
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const bool by_object = cells->object_id_offset >= 0 && !connect_across_objects;
-  return LabelToHost(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
-                     by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, nullptr, 0.0, cells->nx,
-                     cells->ny, cells->nz, labels_host, num_components);
+  vgt::HostStaging staging;
+  const auto labels = staging.Out(labels_host, static_cast<size_t>(cells->nx * cells->ny * cells->nz));
+  return staging.Run(*ctx, "connected components of a tagged map", FailHip, [&](hipStream_t) {
+    return RunLabelling(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
+                        by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, nullptr, 0.0, cells->nx,
+                        cells->ny, cells->nz, labels.dev(), num_components);
+  });
 }
 
 int vgt_hip_cells_spatial_segments_dev(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const double* extrema_dev,
@@ -3069,23 +2964,15 @@ int vgt_hip_cells_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const
   if (rc != VGT_HIP_OK) return rc;
   if (!extrema_host || !labels_host || !num_segments) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  const size_t bytes = static_cast<size_t>(cells->nx * cells->ny * cells->nz) * 3 * sizeof(double);
-  vgt::DeviceTemp extrema_dev;
-  VGT_TRY_HIP(extrema_dev.Allocate(bytes), "allocate extrema map");
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(extrema_dev.as<void>(), extrema_host, bytes, hipMemcpyHostToDevice, ctx->stream);
-  }
-  int result;
-  if (err == hipSuccess)
-    result = LabelToHost(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
-                         vgt::kComponentSegments, extrema_dev.as<double>(), connected_threshold, cells->nx, cells->ny,
-                         cells->nz, labels_host, num_segments);
-  else
-    result = FailHip("upload extrema map", err);
-  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
-  return result;
+  const size_t n = static_cast<size_t>(cells->nx * cells->ny * cells->nz);
+  vgt::HostStaging staging;
+  const auto extrema = staging.In(extrema_host, n * 3);
+  const auto labels = staging.Out(labels_host, n);
+  return staging.Run(*ctx, "spatial segments", FailHip, [&](hipStream_t) {
+    return RunLabelling(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
+                        vgt::kComponentSegments, extrema.dev(), connected_threshold, cells->nx, cells->ny, cells->nz,
+                        labels.dev(), num_segments);
+  });
 }
 
 int vgt_hip_cells_update_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double connected_threshold,
@@ -3101,31 +2988,26 @@ int vgt_hip_cells_update_spatial_segments(vgt_hip_ctx* ctx, vgt_hip_cells* cells
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const int64_t nx = cells->nx, ny = cells->ny, nz = cells->nz, n = nx * ny * nz;
-  vgt::DeviceTemp extrema_dev, extrema_scratch;
-  VGT_TRY_HIP(extrema_dev.Allocate(static_cast<size_t>(n) * 3 * sizeof(double)), "update spatial segments");
-  VGT_TRY_HIP(extrema_scratch.Allocate(vgt::LocalExtremaScratchBytes(n)), "update spatial segments");
-  hipError_t err = hipSuccess;
-  {
-    // S/tagged_object_occupancy_component_map.cpp:786-790: the field of every filled cell with a virtual border, the
-    // free-and-named-objects field without; its extrema map; the segments.  Field and map stay on the device.
-    std::lock_guard<std::mutex> lock(ctx->mutex);
+  vgt::HostStaging staging;
+  const auto extrema = staging.Scratch<double>(static_cast<size_t>(n) * 3 * sizeof(double));
+  const auto extrema_scratch = staging.Scratch(vgt::LocalExtremaScratchBytes(n));
+  const auto labels = staging.Out(labels_host, static_cast<size_t>(n));
+  // S/tagged_object_occupancy_component_map.cpp:786-790: the field of every filled cell with a virtual border, the
+  // free-and-named-objects field without; its extrema map; the segments.  Field and map stay on the device.
+  return staging.Run(*ctx, "update spatial segments", FailHip, [&](hipStream_t s) {
     const vgt::SdfParams p{nx, ny, nz, resolution, unknown_is_filled ? 1 : 0, add_virtual_border ? 1 : 0};
-    if (add_virtual_border)
-      rc = RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf.as<float>());
-    else
-    {
-      err = cells->sdf_named.Reserve(static_cast<size_t>(n) * sizeof(float));
-      if (err == hipSuccess) rc = RunFreeAndNamedSdf(ctx, cells, p);
-    }
-    if (err == hipSuccess && rc == VGT_HIP_OK)
-      err = vgt::LaunchLocalExtremaMap(cells->sdf.as<float>(), nx, ny, nz, resolution, rotation,
-                                       extrema_dev.as<double>(), extrema_scratch.as<void>(), ctx->stream);
-    err = DrainKeepingFirst(ctx->stream, err);  // (`rotation` is the caller's; the scratch goes with the call)
-  }
-  if (rc != VGT_HIP_OK) return rc;
-  VGT_TRY_HIP(err, "update spatial segments");
-  return LabelToHost(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset, vgt::kComponentSegments,
-                     extrema_dev.as<double>(), connected_threshold, nx, ny, nz, labels_host, num_segments);
+    if (!add_virtual_border)
+      VGT_TRY_HIP(cells->sdf_named.Reserve(static_cast<size_t>(n) * sizeof(float)), "update spatial segments");
+    const int sdf_rc = add_virtual_border ? RunCellsSdf(ctx, cells, 0, 0, p, cells->sdf.as<float>())
+                                          : RunFreeAndNamedSdf(ctx, cells, p);
+    if (sdf_rc != VGT_HIP_OK) return sdf_rc;
+    VGT_TRY_HIP(vgt::LaunchLocalExtremaMap(cells->sdf.as<float>(), nx, ny, nz, resolution, rotation, extrema.dev(),
+                                           extrema_scratch.dev(), s),
+                "update spatial segments");
+    return RunLabelling(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
+                        vgt::kComponentSegments, extrema.dev(), connected_threshold, nx, ny, nz, labels.dev(),
+                        num_segments);
+  });
 }
 
 namespace
@@ -3162,19 +3044,15 @@ int vgt_hip_component_surface_mask(vgt_hip_ctx* ctx, const float* occupancy_host
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const size_t n = static_cast<size_t>(nx * ny * nz);
-  vgt::DeviceTemp buffer;  // occupancy, labels, mask
-  VGT_TRY_HIP(buffer.Allocate(n * 9), "allocate surface mask buffers");
-  float* const occupancy_dev = buffer.as<float>();
-  uint32_t* const labels_dev = reinterpret_cast<uint32_t*>(buffer.as<char>() + n * 4);
-  uint8_t* const mask_dev = buffer.as<uint8_t>() + n * 8;
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipError_t err = hipMemcpyAsync(occupancy_dev, occupancy_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(labels_dev, labels_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess)
-    err = vgt::LaunchComponentSurfaceMask(occupancy_dev, labels_dev, nx, ny, nz, component_types, mask_dev, ctx->stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(mask_host, mask_dev, n, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "component surface mask");
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto occupancy = staging.In(occupancy_host, n);
+  const auto labels = staging.In(labels_host, n);
+  const auto mask = staging.Out(mask_host, n);
+  return staging.Run(*ctx, "component surface mask", FailHip, [&](hipStream_t s) {
+    return HipResult("component surface mask",
+                     vgt::LaunchComponentSurfaceMask(occupancy.dev(), labels.dev(), nx, ny, nz, component_types,
+                                                     mask.dev(), s));
+  });
 }
 
 /* ------------------------- selected cells as compact ordered lists ------------------------- */
@@ -3212,17 +3090,13 @@ int RunSelect(vgt_hip_ctx* ctx, const vgt::SelectGrid& grid, const vgt::SelectOu
 {
   const int64_t n = static_cast<int64_t>(grid.nx) * grid.ny * grid.nz;
   const size_t need = vgt::SelectScratchBytes(n);
-  if (need > ctx->select_ws.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the selection scratch");
-    VGT_TRY_HIP(ctx->select_ws.Reserve(need), "allocate selection scratch");
-  }
+  const int grown = GrowCache(ctx->stream, &ctx->select_ws, need, "drain before regrowing the selection scratch",
+                              "allocate selection scratch");
+  if (grown != VGT_HIP_OK) return grown;
   void* const scratch = ctx->select_ws.data();
   hipError_t err = vgt::LaunchSelectMark(grid, scratch, ctx->stream);
   uint32_t selected = 0;
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(&selected, vgt::SelectCountPtr(scratch, n), sizeof(selected), hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "select cells");  // (`selected` is on this stack)
+  VGT_TRY_HIP(ReadBack(ctx->stream, err, &selected, vgt::SelectCountPtr(scratch, n)), "select cells");
   *count = static_cast<int64_t>(selected);
   if (!out.indices_dev) return VGT_HIP_OK;  // count only
   if (*count > out.capacity)
@@ -3246,33 +3120,22 @@ int RunSelectToHost(vgt_hip_ctx* ctx, const vgt::SelectGrid& grid, const void* p
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the selection holds " + std::to_string(*count) +
                                                   " cells, the output buffers " + std::to_string(capacity));
   if (*count == 0) return VGT_HIP_OK;
-  const size_t list_bytes = static_cast<size_t>(*count) * 4;
-  const size_t lists = 1 + (values_host ? 1 : 0) + (payload_host ? 1 : 0);
-  vgt::DeviceTemp buffer;  // indices, values, payload
-  VGT_TRY_HIP(buffer.Allocate(list_bytes * lists), "allocate selection lists");
-  char* next = buffer.as<char>();
-  vgt::SelectOutput out{};
-  out.indices_dev = reinterpret_cast<int32_t*>(next);
-  next += list_bytes;
-  if (values_host)
-  {
-    out.values_dev = reinterpret_cast<float*>(next);
-    next += list_bytes;
-  }
-  if (payload_host) out.payload_dev = reinterpret_cast<uint32_t*>(next);
-  out.payload_source_dev = payload_source_dev;
-  out.payload_stride = payload_stride;
-  out.capacity = *count;
-  // (the scratch still holds the marks of the count above: same grid, same stream, nothing enqueued in between)
-  hipError_t err = vgt::LaunchSelectEmit(grid, out, ctx->select_ws.data(), ctx->stream);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(indices_host, out.indices_dev, list_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (err == hipSuccess && values_host)
-    err = hipMemcpyAsync(values_host, out.values_dev, list_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (err == hipSuccess && payload_host)
-    err = hipMemcpyAsync(payload_host, out.payload_dev, list_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "select cells");
-  return VGT_HIP_OK;
+  const size_t selected = static_cast<size_t>(*count);
+  vgt::HostStaging staging;
+  const auto indices = staging.Out(indices_host, selected);
+  const auto values = staging.Out(values_host, selected);
+  const auto payload = staging.Out(payload_host, selected);
+  return staging.RunLocked(ctx->stream, "select cells", FailHip, [&](hipStream_t s) {
+    vgt::SelectOutput out{};
+    out.indices_dev = indices.dev();
+    out.values_dev = values.dev();
+    out.payload_dev = payload.dev();
+    out.payload_source_dev = payload_source_dev;
+    out.payload_stride = payload_stride;
+    out.capacity = *count;
+    // (the scratch still holds the marks of the count above: same grid, same stream, nothing enqueued in between)
+    return HipResult("select cells", vgt::LaunchSelectEmit(grid, out, ctx->select_ws.data(), s));
+  });
 }
 
 vgt::SelectGrid MakeSelectGrid(const void* cells_dev, int cell_bytes, const void* labels_dev, int label_stride, int64_t nx,
@@ -3324,23 +3187,14 @@ int vgt_hip_select_cells(vgt_hip_ctx* ctx, const float* values_host, const uint3
   const size_t n = static_cast<size_t>(nx * ny * nz);
   // (labels that neither the rule nor a list needs stay on the host)
   const bool use_labels = labels_host && (rule == VGT_HIP_SELECT_COMPONENT_SURFACE || labels_out);
-  vgt::DeviceTemp buffer;  // values, labels
-  VGT_TRY_HIP(buffer.Allocate(n * (use_labels ? 8 : 4)), "allocate selection inputs");
-  float* const values_dev = buffer.as<float>();
-  uint32_t* const labels_dev = use_labels ? reinterpret_cast<uint32_t*>(buffer.as<char>() + n * 4) : nullptr;
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipError_t err = hipMemcpyAsync(values_dev, values_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess && use_labels)
-    err = hipMemcpyAsync(labels_dev, labels_host, n * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (err != hipSuccess)
-  {
-    (void)hipStreamSynchronize(ctx->stream);  // (an upload may still be in flight)
-    return FailHip("upload selection inputs", err);
-  }
-  const vgt::SelectGrid grid = MakeSelectGrid(values_dev, 4, labels_dev, 4, nx, ny, nz, rule, class_mask, threshold);
-  const int result = RunSelectToHost(ctx, grid, labels_dev, 4, indices_out, values_out, labels_out, capacity, count);
-  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-  return result;
+  vgt::HostStaging staging;
+  const auto values = staging.In(values_host, n);
+  const auto labels = staging.In(use_labels ? labels_host : nullptr, n);
+  return staging.Run(*ctx, "select cells", FailHip, [&](hipStream_t) {
+    const vgt::SelectGrid grid =
+        MakeSelectGrid(values.dev(), 4, labels.dev(), 4, nx, ny, nz, rule, class_mask, threshold);
+    return RunSelectToHost(ctx, grid, labels.dev(), 4, indices_out, values_out, labels_out, capacity, count);
+  });
 }
 
 int vgt_hip_cells_select(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* labels_dev_or_null, int rule,
@@ -3420,10 +3274,8 @@ int RunTopology(vgt_hip_ctx* ctx, const vgt::TopologyGrid& grid, vgt_hip_compone
   VGT_TRY_HIP(table_dev.Allocate(table_bytes), "component topology");
   void* const vertices = vertex_scratch.as<void>();
   hipError_t err = vgt::LaunchTopologyCountNodes(grid, vertices, ctx->stream);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(&num_nodes, vgt::TopologyNodeCountPtr(vertices, grid.nx, grid.ny, grid.nz), sizeof(num_nodes),
-                         hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "component topology");
+  VGT_TRY_HIP(ReadBack(ctx->stream, err, &num_nodes, vgt::TopologyNodeCountPtr(vertices, grid.nx, grid.ny, grid.nz)),
+              "component topology");
   if (num_nodes >= 0x7fffffffULL)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "component topology supports fewer than 2^31 surface nodes");
   if (num_nodes > 0)
@@ -3437,30 +3289,32 @@ int RunTopology(vgt_hip_ctx* ctx, const vgt::TopologyGrid& grid, vgt_hip_compone
   return VGT_HIP_OK;
 }
 
-// Labels the cells into a temporary device grid, then the table (and the labels, when asked for) to the host.
-int LabelAndTopology(vgt_hip_ctx* ctx, const void* cells_dev, int cell_bytes, int object_id_offset, int mode, int64_t nx,
-                     int64_t ny, int64_t nz, int component_types, uint32_t* labels_host, uint32_t* num_components,
-                     vgt_hip_component_topology_t* out_host, uint64_t out_capacity)
+// Labels the cells into a temporary device grid, then the table (and the labels, when asked for) to the host: one unit
+// on the context.  Exactly one of the two sources is given: `occupancy_host`, which is uploaded (then records_dev is
+// null and cell_bytes 4), or a handle's `records_dev` (then occupancy_host is null).
+int LabelAndTopology(vgt_hip_ctx* ctx, const float* occupancy_host, const void* records_dev, int cell_bytes,
+                     int object_id_offset, int mode, int64_t nx, int64_t ny, int64_t nz, int component_types,
+                     uint32_t* labels_host, uint32_t* num_components, vgt_hip_component_topology_t* out_host,
+                     uint64_t out_capacity)
 {
-  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(uint32_t);
-  vgt::DeviceTemp labels;
-  VGT_TRY_HIP(labels.Allocate(bytes), "allocate labels");
-  uint32_t* const labels_dev = labels.as<uint32_t>();
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  uint32_t count = 0;
-  int rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, nullptr, 0.0, nx, ny, nz, labels_dev, &count);
-  if (rc != VGT_HIP_OK) return rc;  // (here and below: the callee has waited for whatever it enqueued)
-  *num_components = count;
-  if (out_capacity < static_cast<uint64_t>(count) + 1)
-    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
-                "the topology table needs num_components + 1 = " + std::to_string(static_cast<uint64_t>(count) + 1) +
-                    " entries, out_capacity is " + std::to_string(out_capacity));
-  rc = RunTopology(ctx, vgt::TopologyGrid{cells_dev, cell_bytes, labels_dev, nx, ny, nz, component_types, count},
-                   out_host);
-  if (rc != VGT_HIP_OK || !labels_host) return rc;
-  const hipError_t err = hipMemcpyAsync(labels_host, labels_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "copy labels to the host");
-  return VGT_HIP_OK;
+  const size_t n = static_cast<size_t>(nx * ny * nz);
+  vgt::HostStaging staging;
+  const auto occupancy = staging.In(occupancy_host, n);
+  const auto labels = labels_host ? staging.Out(labels_host, n) : staging.Scratch<uint32_t>(n * sizeof(uint32_t));
+  return staging.Run(*ctx, "component topology", FailHip, [&](hipStream_t) {
+    const void* const cells_dev = occupancy_host ? occupancy.dev() : records_dev;
+    uint32_t count = 0;
+    const int rc = RunLabelling(ctx, cells_dev, cell_bytes, object_id_offset, mode, nullptr, 0.0, nx, ny, nz,
+                                labels.dev(), &count);
+    if (rc != VGT_HIP_OK) return rc;
+    *num_components = count;
+    if (out_capacity < static_cast<uint64_t>(count) + 1)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "the topology table needs num_components + 1 = " + std::to_string(static_cast<uint64_t>(count) + 1) +
+                      " entries, out_capacity is " + std::to_string(out_capacity));
+    return RunTopology(ctx, vgt::TopologyGrid{cells_dev, cell_bytes, labels.dev(), nx, ny, nz, component_types, count},
+                       out_host);
+  });
 }
 }  // namespace
 
@@ -3488,22 +3342,8 @@ int vgt_hip_component_topology(vgt_hip_ctx* ctx, const float* occupancy_host, in
   if (!ctx || !occupancy_host || !num_components || !out_host)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
-  const size_t bytes = static_cast<size_t>(nx * ny * nz) * sizeof(float);
-  vgt::DeviceTemp occupancy_dev;
-  VGT_TRY_HIP(occupancy_dev.Allocate(bytes), "allocate occupancy");
-  hipError_t err;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mutex);
-    err = hipMemcpyAsync(occupancy_dev.as<void>(), occupancy_host, bytes, hipMemcpyHostToDevice, ctx->stream);
-  }
-  int result;
-  if (err == hipSuccess)
-    result = LabelAndTopology(ctx, occupancy_dev.as<void>(), 4, -1, vgt::kComponentClasses, nx, ny, nz, component_types,
-                              labels_host, num_components, out_host, out_capacity);
-  else
-    result = FailHip("upload occupancy", err);
-  if (result != VGT_HIP_OK) (void)hipStreamSynchronize(ctx->stream);  // (the upload may still be in flight)
-  return result;
+  return LabelAndTopology(ctx, occupancy_host, nullptr, 4, -1, vgt::kComponentClasses, nx, ny, nz, component_types,
+                          labels_host, num_components, out_host, out_capacity);
 }
 
 int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int connect_across_objects,
@@ -3519,7 +3359,7 @@ int vgt_hip_cells_component_topology(vgt_hip_ctx* ctx, vgt_hip_cells* cells, int
   if (rc != VGT_HIP_OK) return rc;
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const bool by_object = cells->object_id_offset >= 0 && !connect_across_objects;
-  return LabelAndTopology(ctx, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
+  return LabelAndTopology(ctx, nullptr, cells->records.as<void>(), cells->cell_bytes, cells->object_id_offset,
                           by_object ? vgt::kComponentClassesAndIds : vgt::kComponentClasses, cells->nx, cells->ny,
                           cells->nz, component_types, labels_host, num_components, out_host, out_capacity);
 }
@@ -3584,11 +3424,9 @@ int RunMeshRasterize(vgt_hip_ctx* ctx, const double* vertices_dev, int64_t num_v
                      int64_t num_triangles, void* cells_dev, const vgt::MeshGrid& grid)
 {
   const size_t need = vgt::MeshScratchBytes(num_triangles);
-  if (need > ctx->mesh_ws.bytes())
-  {
-    VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "drain before regrowing the mesh scratch");
-    VGT_TRY_HIP(ctx->mesh_ws.Reserve(need), "allocate mesh scratch");
-  }
+  const int grown = GrowCache(ctx->stream, &ctx->mesh_ws, need, "drain before regrowing the mesh scratch",
+                              "allocate mesh scratch");
+  if (grown != VGT_HIP_OK) return grown;
   void* const scratch = ctx->mesh_ws.data();
   vgt::MeshTotals totals{};
   vgt::MeshStatus status{};
@@ -3596,10 +3434,7 @@ int RunMeshRasterize(vgt_hip_ctx* ctx, const double* vertices_dev, int64_t num_v
   if (err == hipSuccess)
     err = hipMemcpyAsync(&totals, vgt::MeshTotalsPtr(scratch, num_triangles), sizeof(totals), hipMemcpyDeviceToHost,
                          ctx->stream);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(&status, vgt::MeshStatusPtr(scratch, num_triangles), sizeof(status), hipMemcpyDeviceToHost,
-                         ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "mesh set-up");  // (both are on this stack)
+  VGT_TRY_HIP(ReadBack(ctx->stream, err, &status, vgt::MeshStatusPtr(scratch, num_triangles)), "mesh set-up");
   if (status.bits & vgt::kMeshBadIndex)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
                 "triangle " + std::to_string(status.first[0]) + " has a vertex index out of range");
@@ -3613,9 +3448,7 @@ int RunMeshRasterize(vgt_hip_ctx* ctx, const double* vertices_dev, int64_t num_v
                 "the triangles' index ranges hold more than 2^36 candidate cells: refused (is the mesh inside the map?)");
   VGT_TRY_HIP(vgt::LaunchMeshBricks(grid, num_triangles, totals.bricks, scratch, cells_dev, ctx->stream), "mesh bricks");
   if (!grid.enforce) return VGT_HIP_OK;
-  err = hipMemcpyAsync(&status, vgt::MeshStatusPtr(scratch, num_triangles), sizeof(status), hipMemcpyDeviceToHost,
-                       ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "mesh bricks");
+  VGT_TRY_HIP(ReadBack(ctx->stream, hipSuccess, &status, vgt::MeshStatusPtr(scratch, num_triangles)), "mesh bricks");
   if (status.bits & vgt::kMeshNotContained)
     return Fail(VGT_HIP_ERR_RUNTIME,
                 "Triangle is not contained by occupancy map (triangle " + std::to_string(status.first[3]) + ")");
@@ -3651,36 +3484,13 @@ int vgt_hip_rasterize_mesh(vgt_hip_ctx* ctx, const double* vertices_xyz_host, in
   VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
   const vgt::MeshGrid grid =
       MakeMeshGrid(cell_bytes, nx, ny, nz, resolution, world_from_grid, grid_from_world, enforce_contains, rule);
-  const size_t vertex_bytes = static_cast<size_t>(num_vertices) * 3 * sizeof(double);
-  const size_t triangle_bytes = static_cast<size_t>(num_triangles) * 3 * sizeof(int32_t);
-  const size_t map_bytes = static_cast<size_t>(nx * ny * nz) * static_cast<size_t>(cell_bytes);
-  vgt::DeviceTemp vertices_dev, triangles_dev, map_dev;
-  VGT_TRY_HIP(vertices_dev.Allocate(vertex_bytes ? vertex_bytes : sizeof(double)), "allocate vertices");
-  VGT_TRY_HIP(triangles_dev.Allocate(triangle_bytes), "allocate triangles");
-  VGT_TRY_HIP(map_dev.Allocate(map_bytes), "allocate the map");
-  std::lock_guard<std::mutex> lock(ctx->mutex);
-  hipError_t err = hipSuccess;
-  if (vertex_bytes)
-    err = hipMemcpyAsync(vertices_dev.as<void>(), vertices_xyz_host, vertex_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(triangles_dev.as<void>(), triangles_host, triangle_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(map_dev.as<void>(), cells_host, map_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (err != hipSuccess)
-  {
-    (void)hipStreamSynchronize(ctx->stream);  // (an upload may still be in flight)
-    return FailHip("upload the mesh and the map", err);
-  }
-  const int result = RunMeshRasterize(ctx, vertices_dev.as<double>(), num_vertices, triangles_dev.as<int32_t>(),
-                                      num_triangles, map_dev.as<void>(), grid);
-  if (result != VGT_HIP_OK)
-  {
-    (void)hipStreamSynchronize(ctx->stream);  // the host map stays as it was
-    return result;
-  }
-  err = hipMemcpyAsync(cells_host, map_dev.as<void>(), map_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "download the map");
-  return VGT_HIP_OK;
+  vgt::HostStaging staging;
+  const auto vertices = staging.In(vertices_xyz_host, static_cast<size_t>(num_vertices) * 3);
+  const auto triangles = staging.In(triangles_host, static_cast<size_t>(num_triangles) * 3);
+  const auto map = staging.InOut(static_cast<char*>(cells_host), static_cast<size_t>(nx * ny * nz) * cell_bytes);
+  return staging.Run(*ctx, "rasterize mesh", FailHip, [&](hipStream_t) {
+    return RunMeshRasterize(ctx, vertices.dev(), num_vertices, triangles.dev(), num_triangles, map.dev(), grid);
+  });
 }
 
 int vgt_hip_mesh_grid_for(const double* vertices_xyz_host, int64_t num_vertices, double resolution, int64_t* nx,
