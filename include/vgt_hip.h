@@ -643,6 +643,66 @@ int vgt_hip_cells_select(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t*
                          int class_mask, int32_t* indices_host, float* occupancy_host, uint32_t* payload_host,
                          int payload_member, int64_t capacity, int64_t* count);
 
+/* ---- the iso-surface of a field or a map as an indexed triangle mesh (csrc/surface_kernels.hip) ----
+ * An extension: the reference offers cubes only (the display exports).  The method is surface nets on the lattice of
+ * cell centres: no case table, shared vertices by construction, a closed and consistently oriented mesh wherever the
+ * surface stays inside the grid.  The vertex and triangle arrays have the formats of vgt_hip_rasterize_mesh.
+ *   field       float values f[i, j, k] on an nx x ny x nz grid, X-major / Z fastest.
+ *   inside(v)   v < iso; with inside_above != 0: v > iso (occupancy: iso = 0.5f, inside_above = 1).  A value equal to iso
+ *               is outside; a NaN is not inside.
+ *   sample      (i, j, k) sits at the cell centre, per axis (index + 0.5) * resolution in double.
+ *   cube        (i, j, k) with 0 <= i < nx - 1, 0 <= j < ny - 1, 0 <= k < nz - 1; its corners are the samples
+ *               (i + a, j + b, k + c), a, b, c in {0, 1}.  ACTIVE: all 8 corners are finite (no NaN, no +-inf), some
+ *               corner is inside and some is not.  A cube with a non-finite corner is void: no vertex, and no face uses it.
+ *   vertex      one per active cube, in double without FMA contraction.  The cube's 12 edges in this order: axis x, then
+ *               y, then z; with (b, c) the next two axes cyclically after axis a (x -> (y, z), y -> (z, x), z -> (x, y)),
+ *               the four edges of axis a have the offsets (db, dc) = (0,0), (0,1), (1,0), (1,1).  An edge runs from its
+ *               lower corner p0 to p1 = p0 + e_a and CROSSES when inside(v0) != inside(v1); then
+ *               t = ((double)iso - (double)v0) / ((double)v1 - (double)v0), and the edge's offset inside the cube is t on
+ *               axis a, db on axis b, dc on axis c.  Per axis component the offsets of the crossing edges are added left
+ *               to right in the edge order, starting from 0.0, and divided by their number n (as a double);
+ *               location_axis = (((double)index_axis + 0.5) + offset_axis) * resolution.  With world_from_grid (16
+ *               doubles, column-major) row r is M[r] * x + M[4 + r] * y + M[8 + r] * z + M[12 + r], left to right: the
+ *               rule of csrc/mesh_kernels.hip.  NULL: the grid frame.
+ *   order       vertices in ascending linear index (i * ny + j) * nz + k of the cube's lowest corner in the SAMPLE grid;
+ *               vertex_cells_out (int32, may be NULL) receives that index (to gather labels, object ids, colours).
+ *   face        one quad, two triangles, per crossing lattice edge p -> p + e_a whose four cubes all exist and are all
+ *               active (for a = x: 1 <= j <= ny - 2 and 1 <= k <= nz - 2, alike for y and z): an edge on a face of the
+ *               lattice gives no quad, a surface that leaves the grid is open there.  With (b, c) as above the cubes, by
+ *               lowest corner: c00 = p - e_b - e_c, c10 = p - e_c, c11 = p, c01 = p - e_b; the loop c00, c10, c11, c01 is
+ *               counter-clockwise seen from +a.  p inside: the normal is +a, (q0, q1, q2, q3) = (c00, c10, c11, c01);
+ *               otherwise (c00, c01, c11, c10).  Triangles (q0, q1, q2) and (q0, q2, q3), as vertex indices.  Normals
+ *               point from inside to outside; the signed volume of a closed result is positive.
+ *   face order  ascending linear index of p, then axis x, y, z.
+ * The result is a function of the input alone (no atomics on the outputs).
+ * *num_vertices and *num_triangles are always stored.  vertices_xyz_out == NULL with both capacities 0 only counts.  A
+ * count above its capacity (vertex_capacity in vertices, triangle_capacity in triangles) fails with
+ * VGT_HIP_ERR_INVALID_ARGUMENT (the message names both numbers) and writes nothing.  triangles_out may be NULL (vertices
+ * only).  Grids below 2^31 cells; 3 * num_triangles below 2^31 (else VGT_HIP_ERR_INVALID_ARGUMENT after the count).  A
+ * grid with an extent of 1 has no cubes: success, 0 and 0, nothing launched.  Blocking: the counts are read back.
+ * Errors before any HIP call (VGT_HIP_ERR_INVALID_ARGUMENT): a null context, field or count, an extent <= 0, a
+ * resolution that is not finite and positive, a non-finite iso, triangles_out or vertex_cells_out without
+ * vertices_xyz_out, a capacity without its buffer.
+ *   vgt_hip_extract_surface        field and mesh in host memory; the outputs are staged at their real size.
+ *   vgt_hip_extract_surface_dev    device pointers for the field and the three outputs (the counts go to the host); runs
+ *                                  on the context's stream; the vertex and triangle buffers are valid inputs of
+ *                                  vgt_hip_rasterize_mesh_dev as they stand.
+ *   vgt_hip_cells_extract_surface  the occupancy member of uploaded cells, iso = 0.5f, inside_above; mesh to host memory.
+ * Scratch the context keeps: 5 bits per voxel (bit planes) + 4 bytes per 64 voxels + 8 bytes per 1024 voxels. */
+int vgt_hip_extract_surface(vgt_hip_ctx* ctx, const float* values_host, int64_t nx, int64_t ny, int64_t nz, float iso,
+                            int inside_above, double resolution, const double* world_from_grid, double* vertices_xyz_out,
+                            int32_t* vertex_cells_out, int64_t vertex_capacity, int32_t* triangles_out,
+                            int64_t triangle_capacity, int64_t* num_vertices, int64_t* num_triangles);
+int vgt_hip_extract_surface_dev(vgt_hip_ctx* ctx, const float* values_dev, int64_t nx, int64_t ny, int64_t nz, float iso,
+                                int inside_above, double resolution, const double* world_from_grid,
+                                double* vertices_xyz_dev, int32_t* vertex_cells_dev, int64_t vertex_capacity,
+                                int32_t* triangles_dev, int64_t triangle_capacity, int64_t* num_vertices,
+                                int64_t* num_triangles);
+int vgt_hip_cells_extract_surface(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double resolution,
+                                  const double* world_from_grid, double* vertices_xyz_out, int32_t* vertex_cells_out,
+                                  int64_t vertex_capacity, int32_t* triangles_out, int64_t triangle_capacity,
+                                  int64_t* num_vertices, int64_t* num_triangles);
+
 /* ---- holes and voids per component: ComputeComponentTopology (I/topology_computation.hpp:331-670, called from
  * S/occupancy_component_map.cpp:594-653 and S/tagged_object_occupancy_component_map.cpp:566-625).
  * The reference walks hash sets per component; its result is this closed form, computed by csrc/topology_kernels.hip.

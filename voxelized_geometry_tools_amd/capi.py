@@ -98,6 +98,10 @@ SIGNATURES = {
     "vgt_hip_select_cells": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _int, _f32, _p, _p, _p, _i64, _p]),
     "vgt_hip_select_cells_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _int, _f32, _p, _p, _p, _i64, _p]),
     "vgt_hip_cells_select": (_int, [_p, _p, _p, _int, _int, _p, _p, _p, _int, _i64, _p]),
+    "vgt_hip_extract_surface": (_int, [_p, _p, _i64, _i64, _i64, _f32, _int, _f64, _p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "vgt_hip_extract_surface_dev": (_int, [_p, _p, _i64, _i64, _i64, _f32, _int, _f64, _p, _p, _p, _i64, _p, _i64, _p,
+                                           _p]),
+    "vgt_hip_cells_extract_surface": (_int, [_p, _p, _f64, _p, _p, _p, _i64, _p, _i64, _p, _p]),
     "vgt_hip_component_topology_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint32, _p]),
     "vgt_hip_component_topology": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_uint64]),
     "vgt_hip_cells_component_topology": (_int, [_p, _p, _int, _int, _p, _p, _p, ctypes.c_uint64]),
@@ -288,6 +292,19 @@ def _topology_table(call, capacity=256):
         check(rc)
         return table[:count.value + 1].copy()
     raise VgtHipError("the component count changed between two calls")
+
+
+def _surface_mesh(call, with_cells):
+    """Runs call(vertices, cells, vertex_capacity, triangles, triangle_capacity, byref(nv), byref(nt)) of a host-output
+    surface extraction twice: to count, then to fetch into arrays of exactly the counts."""
+    nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(call(None, None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)))
+    vertices = np.empty((int(nv.value), 3), dtype=np.float64)
+    triangles = np.empty((int(nt.value), 3), dtype=np.int32)
+    cells = np.empty(int(nv.value), dtype=np.int32) if with_cells else None
+    if nv.value:
+        check(call(vertices, cells, len(vertices), triangles, len(triangles), ctypes.byref(nv), ctypes.byref(nt)))
+    return (vertices, triangles, cells) if with_cells else (vertices, triangles)
 
 
 def mesh_grid_for(vertices, resolution):
@@ -553,6 +570,58 @@ class Context:
                      with_occupancy=False):
         """vgt_hip_cells_select on a Cells handle of this context: see Cells.select."""
         return cells.select(rule, class_mask, payload_member, labels_ptr, with_occupancy)
+
+    def extract_surface(self, values, resolution, iso=0.0, inside_above=False, world_from_grid=None, with_cells=False):
+        """vgt_hip_extract_surface: the iso-surface of a float grid as an indexed mesh (surface nets on the lattice of
+        cell centres; include/vgt_hip.h states the rules) -> (vertices float64 [V, 3], triangles int32 [T, 3]) and, with
+        with_cells=True, the int32 linear index [V] of each vertex's cube.  inside is v < iso, or v > iso with
+        inside_above (occupancy: iso=0.5, inside_above=True).  world_from_grid: 16 doubles column-major, None = the grid
+        frame.  One call counts, a second one fetches."""
+        val = np.ascontiguousarray(values, dtype=np.float32)
+        if val.ndim != 3:
+            raise ValueError("values must be an (nx, ny, nz) grid")
+        wfg, _ = _mesh_transforms(world_from_grid, None)
+
+        def call(vertices, cells, vertex_capacity, triangles, triangle_capacity, nv, nt):
+            return self._lib.vgt_hip_extract_surface(
+                self.handle, _ptr(val), *val.shape, float(iso), int(bool(inside_above)), float(resolution), _ptr(wfg),
+                _ptr(vertices), _ptr(cells), vertex_capacity, _ptr(triangles), triangle_capacity, nv, nt)
+
+        return _surface_mesh(call, with_cells)
+
+    def extract_surface_dev(self, values, resolution, iso=0.0, inside_above=False, world_from_grid=None,
+                            with_cells=False, shape=None):
+        """vgt_hip_extract_surface_dev: `values` is a float32 torch tensor (nx, ny, nz) on the context's device, or a
+        device pointer with `shape`.  Returns torch tensors on that device, (vertices float64 [V, 3], triangles int32
+        [T, 3][, cells int32 [V]]): valid inputs of rasterize_mesh_dev as they stand.  The field must be complete before
+        the call (it runs on the context's stream); the mesh is complete when the call returns."""
+        import torch
+        device = "cuda:%d" % self._lib.vgt_hip_device_of(self.handle)
+        if shape is None:
+            if values.dtype != torch.float32 or values.dim() != 3 or not values.is_contiguous():
+                raise ValueError("values must be a contiguous float32 (nx, ny, nz) tensor")
+            shape, values_ptr = tuple(values.shape), values.data_ptr()
+        else:
+            values_ptr = values.data_ptr() if hasattr(values, "data_ptr") else values
+        shape = [int(c) for c in shape]
+        wfg, _ = _mesh_transforms(world_from_grid, None)
+        nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+
+        def call(vertices, cells, vertex_capacity, triangles, triangle_capacity):
+            check(self._lib.vgt_hip_extract_surface_dev(
+                self.handle, _ptr(values_ptr), *shape, float(iso), int(bool(inside_above)), float(resolution), _ptr(wfg),
+                _ptr(vertices), _ptr(cells), vertex_capacity, _ptr(triangles), triangle_capacity, ctypes.byref(nv),
+                ctypes.byref(nt)))
+
+        call(None, None, 0, None, 0)
+        vertices = torch.empty((int(nv.value), 3), dtype=torch.float64, device=device)
+        triangles = torch.empty((int(nt.value), 3), dtype=torch.int32, device=device)
+        cells = torch.empty(int(nv.value), dtype=torch.int32, device=device) if with_cells else None
+        if nv.value:
+            torch.cuda.synchronize(device)  # (the buffers are torch's: nothing of its streams may still use them)
+            call(vertices.data_ptr(), cells.data_ptr() if with_cells else None, len(vertices), triangles.data_ptr(),
+                 len(triangles))
+        return (vertices, triangles, cells) if with_cells else (vertices, triangles)
 
     def component_topology(self, occupancy, component_types, with_labels=False):
         """ComputeComponentTopology of an occupancy grid (it labels the grid first): a COMPONENT_TOPOLOGY array with one
@@ -1180,6 +1249,18 @@ class Cells:
             call(indices, occ, payload, n)
         out = (indices,) + ((occ,) if with_occupancy else ()) + ((payload,) if want_payload else ())
         return out if len(out) > 1 else indices
+
+    def extract_surface(self, resolution, world_from_grid=None, with_cells=False):
+        """vgt_hip_cells_extract_surface: the surface of the uploaded cells' occupancy (inside: > 0.5) as an indexed
+        mesh, as Context.extract_surface(occupancy, resolution, 0.5, True, ...) returns it."""
+        wfg, _ = _mesh_transforms(world_from_grid, None)
+
+        def call(vertices, cells, vertex_capacity, triangles, triangle_capacity, nv, nt):
+            return self._lib.vgt_hip_cells_extract_surface(
+                self.ctx.handle, self.handle, float(resolution), _ptr(wfg), _ptr(vertices), _ptr(cells),
+                vertex_capacity, _ptr(triangles), triangle_capacity, nv, nt)
+
+        return _surface_mesh(call, with_cells)
 
     def component_topology(self, component_types, connect_across_objects=False, with_labels=False):
         """ComputeComponentTopology of the uploaded cells: the COMPONENT_TOPOLOGY table of Context.component_topology;

@@ -74,6 +74,8 @@ struct vgt_hip_ctx
   vgt::DeviceCache component_ws;
   // Scratch of the cell selection (bit grid + scan counts), kept likewise
   vgt::DeviceCache select_ws;
+  // Scratch of the surface extraction (bit planes, vertex bases, scan counts), kept likewise
+  vgt::DeviceCache surface_ws;
   // Scratch of the mesh rasterizer (triangle records, work-list offsets, totals and status), kept likewise
   vgt::DeviceCache mesh_ws;
   // Page-locked staging ring of the batched downloads (DownloadToHostArrays): kStagingSlots slots of kStagingSlotBytes,
@@ -269,7 +271,7 @@ int GrowCache(hipStream_t s, vgt::DeviceCache* cache, size_t need, const char* d
 void FreeCachedSdfBuffers(vgt_hip_ctx* ctx)
 {
   for (vgt::DeviceCache* b : {&ctx->sdf_in, &ctx->sdf_out, &ctx->sdf_ws, &ctx->ray_scratch, &ctx->component_ws,
-                             &ctx->select_ws, &ctx->mesh_ws})
+                             &ctx->select_ws, &ctx->surface_ws, &ctx->mesh_ws})
     (void)b->Release();
   if (ctx->host_staging) (void)hipHostFree(ctx->host_staging);
   ctx->host_staging = nullptr;
@@ -3239,6 +3241,187 @@ int vgt_hip_cells_select(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t*
   std::lock_guard<std::mutex> lock(ctx->mutex);
   return RunSelectToHost(ctx, grid, payload_at >= 0 ? records + payload_at : nullptr, cells->cell_bytes, indices_host,
                          occupancy_host, payload_at >= 0 ? payload_host : nullptr, capacity, count);
+}
+
+/* ------------------------- the iso-surface as an indexed triangle mesh ------------------------- */
+
+namespace
+{
+// Where a caller wants the mesh, in host or in device memory.
+struct SurfaceBuffers
+{
+  double* vertices;
+  int32_t* vertex_cells;
+  int64_t vertex_capacity;
+  int32_t* triangles;
+  int64_t triangle_capacity;
+  int64_t* num_vertices;
+  int64_t* num_triangles;
+};
+
+// Everything that can be said about an extraction before any HIP call (the context is not looked into).
+int CheckSurfaceArguments(const vgt_hip_ctx* ctx, const void* values, int64_t nx, int64_t ny, int64_t nz, float iso,
+                          double resolution, const SurfaceBuffers& b)
+{
+  if (!ctx || !values || !b.num_vertices || !b.num_triangles) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckComponentGrid(nx, ny, nz);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!(resolution > 0.0) || !std::isfinite(resolution))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "resolution must be finite and greater than zero");
+  if (!std::isfinite(iso)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the iso level must be finite");
+  if (b.triangles && !b.vertices)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a triangle buffer needs a vertex buffer: the triangles index the vertices");
+  if (b.vertex_cells && !b.vertices) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a vertex cell buffer needs a vertex buffer");
+  if (b.vertex_capacity < 0 || (b.vertex_capacity > 0 && !b.vertices))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "invalid vertex buffer (capacity without a buffer, or a negative one)");
+  if (b.triangle_capacity < 0 || (b.triangle_capacity > 0 && !b.triangles))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "invalid triangle buffer (capacity without a buffer, or a negative one)");
+  return VGT_HIP_OK;
+}
+
+vgt::SurfaceGrid MakeSurfaceGrid(const void* values_dev, int value_stride, int64_t nx, int64_t ny, int64_t nz, float iso,
+                                 int inside_above, double resolution, const double* world_from_grid)
+{
+  vgt::SurfaceGrid g{};
+  g.values_dev = values_dev;
+  g.value_stride = value_stride;
+  g.nx = static_cast<int>(nx);
+  g.ny = static_cast<int>(ny);
+  g.nz = static_cast<int>(nz);
+  g.iso = iso;
+  g.inside_above = inside_above ? 1 : 0;
+  g.resolution = resolution;
+  g.has_transform = world_from_grid ? 1 : 0;
+  if (world_from_grid) std::memcpy(g.world_from_grid, world_from_grid, sizeof(g.world_from_grid));
+  return g;
+}
+
+// A grid with an extent of 1 has no cubes: an empty mesh, nothing launched.
+bool SurfaceHasNoCubes(int64_t nx, int64_t ny, int64_t nz, const SurfaceBuffers& b)
+{
+  if (nx > 1 && ny > 1 && nz > 1) return false;
+  *b.num_vertices = 0;
+  *b.num_triangles = 0;
+  return true;
+}
+
+// Marks and counts on the context's stream, waits for the two counts and stores them; then compares them with the
+// capacities.  *emit: there is something to write and room for it.  Caller holds the context mutex and has set the device.
+int CountSurface(vgt_hip_ctx* ctx, const vgt::SurfaceGrid& grid, const SurfaceBuffers& b, bool* emit)
+{
+  *emit = false;
+  const int64_t n = static_cast<int64_t>(grid.nx) * grid.ny * grid.nz;
+  const int grown = GrowCache(ctx->stream, &ctx->surface_ws, vgt::SurfaceScratchBytes(n),
+                              "drain before regrowing the surface scratch", "allocate surface scratch");
+  if (grown != VGT_HIP_OK) return grown;
+  void* const scratch = ctx->surface_ws.data();
+  const hipError_t err = vgt::LaunchSurfaceMark(grid, scratch, ctx->stream);
+  vgt::SurfaceCounts counts{};
+  VGT_TRY_HIP(ReadBack(ctx->stream, err, &counts, vgt::SurfaceCountsPtr(scratch, n)), "extract surface");
+  // (3 int32 per triangle, 2 triangles per quad: 3 * num_triangles stays below 2^31)
+  if (counts.quads * 6ull >= 0x80000000ull)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the surface holds " + std::to_string(counts.quads * 2ull) +
+                                                  " triangles: 3 * num_triangles must stay below 2^31");
+  *b.num_vertices = static_cast<int64_t>(counts.vertices);
+  *b.num_triangles = static_cast<int64_t>(counts.quads) * 2;
+  if (!b.vertices) return VGT_HIP_OK;  // count only
+  if (*b.num_vertices > b.vertex_capacity)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the surface holds " + std::to_string(*b.num_vertices) +
+                                                  " vertices, the vertex buffers " + std::to_string(b.vertex_capacity));
+  if (b.triangles && *b.num_triangles > b.triangle_capacity)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the surface holds " + std::to_string(*b.num_triangles) +
+                                                  " triangles, the triangle buffer " + std::to_string(b.triangle_capacity));
+  *emit = *b.num_vertices > 0;
+  return VGT_HIP_OK;
+}
+
+// The mesh into DEVICE buffers, from the marks of the CountSurface just before (same grid, same stream, nothing enqueued
+// in between).
+hipError_t EmitSurface(vgt_hip_ctx* ctx, const vgt::SurfaceGrid& grid, double* vertices_dev, int32_t* vertex_cells_dev,
+                       int32_t* triangles_dev, int64_t num_triangles, hipStream_t s)
+{
+  const vgt::SurfaceOutput out{vertices_dev, vertex_cells_dev, num_triangles > 0 ? triangles_dev : nullptr};
+  return vgt::LaunchSurfaceEmit(grid, out, ctx->surface_ws.data(), s);
+}
+
+// Counts, then emits into device buffers of exactly the counts and downloads them.  Caller holds the context mutex.
+int RunSurfaceToHost(vgt_hip_ctx* ctx, const vgt::SurfaceGrid& grid, const SurfaceBuffers& b)
+{
+  bool emit = false;
+  const int rc = CountSurface(ctx, grid, b, &emit);
+  if (rc != VGT_HIP_OK || !emit) return rc;
+  const size_t num_vertices = static_cast<size_t>(*b.num_vertices), num_triangles = static_cast<size_t>(*b.num_triangles);
+  vgt::HostStaging staging;
+  const auto vertices = staging.Out(b.vertices, num_vertices * 3);
+  const auto vertex_cells = staging.Out(b.vertex_cells, num_vertices);
+  const auto triangles = staging.Out(num_triangles ? b.triangles : nullptr, num_triangles * 3);
+  return staging.RunLocked(ctx->stream, "extract surface", FailHip, [&](hipStream_t s) {
+    return HipResult("extract surface", EmitSurface(ctx, grid, vertices.dev(), vertex_cells.dev(), triangles.dev(),
+                                                    *b.num_triangles, s));
+  });
+}
+}  // namespace
+
+int vgt_hip_extract_surface_dev(vgt_hip_ctx* ctx, const float* values_dev, int64_t nx, int64_t ny, int64_t nz, float iso,
+                                int inside_above, double resolution, const double* world_from_grid,
+                                double* vertices_xyz_dev, int32_t* vertex_cells_dev, int64_t vertex_capacity,
+                                int32_t* triangles_dev, int64_t triangle_capacity, int64_t* num_vertices,
+                                int64_t* num_triangles)
+{
+  const SurfaceBuffers b{vertices_xyz_dev, vertex_cells_dev, vertex_capacity, triangles_dev,
+                         triangle_capacity, num_vertices,    num_triangles};
+  const int rc = CheckSurfaceArguments(ctx, values_dev, nx, ny, nz, iso, resolution, b);
+  if (rc != VGT_HIP_OK) return rc;
+  if (SurfaceHasNoCubes(nx, ny, nz, b)) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const vgt::SurfaceGrid grid = MakeSurfaceGrid(values_dev, 4, nx, ny, nz, iso, inside_above, resolution, world_from_grid);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  bool emit = false;
+  const int counted = CountSurface(ctx, grid, b, &emit);
+  if (counted != VGT_HIP_OK || !emit) return counted;
+  const hipError_t err =
+      EmitSurface(ctx, grid, vertices_xyz_dev, vertex_cells_dev, triangles_dev, *num_triangles, ctx->stream);
+  VGT_TRY_HIP(DrainKeepingFirst(ctx->stream, err), "extract surface");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_extract_surface(vgt_hip_ctx* ctx, const float* values_host, int64_t nx, int64_t ny, int64_t nz, float iso,
+                            int inside_above, double resolution, const double* world_from_grid, double* vertices_xyz_out,
+                            int32_t* vertex_cells_out, int64_t vertex_capacity, int32_t* triangles_out,
+                            int64_t triangle_capacity, int64_t* num_vertices, int64_t* num_triangles)
+{
+  const SurfaceBuffers b{vertices_xyz_out, vertex_cells_out, vertex_capacity, triangles_out,
+                         triangle_capacity, num_vertices,    num_triangles};
+  const int rc = CheckSurfaceArguments(ctx, values_host, nx, ny, nz, iso, resolution, b);
+  if (rc != VGT_HIP_OK) return rc;
+  if (SurfaceHasNoCubes(nx, ny, nz, b)) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  vgt::HostStaging staging;
+  const auto values = staging.In(values_host, static_cast<size_t>(nx * ny * nz));
+  return staging.Run(*ctx, "extract surface", FailHip, [&](hipStream_t) {
+    return RunSurfaceToHost(
+        ctx, MakeSurfaceGrid(values.dev(), 4, nx, ny, nz, iso, inside_above, resolution, world_from_grid), b);
+  });
+}
+
+int vgt_hip_cells_extract_surface(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double resolution,
+                                  const double* world_from_grid, double* vertices_xyz_out, int32_t* vertex_cells_out,
+                                  int64_t vertex_capacity, int32_t* triangles_out, int64_t triangle_capacity,
+                                  int64_t* num_vertices, int64_t* num_triangles)
+{
+  int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  const SurfaceBuffers b{vertices_xyz_out, vertex_cells_out, vertex_capacity, triangles_out,
+                         triangle_capacity, num_vertices,    num_triangles};
+  rc = CheckSurfaceArguments(ctx, cells, cells->nx, cells->ny, cells->nz, 0.5f, resolution, b);
+  if (rc != VGT_HIP_OK) return rc;
+  if (SurfaceHasNoCubes(cells->nx, cells->ny, cells->nz, b)) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  // (the float occupancy is the first member of every cell layout)
+  const vgt::SurfaceGrid grid = MakeSurfaceGrid(cells->records.as<void>(), cells->cell_bytes, cells->nx, cells->ny,
+                                                cells->nz, 0.5f, 1, resolution, world_from_grid);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunSurfaceToHost(ctx, grid, b);
 }
 
 /* ------------------------- holes and voids per component ------------------------- */

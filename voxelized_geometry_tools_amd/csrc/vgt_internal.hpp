@@ -320,6 +320,46 @@ hipError_t LaunchSelectMark(const SelectGrid& grid, void* scratch_dev, hipStream
 hipError_t LaunchSelectEmit(const SelectGrid& grid, const SelectOutput& out, const void* scratch_dev,
                             hipStream_t stream);
 
+// --- launchers (surface_kernels.hip): the iso-surface of a field as an indexed triangle mesh ---
+// The rules: include/vgt_hip.h, vgt_hip_extract_surface.  values_dev: one float every value_stride bytes (a plain float
+// grid: 4; the occupancy of cell records: cell_bytes).  Grids below 2^31 cells.
+struct SurfaceGrid
+{
+  const void* values_dev;
+  int value_stride;
+  int nx, ny, nz;
+  float iso;
+  int inside_above;
+  double resolution;
+  int has_transform;  // 0: the vertices stay in the grid frame
+  double world_from_grid[16];
+};
+// vertices_dev: 3 doubles per vertex; vertex_cells_dev (or nullptr): the linear index of each vertex's cube;
+// triangles_dev (or nullptr): 6 int32 per quad.
+struct SurfaceOutput
+{
+  double* vertices_dev;
+  int32_t* vertex_cells_dev;
+  int32_t* triangles_dev;
+};
+// quads is exact; quads_scanned is the int32 scan's total, the one the quad offsets are good for: the two differ when
+// the quads do not fit the scan (2^31 or more), which the caller must refuse before LaunchSurfaceEmit.
+struct SurfaceCounts
+{
+  uint32_t vertices, quads_scanned;
+  unsigned long long quads;
+};
+// Two steps, because the outputs are sized by what the first one counts:
+//   LaunchSurfaceMark  the bit planes, the block counts and their scans into scratch_dev (SurfaceScratchBytes bytes:
+//                      5 bits per voxel + 4 bytes per 64 voxels + 8 bytes per 1024 voxels); the counts lie at
+//                      SurfaceCountsPtr afterwards (stream-ordered);
+//   LaunchSurfaceEmit  the vertices, and the triangles when asked for, from the scratch of a LaunchSurfaceMark of the
+//                      same grid (it adds the per-word vertex bases to the scratch).
+size_t SurfaceScratchBytes(int64_t num_cells);
+const SurfaceCounts* SurfaceCountsPtr(const void* scratch_dev, int64_t num_cells);
+hipError_t LaunchSurfaceMark(const SurfaceGrid& grid, void* scratch_dev, hipStream_t stream);
+hipError_t LaunchSurfaceEmit(const SurfaceGrid& grid, const SurfaceOutput& out, void* scratch_dev, hipStream_t stream);
+
 // --- launchers (topology_kernels.hip): holes and voids per component ---
 // One entry per label, the layout of vgt_hip_component_topology_t (include/vgt_hip.h).
 struct ComponentTopologyEntry
