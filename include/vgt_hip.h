@@ -703,6 +703,103 @@ int vgt_hip_cells_extract_surface(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double
                                   int64_t vertex_capacity, int32_t* triangles_out, int64_t triangle_capacity,
                                   int64_t* num_vertices, int64_t* num_triangles);
 
+/* ---- cost-to-go through free space, the neighbour to step to, and path tracing (csrc/travel_kernels.hip) ----
+ * An extension: how far every cell is from a set of sources THROUGH passable cells -- the navigation function of a grid
+ * planner, an admissible heuristic, "reachable within this budget".  This comment is the definition; the numpy
+ * restatement (tests/travel_ref.py), the kernels and every binding refer to it.
+ *   grid      nx x ny x nz, linear index c = x * ny * nz + y * nz + z, fewer than 2^31 cells.
+ *   passable  a cell is passable exactly when vgt_hip_cast_segments in the corresponding mode would NOT call it a hit:
+ *               VGT_HIP_TRAVEL_OCCUPANCY  float occupancy; blocked when occ > 0.5f || (unknown_is_filled && occ == 0.5f).
+ *                                         A NaN is passable, +inf is blocked.
+ *               VGT_HIP_TRAVEL_SDF_ABOVE  float SDF; blocked when (double)value <= threshold (NaN passable, +-inf
+ *                                         compare as they are).  A NaN threshold is an invalid argument.  With the
+ *                                         threshold at the robot's radius this is the inflated map.
+ *             vgt_hip_cells_travel_cost: blocked is the filled predicate of vgt_hip_cells_sdf, occupancy (with
+ *             unknown_is_filled) AND (num_objects == 0 or the cell's object id is listed).
+ *   moves     the 26 neighbour offsets d fall into three classes by their number k = 1, 2, 3 of non-zero components.
+ *             weights[k - 1] (uint32) is the cost of a move of class k; 0 disables the class.  weights[0] > 0, every
+ *             weight <= 65535.  {1,0,0}: 6-connected step counts; {2,3,0}: 18-connected; {10,14,17}: the usual
+ *             quasi-Euclidean 26-connected costs.  A move a -> b = a + d is ALLOWED when its class is enabled, b is in
+ *             the grid and both cells are passable; with flags & VGT_HIP_TRAVEL_NO_CORNER_CUTTING additionally every
+ *             cell a + s, s_i in {0, d_i}, must be passable (the 2 x 2 or 2 x 2 x 2 block the move spans).  Both rules
+ *             are symmetric: cost-to-go and cost-from coincide.
+ *   sources   int32 sources[num_sources], linear indices; uint32 source_costs[num_sources] or NULL (all 0).  A source
+ *             outside [0, cells), on a blocked cell, or with an initial cost above cost_limit contributes nothing (not
+ *             an error).  Duplicates: the least initial cost.
+ *   cost      uint32 cost[c]: the least init(s) + sum of weights over all contributing sources s and all paths of
+ *             allowed moves from s to c, without wrap-around; VGT_HIP_TRAVEL_UNREACHED where c is blocked, unreachable,
+ *             or that least value exceeds cost_limit.  cost_limit <= 0xfffffffe, and that value means no limit.
+ *             Candidates are formed in 64 bits and dropped when above the limit, so nothing overflows, and the result
+ *             is exact (every prefix of a shortest path within the limit is within the limit).
+ *   toward    int32 toward[c], optional, built from the CONVERGED cost in a pass of its own: -1 where cost[c] is
+ *             UNREACHED; else the first b, over the offsets (dx, dy, dz) in ascending lexicographic order of -1, 0, 1,
+ *             such that the move c -> b is allowed and cost[b] + weight == cost[c]; -1 when there is none; and, applied
+ *             last, c itself where c is a contributing source with init(c) == cost[c] (a ROOT).  Enabled weights are
+ *             positive, so following toward strictly lowers the cost and ends at a root.
+ *   num_reached  int64, optional: the number of cells with cost != VGT_HIP_TRAVEL_UNREACHED.
+ * The cost field is the unique fixed point of the relaxation and toward a pure function of it: no output depends on
+ * launch order, on where atomics land or on how often a tile is revisited.
+ *   method    cost is relaxed by tiles of 8 x 8 x 16 cells (Z fastest) in rounds, one launch each; after a round the
+ *             host reads ONE word, "some tile is active", and stops when it is zero.  A round in which anything fell
+ *             lowers at least one cell of a field of integers bounded below, so the rounds end.  The loop is bounded all
+ *             the same: a tile is re-run only because one of its at most 26 neighbours or a seed flagged it, so after
+ *             tiles * 27 + 2 rounds with something still active the call ends with VGT_HIP_ERR_RUNTIME.  That cannot
+ *             happen in a correct build; the bound is there so that a defect ends the call instead of spinning.
+ *   vgt_hip_travel_cost        field, sources and outputs in host memory; blocking.
+ *   vgt_hip_travel_cost_dev    everything in device memory (e.g. the output of vgt_hip_sdf_dev); only num_reached is a
+ *                              host pointer.  workspace_dev: what vgt_hip_travel_cost_workspace_bytes says for the grid (0
+ *                              for an empty grid or one over the limits): 1 bit per cell, two 4-byte flags per tile,
+ *                              32 bytes of status.  A smaller workspace_bytes is an invalid argument.  The call copies nothing but
+ *                              one word per round, SYNCHRONISES the context's stream every round, and returns when the
+ *                              field has converged and every output is complete.  The first 32 bytes of the workspace
+ *                              then hold uint32 {0, 0, rounds, 0}, uint64 reached, uint64 tile runs over all rounds.
+ *   vgt_hip_cells_travel_cost  uploaded cell records (all map types), outputs to host memory.
+ * Errors, VGT_HIP_ERR_INVALID_ARGUMENT before any device work and with the outputs untouched: a NULL required pointer
+ * (context, field, weights, cost; sources when num_sources > 0), a negative extent, 2^31 cells or more, an unknown mode
+ * or flag bit, a NaN threshold in SDF mode, weights[0] == 0, a weight above 65535, cost_limit == 0xffffffff,
+ * num_sources < 0.  An empty grid succeeds (num_reached = 0, nothing else written); num_sources == 0 succeeds and writes
+ * UNREACHED and -1 everywhere.
+ *
+ * Path tracing follows toward for a batch of starts on the device, so that the 4 B / voxel field need not come home.
+ * starts int32[num_starts]; max_cells >= 1; start i writes the cells of its path, start first and root last, to
+ * paths[i * max_cells + k], k < lengths[i]; slots beyond lengths[i] are left untouched.  status[i] (uint8):
+ *   VGT_HIP_TRACE_OK         ended at a root (toward[c] == c).
+ *   VGT_HIP_TRACE_UNREACHED  toward[start] == -1; length 0.
+ *   VGT_HIP_TRACE_TRUNCATED  max_cells cells written and no root yet (also what bounds a malformed, cyclic toward).
+ *   VGT_HIP_TRACE_INVALID    the start is outside [0, num_cells), or an entry read on the way is outside
+ *                            [-1, num_cells) or is -1 after the start; the length is what was written before it.
+ * One lane per start.  Errors (VGT_HIP_ERR_INVALID_ARGUMENT, before any device work): a NULL pointer (starts only when
+ * num_starts > 0), num_cells < 0 or >= 2^31, num_starts < 0, max_cells < 1.  vgt_hip_trace_paths_dev enqueues on the
+ * context's stream and does not wait. */
+#define VGT_HIP_TRAVEL_OCCUPANCY 0
+#define VGT_HIP_TRAVEL_SDF_ABOVE 1
+#define VGT_HIP_TRAVEL_NO_CORNER_CUTTING 1u
+#define VGT_HIP_TRAVEL_UNREACHED 0xffffffffu
+#define VGT_HIP_TRACE_OK 0
+#define VGT_HIP_TRACE_UNREACHED 1
+#define VGT_HIP_TRACE_TRUNCATED 2
+#define VGT_HIP_TRACE_INVALID 3
+size_t vgt_hip_travel_cost_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int vgt_hip_travel_cost(vgt_hip_ctx* ctx, const float* field_host, int64_t nx, int64_t ny, int64_t nz, int32_t mode,
+                        int unknown_is_filled, double threshold, const uint32_t* weights, uint32_t flags,
+                        const int32_t* sources_host, const uint32_t* source_costs_host, int64_t num_sources,
+                        uint32_t cost_limit, uint32_t* cost_host, int32_t* toward_host, int64_t* num_reached);
+int vgt_hip_travel_cost_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t nx, int64_t ny, int64_t nz, int32_t mode,
+                            int unknown_is_filled, double threshold, const uint32_t* weights, uint32_t flags,
+                            const int32_t* sources_dev, const uint32_t* source_costs_dev, int64_t num_sources,
+                            uint32_t cost_limit, uint32_t* cost_dev, int32_t* toward_dev, int64_t* num_reached,
+                            void* workspace_dev, size_t workspace_bytes);
+int vgt_hip_cells_travel_cost(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* objects_to_use,
+                              int64_t num_objects, int unknown_is_filled, const uint32_t* weights, uint32_t flags,
+                              const int32_t* sources_host, const uint32_t* source_costs_host, int64_t num_sources,
+                              uint32_t cost_limit, uint32_t* cost_host, int32_t* toward_host, int64_t* num_reached);
+int vgt_hip_trace_paths(vgt_hip_ctx* ctx, const int32_t* toward_host, int64_t num_cells, const int32_t* starts_host,
+                        int64_t num_starts, int32_t max_cells, int32_t* paths_host, int32_t* lengths_host,
+                        uint8_t* status_host);
+int vgt_hip_trace_paths_dev(vgt_hip_ctx* ctx, const int32_t* toward_dev, int64_t num_cells, const int32_t* starts_dev,
+                            int64_t num_starts, int32_t max_cells, int32_t* paths_dev, int32_t* lengths_dev,
+                            uint8_t* status_dev);
+
 /* ---- holes and voids per component: ComputeComponentTopology (I/topology_computation.hpp:331-670, called from
  * S/occupancy_component_map.cpp:594-653 and S/tagged_object_occupancy_component_map.cpp:566-625).
  * The reference walks hash sets per component; its result is this closed form, computed by csrc/topology_kernels.hip.

@@ -102,6 +102,15 @@ SIGNATURES = {
     "vgt_hip_extract_surface_dev": (_int, [_p, _p, _i64, _i64, _i64, _f32, _int, _f64, _p, _p, _p, _i64, _p, _i64, _p,
                                            _p]),
     "vgt_hip_cells_extract_surface": (_int, [_p, _p, _f64, _p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "vgt_hip_travel_cost_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
+    "vgt_hip_travel_cost": (_int, [_p, _p, _i64, _i64, _i64, _i32, _int, _f64, _p, ctypes.c_uint32, _p, _p, _i64,
+                                   ctypes.c_uint32, _p, _p, _p]),
+    "vgt_hip_travel_cost_dev": (_int, [_p, _p, _i64, _i64, _i64, _i32, _int, _f64, _p, ctypes.c_uint32, _p, _p, _i64,
+                                       ctypes.c_uint32, _p, _p, _p, _p, _sz]),
+    "vgt_hip_cells_travel_cost": (_int, [_p, _p, _p, _i64, _int, _p, ctypes.c_uint32, _p, _p, _i64, ctypes.c_uint32, _p,
+                                         _p, _p]),
+    "vgt_hip_trace_paths": (_int, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "vgt_hip_trace_paths_dev": (_int, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "vgt_hip_component_topology_dev": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, ctypes.c_uint32, _p]),
     "vgt_hip_component_topology": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_uint64]),
     "vgt_hip_cells_component_topology": (_int, [_p, _p, _int, _int, _p, _p, _p, ctypes.c_uint64]),
@@ -292,6 +301,28 @@ def _topology_table(call, capacity=256):
         check(rc)
         return table[:count.value + 1].copy()
     raise VgtHipError("the component count changed between two calls")
+
+
+TRAVEL_OCCUPANCY, TRAVEL_SDF_ABOVE = 0, 1
+TRAVEL_NO_CORNER_CUTTING = 1
+TRAVEL_UNREACHED = 0xffffffff
+TRAVEL_NO_LIMIT = 0xfffffffe
+TRACE_OK, TRACE_UNREACHED, TRACE_TRUNCATED, TRACE_INVALID = 0, 1, 2, 3
+
+
+def travel_cost_workspace_bytes(shape):
+    """vgt_hip_travel_cost_workspace_bytes: 0 for an empty grid or one over the limits."""
+    return int(load().vgt_hip_travel_cost_workspace_bytes(*[int(s) for s in shape]))
+
+
+def _travel_sources(sources, source_costs):
+    src = np.ascontiguousarray(np.asarray(sources, dtype=np.int32).reshape(-1))
+    costs = None
+    if source_costs is not None:
+        costs = np.ascontiguousarray(np.asarray(source_costs, dtype=np.uint32).reshape(-1))
+        if costs.size != src.size:
+            raise ValueError("one initial cost per source")
+    return src, costs
 
 
 def _surface_mesh(call, with_cells):
@@ -622,6 +653,58 @@ class Context:
             call(vertices.data_ptr(), cells.data_ptr() if with_cells else None, len(vertices), triangles.data_ptr(),
                  len(triangles))
         return (vertices, triangles, cells) if with_cells else (vertices, triangles)
+
+    def travel_cost(self, field, sources, weights=(10, 14, 17), mode=TRAVEL_OCCUPANCY, unknown_is_filled=True,
+                    threshold=0.0, no_corner_cutting=False, source_costs=None, cost_limit=TRAVEL_NO_LIMIT,
+                    with_toward=True):
+        """vgt_hip_travel_cost: the least cost from the sources (linear indices) to every cell through passable cells
+        (include/vgt_hip.h states the rules) -> (cost uint32 (nx, ny, nz), toward int32 or None, num_reached)."""
+        f = np.ascontiguousarray(field, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("field must be an (nx, ny, nz) grid")
+        src, costs = _travel_sources(sources, source_costs)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.uint32).reshape(3))
+        cost = np.empty(f.shape, dtype=np.uint32)
+        toward = np.empty(f.shape, dtype=np.int32) if with_toward else None
+        reached = ctypes.c_int64(0)
+        check(self._lib.vgt_hip_travel_cost(
+            self.handle, _ptr(f), *f.shape, int(mode), int(bool(unknown_is_filled)), float(threshold), _ptr(w),
+            TRAVEL_NO_CORNER_CUTTING if no_corner_cutting else 0, _ptr(src), _ptr(costs), src.size, int(cost_limit),
+            _ptr(cost), _ptr(toward), ctypes.byref(reached)))
+        return cost, toward, int(reached.value)
+
+    def travel_cost_dev(self, field_ptr, shape, sources_ptr, num_sources, cost_ptr, ws_ptr, ws_bytes, toward_ptr=None,
+                        source_costs_ptr=None, weights=(10, 14, 17), mode=TRAVEL_OCCUPANCY, unknown_is_filled=True,
+                        threshold=0.0, no_corner_cutting=False, cost_limit=TRAVEL_NO_LIMIT):
+        """vgt_hip_travel_cost_dev: field, sources, outputs and workspace on the device -> num_reached.  Synchronises
+        the context's stream; the outputs are complete when it returns."""
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.uint32).reshape(3))
+        reached = ctypes.c_int64(0)
+        check(self._lib.vgt_hip_travel_cost_dev(
+            self.handle, _ptr(field_ptr), *[int(c) for c in shape], int(mode), int(bool(unknown_is_filled)),
+            float(threshold), _ptr(w), TRAVEL_NO_CORNER_CUTTING if no_corner_cutting else 0, _ptr(sources_ptr),
+            _ptr(source_costs_ptr), int(num_sources), int(cost_limit), _ptr(cost_ptr), _ptr(toward_ptr),
+            ctypes.byref(reached), _ptr(ws_ptr), int(ws_bytes)))
+        return int(reached.value)
+
+    def trace_paths(self, toward, starts, max_cells, fill=-1):
+        """vgt_hip_trace_paths: follows `toward` from every start -> (paths int32 [N, max_cells], pre-filled with `fill`
+        beyond each length, lengths int32 [N], status uint8 [N] (TRACE_*))."""
+        t = np.ascontiguousarray(toward, dtype=np.int32).reshape(-1)
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.int32).reshape(-1))
+        paths = np.full((st.size, max(int(max_cells), 0)), fill, dtype=np.int32)
+        lengths = np.zeros(st.size, dtype=np.int32)
+        status = np.zeros(st.size, dtype=np.uint8)
+        check(self._lib.vgt_hip_trace_paths(self.handle, _ptr(t), t.size, _ptr(st), st.size, int(max_cells), _ptr(paths),
+                                            _ptr(lengths), _ptr(status)))
+        return paths, lengths, status
+
+    def trace_paths_dev(self, toward_ptr, num_cells, starts_ptr, num_starts, max_cells, paths_ptr, lengths_ptr,
+                        status_ptr):
+        """vgt_hip_trace_paths_dev: everything on the device; enqueued on the context's stream."""
+        check(self._lib.vgt_hip_trace_paths_dev(self.handle, _ptr(toward_ptr), int(num_cells), _ptr(starts_ptr),
+                                                int(num_starts), int(max_cells), _ptr(paths_ptr), _ptr(lengths_ptr),
+                                                _ptr(status_ptr)))
 
     def component_topology(self, occupancy, component_types, with_labels=False):
         """ComputeComponentTopology of an occupancy grid (it labels the grid first): a COMPONENT_TOPOLOGY array with one
@@ -1261,6 +1344,22 @@ class Cells:
                 vertex_capacity, _ptr(triangles), triangle_capacity, nv, nt)
 
         return _surface_mesh(call, with_cells)
+
+    def travel_cost(self, sources, weights=(10, 14, 17), objects_to_use=(), unknown_is_filled=True,
+                    no_corner_cutting=False, source_costs=None, cost_limit=TRAVEL_NO_LIMIT, with_toward=True):
+        """vgt_hip_cells_travel_cost: Context.travel_cost on the uploaded cells; blocked is the filled predicate of
+        sdf() -> (cost, toward or None, num_reached)."""
+        objs = np.ascontiguousarray(np.asarray(list(objects_to_use), dtype=np.uint32))
+        src, costs = _travel_sources(sources, source_costs)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.uint32).reshape(3))
+        cost = np.empty(self.shape, dtype=np.uint32)
+        toward = np.empty(self.shape, dtype=np.int32) if with_toward else None
+        reached = ctypes.c_int64(0)
+        check(self._lib.vgt_hip_cells_travel_cost(
+            self.ctx.handle, self.handle, _ptr(objs) if objs.size else None, objs.size, int(bool(unknown_is_filled)),
+            _ptr(w), TRAVEL_NO_CORNER_CUTTING if no_corner_cutting else 0, _ptr(src), _ptr(costs), src.size,
+            int(cost_limit), _ptr(cost), _ptr(toward), ctypes.byref(reached)))
+        return cost, toward, int(reached.value)
 
     def component_topology(self, component_types, connect_across_objects=False, with_labels=False):
         """ComputeComponentTopology of the uploaded cells: the COMPONENT_TOPOLOGY table of Context.component_topology;

@@ -3424,6 +3424,256 @@ int vgt_hip_cells_extract_surface(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double
   return RunSurfaceToHost(ctx, grid, b);
 }
 
+/* ------------------------- cost-to-go through free space, path tracing ------------------------- */
+
+namespace
+{
+bool TravelShapeWithinLimits(int64_t nx, int64_t ny, int64_t nz)
+{
+  constexpr int64_t kLimit = 0x7fffffffLL;
+  if (nx < 0 || ny < 0 || nz < 0) return false;
+  if (nx == 0 || ny == 0 || nz == 0) return true;
+  return nx <= kLimit && ny <= kLimit && nz <= kLimit && nx * ny <= kLimit && nx * ny * nz <= kLimit;
+}
+
+// Everything that can be said about a cost-to-go call before any HIP call (the context is not looked into).  mode: null
+// for cell records, which have no field mode.
+int CheckTravelArguments(const vgt_hip_ctx* ctx, const void* field, int64_t nx, int64_t ny, int64_t nz,
+                         const int32_t* mode, double threshold, const uint32_t* weights, uint32_t flags,
+                         const int32_t* sources, int64_t num_sources, uint32_t cost_limit, const uint32_t* cost,
+                         vgt::TravelGrid* grid)
+{
+  if (!ctx || !field || !weights || !cost) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_sources < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the number of sources must not be negative");
+  if (num_sources > 0 && !sources) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (nx < 0 || ny < 0 || nz < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must not be negative");
+  if (!TravelShapeWithinLimits(nx, ny, nz))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "travel costs support grids below 2^31 cells");
+  if (mode && *mode != VGT_HIP_TRAVEL_OCCUPANCY && *mode != VGT_HIP_TRAVEL_SDF_ABOVE)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown travel-cost mode");
+  if (flags & ~VGT_HIP_TRAVEL_NO_CORNER_CUTTING) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown travel-cost flag");
+  if (mode && *mode == VGT_HIP_TRAVEL_SDF_ABOVE && std::isnan(threshold))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the SDF threshold must be a number");
+  if (weights[0] == 0u) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "weights[0] (the axis moves) must be greater than zero");
+  if (weights[0] > 65535u || weights[1] > 65535u || weights[2] > 65535u)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a move weight must be at most 65535");
+  if (cost_limit == VGT_HIP_TRAVEL_UNREACHED)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the cost limit must be at most 0xfffffffe (which means no limit)");
+  *grid = vgt::TravelGrid{static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz),
+                          {weights[0], weights[1], weights[2]}, flags, cost_limit};
+  return VGT_HIP_OK;
+}
+
+int TravelSourceOf(int32_t mode)
+{
+  return mode == VGT_HIP_TRAVEL_OCCUPANCY ? vgt::kTravelFromOccupancy : vgt::kTravelFromSdf;
+}
+
+// Seeds, runs the rounds until no tile is active (one word read back per round), then `toward` and the count.  Every
+// buffer is on the device; the stream is idle when this returns.  Caller holds the context mutex and has set the device.
+int RunTravelCost(hipStream_t s, const void* field_dev, int source, int unknown_is_filled, double threshold,
+                  const vgt::TravelGrid& grid, const int32_t* sources_dev, const uint32_t* source_costs_dev,
+                  int64_t num_sources, uint32_t* cost_dev, int32_t* toward_dev, int64_t* num_reached,
+                  void* workspace_dev)
+{
+  const char* what = "travel cost";
+  const vgt::TravelWorkspace w = vgt::CarveTravelWorkspace(grid.nx, grid.ny, grid.nz);
+  auto* const status_dev = reinterpret_cast<vgt::TravelStatus*>(static_cast<char*>(workspace_dev) + w.status_offset);
+  hipError_t err = vgt::LaunchTravelSeed(field_dev, source, unknown_is_filled, threshold, grid, sources_dev,
+                                         source_costs_dev, num_sources, cost_dev, workspace_dev, s);
+  // (see vgt_hip.h: a tile runs again only when a neighbour or a seed flagged it)
+  const int64_t most_rounds = w.tiles * 27 + 2;
+  int64_t round = 0;
+  for (bool active = num_sources > 0; active && err == hipSuccess; round++)
+  {
+    if (round == most_rounds)
+    {
+      (void)hipStreamSynchronize(s);
+      return Fail(VGT_HIP_ERR_RUNTIME, "[travel cost] tiles are still active after tiles * 27 + 2 rounds");
+    }
+    err = vgt::LaunchTravelRound(grid, cost_dev, workspace_dev, round, s);
+    uint32_t next_active = 0;
+    err = ReadBack(s, err, &next_active, &status_dev->active[(round + 1) & 1]);
+    active = next_active != 0u;
+  }
+  if (err == hipSuccess && (toward_dev || num_reached))
+    err = vgt::LaunchTravelToward(grid, sources_dev, source_costs_dev, num_sources, cost_dev, toward_dev, workspace_dev, s);
+  const uint32_t rounds = static_cast<uint32_t>(round);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&status_dev->rounds, &rounds, sizeof(rounds), hipMemcpyHostToDevice, s);
+  unsigned long long reached = 0;
+  VGT_TRY_HIP(ReadBack(s, err, &reached, &status_dev->reached), what);
+  if (num_reached) *num_reached = static_cast<int64_t>(reached);
+  return VGT_HIP_OK;
+}
+
+int CheckTraceArguments(const vgt_hip_ctx* ctx, const int32_t* toward, int64_t num_cells, const int32_t* starts,
+                        int64_t num_starts, int32_t max_cells, const int32_t* paths, const int32_t* lengths,
+                        const uint8_t* status)
+{
+  if (!ctx || !toward || !paths || !lengths || !status) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_starts < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the number of starts must not be negative");
+  if (num_starts > 0 && !starts) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_cells < 0 || num_cells >= 0x80000000LL)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "path tracing supports grids below 2^31 cells");
+  if (max_cells < 1) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "max_cells must be at least 1");
+  return VGT_HIP_OK;
+}
+}  // namespace
+
+size_t vgt_hip_travel_cost_workspace_bytes(int64_t nx, int64_t ny, int64_t nz)
+{
+  if (!TravelShapeWithinLimits(nx, ny, nz) || nx * ny * nz == 0) return 0;
+  return vgt::CarveTravelWorkspace(nx, ny, nz).bytes;
+}
+
+int vgt_hip_travel_cost_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t nx, int64_t ny, int64_t nz, int32_t mode,
+                            int unknown_is_filled, double threshold, const uint32_t* weights, uint32_t flags,
+                            const int32_t* sources_dev, const uint32_t* source_costs_dev, int64_t num_sources,
+                            uint32_t cost_limit, uint32_t* cost_dev, int32_t* toward_dev, int64_t* num_reached,
+                            void* workspace_dev, size_t workspace_bytes)
+{
+  vgt::TravelGrid grid;
+  const int rc = CheckTravelArguments(ctx, field_dev, nx, ny, nz, &mode, threshold, weights, flags,
+                                      sources_dev, num_sources, cost_limit, cost_dev, &grid);
+  if (rc != VGT_HIP_OK) return rc;
+  if (nx * ny * nz == 0)
+  {
+    if (num_reached) *num_reached = 0;
+    return VGT_HIP_OK;
+  }
+  if (!workspace_dev) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (workspace_bytes < vgt::CarveTravelWorkspace(nx, ny, nz).bytes)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "travel-cost workspace too small");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  return RunTravelCost(ctx->stream, field_dev, TravelSourceOf(mode), unknown_is_filled ? 1 : 0, threshold, grid,
+                       sources_dev, source_costs_dev, num_sources, cost_dev, toward_dev, num_reached, workspace_dev);
+}
+
+int vgt_hip_travel_cost(vgt_hip_ctx* ctx, const float* field_host, int64_t nx, int64_t ny, int64_t nz, int32_t mode,
+                        int unknown_is_filled, double threshold, const uint32_t* weights, uint32_t flags,
+                        const int32_t* sources_host, const uint32_t* source_costs_host, int64_t num_sources,
+                        uint32_t cost_limit, uint32_t* cost_host, int32_t* toward_host, int64_t* num_reached)
+{
+  vgt::TravelGrid grid;
+  const int rc = CheckTravelArguments(ctx, field_host, nx, ny, nz, &mode, threshold, weights, flags,
+                                      sources_host, num_sources, cost_limit, cost_host, &grid);
+  if (rc != VGT_HIP_OK) return rc;
+  if (nx * ny * nz == 0)
+  {
+    if (num_reached) *num_reached = 0;
+    return VGT_HIP_OK;
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t n = static_cast<size_t>(nx * ny * nz), q = static_cast<size_t>(num_sources);
+  vgt::HostStaging staging;
+  const auto field = staging.In(field_host, n);
+  const auto sources = staging.In(sources_host, q);
+  const auto source_costs = staging.In(source_costs_host, q);
+  const auto cost = staging.Out(cost_host, n);
+  const auto toward = staging.Out(toward_host, n);
+  const auto workspace = staging.Scratch(vgt::CarveTravelWorkspace(nx, ny, nz).bytes);
+  int64_t reached = 0;
+  const int result = staging.Run(*ctx, "travel cost", FailHip, [&](hipStream_t s) {
+    return RunTravelCost(s, field.dev(), TravelSourceOf(mode), unknown_is_filled ? 1 : 0, threshold, grid, sources.dev(),
+                         source_costs.dev(), num_sources, cost.dev(), toward.dev(), &reached, workspace.dev());
+  });
+  if (result == VGT_HIP_OK && num_reached) *num_reached = reached;
+  return result;
+}
+
+int vgt_hip_cells_travel_cost(vgt_hip_ctx* ctx, vgt_hip_cells* cells, const uint32_t* objects_to_use,
+                              int64_t num_objects, int unknown_is_filled, const uint32_t* weights, uint32_t flags,
+                              const int32_t* sources_host, const uint32_t* source_costs_host, int64_t num_sources,
+                              uint32_t cost_limit, uint32_t* cost_host, int32_t* toward_host, int64_t* num_reached)
+{
+  int rc = CheckCells(ctx, cells);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_objects < 0 || (num_objects > 0 && !objects_to_use)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_objects > 0 && cells->object_id_offset < 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "this cell type carries no object id");
+  vgt::TravelGrid grid;
+  rc = CheckTravelArguments(ctx, cells, cells->nx, cells->ny, cells->nz, nullptr, 0.0, weights, flags, sources_host,
+                            num_sources, cost_limit, cost_host, &grid);
+  if (rc != VGT_HIP_OK) return rc;
+  const int64_t cells_total = cells->nx * cells->ny * cells->nz;
+  if (cells_total == 0)
+  {
+    if (num_reached) *num_reached = 0;
+    return VGT_HIP_OK;
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "travel cost of a tagged map";
+  // (sorted and distinct, as vgt_hip_cells_sdf hands the list to the same predicate kernel)
+  std::vector<uint32_t> objects(objects_to_use, objects_to_use + num_objects);
+  std::sort(objects.begin(), objects.end());
+  objects.erase(std::unique(objects.begin(), objects.end()), objects.end());
+  const size_t n = static_cast<size_t>(cells_total), q = static_cast<size_t>(num_sources);
+  vgt::HostStaging staging;
+  const auto sources = staging.In(sources_host, q);
+  const auto source_costs = staging.In(source_costs_host, q);
+  const auto cost = staging.Out(cost_host, n);
+  const auto toward = staging.Out(toward_host, n);
+  const auto workspace = staging.Scratch(vgt::CarveTravelWorkspace(cells->nx, cells->ny, cells->nz).bytes);
+  int64_t reached = 0;
+  const int result = staging.Run(*ctx, what, FailHip, [&](hipStream_t s) -> int {
+    const int grown = GrowCache(s, &cells->objects, objects.size() * sizeof(uint32_t),
+                                "drain before regrowing object list", "allocate object list");
+    if (grown != VGT_HIP_OK) return grown;
+    if (!objects.empty())  // (pageable source: staged when the call returns)
+      VGT_TRY_HIP(hipMemcpyAsync(cells->objects.data(), objects.data(), objects.size() * sizeof(uint32_t),
+                                 hipMemcpyHostToDevice, s),
+                  what);
+    VGT_TRY_HIP(vgt::LaunchCellMask(cells->records.as<void>(), cells_total, cells->cell_bytes, cells->object_id_offset,
+                                    objects.empty() ? 0 : 1, cells->objects.as<uint32_t>(),
+                                    static_cast<int>(objects.size()), unknown_is_filled ? 1 : 0,
+                                    cells->mask.as<uint8_t>(), s),
+                what);
+    return RunTravelCost(s, cells->mask.as<uint8_t>(), vgt::kTravelFromMask, 0, 0.0, grid, sources.dev(),
+                         source_costs.dev(), num_sources, cost.dev(), toward.dev(), &reached, workspace.dev());
+  });
+  if (result == VGT_HIP_OK && num_reached) *num_reached = reached;
+  return result;
+}
+
+int vgt_hip_trace_paths_dev(vgt_hip_ctx* ctx, const int32_t* toward_dev, int64_t num_cells, const int32_t* starts_dev,
+                            int64_t num_starts, int32_t max_cells, int32_t* paths_dev, int32_t* lengths_dev,
+                            uint8_t* status_dev)
+{
+  const int rc = CheckTraceArguments(ctx, toward_dev, num_cells, starts_dev, num_starts, max_cells, paths_dev,
+                                     lengths_dev, status_dev);
+  if (rc != VGT_HIP_OK || num_starts == 0) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(vgt::LaunchTracePaths(toward_dev, num_cells, starts_dev, num_starts, max_cells, paths_dev, lengths_dev,
+                                    status_dev, ctx->stream),
+              "trace paths");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_trace_paths(vgt_hip_ctx* ctx, const int32_t* toward_host, int64_t num_cells, const int32_t* starts_host,
+                        int64_t num_starts, int32_t max_cells, int32_t* paths_host, int32_t* lengths_host,
+                        uint8_t* status_host)
+{
+  const int rc = CheckTraceArguments(ctx, toward_host, num_cells, starts_host, num_starts, max_cells, paths_host,
+                                     lengths_host, status_host);
+  if (rc != VGT_HIP_OK || num_starts == 0) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const size_t q = static_cast<size_t>(num_starts);
+  vgt::HostStaging staging;
+  const auto toward = staging.In(toward_host, static_cast<size_t>(num_cells));
+  const auto starts = staging.In(starts_host, q);
+  // (up and down: the slots beyond a path's length come back as the caller gave them)
+  const auto paths = staging.InOut(paths_host, q * static_cast<size_t>(max_cells));
+  const auto lengths = staging.Out(lengths_host, q);
+  const auto status = staging.Out(status_host, q);
+  return staging.Run(*ctx, "trace paths", FailHip, [&](hipStream_t s) {
+    return HipResult("trace paths", vgt::LaunchTracePaths(toward.dev(), num_cells, starts.dev(), num_starts, max_cells,
+                                                          paths.dev(), lengths.dev(), status.dev(), s));
+  });
+}
+
 /* ------------------------- holes and voids per component ------------------------- */
 
 static_assert(sizeof(vgt_hip_component_topology_t) == 32 &&

@@ -360,6 +360,51 @@ const SurfaceCounts* SurfaceCountsPtr(const void* scratch_dev, int64_t num_cells
 hipError_t LaunchSurfaceMark(const SurfaceGrid& grid, void* scratch_dev, hipStream_t stream);
 hipError_t LaunchSurfaceEmit(const SurfaceGrid& grid, const SurfaceOutput& out, void* scratch_dev, hipStream_t stream);
 
+// --- launchers (travel_kernels.hip): cost-to-go through free space, `toward`, path tracing ---
+// The rules: include/vgt_hip.h, vgt_hip_travel_cost.  Grids below 2^31 cells.
+// The tile a workgroup relaxes in LDS (Z fastest); DESIGN.md 4i says why these extents.
+constexpr int kTravelTileX = 8, kTravelTileY = 8, kTravelTileZ = 16;
+// What the passable bit plane is made from: float occupancy, a float SDF against a threshold, a uint8 filled mask.
+constexpr int kTravelFromOccupancy = 0, kTravelFromSdf = 1, kTravelFromMask = 2;
+constexpr uint8_t kTraceOk = 0, kTraceUnreached = 1, kTraceTruncated = 2, kTraceInvalid = 3;
+struct TravelGrid
+{
+  int nx, ny, nz;
+  uint32_t weights[3];
+  uint32_t flags;
+  uint32_t cost_limit;
+};
+// The head of the workspace.  active[r & 1]: some tile must run in round r; reached: cells with a cost, added up by
+// LaunchTravelToward; tiles_run: tiles that ran, over all rounds (what a measurement divides by rounds * tiles).
+struct TravelStatus
+{
+  uint32_t active[2];
+  uint32_t rounds;  // stored by the host loop when it ends
+  uint32_t reserved;
+  unsigned long long reached;
+  unsigned long long tiles_run;
+};
+struct TravelWorkspace
+{
+  size_t status_offset, flags_offset[2], words_offset, bytes;
+  int64_t tiles;
+};
+TravelWorkspace CarveTravelWorkspace(int64_t nx, int64_t ny, int64_t nz);
+// Zeroes the workspace's head, fills cost with UNREACHED, classifies `field_dev` (kTravelFrom...) into the bit plane and
+// seeds the sources.  Then LaunchTravelRound for round = 0, 1, ... while TravelStatus::active[(round + 1) & 1], read
+// after the round, is non-zero; then LaunchTravelToward (toward_dev may be null: it only counts the reached cells).
+hipError_t LaunchTravelSeed(const void* field_dev, int source, int unknown_is_filled, double threshold,
+                            const TravelGrid& grid, const int32_t* sources_dev, const uint32_t* source_costs_dev,
+                            int64_t num_sources, uint32_t* cost_dev, void* workspace_dev, hipStream_t stream);
+hipError_t LaunchTravelRound(const TravelGrid& grid, uint32_t* cost_dev, void* workspace_dev, int64_t round,
+                             hipStream_t stream);
+hipError_t LaunchTravelToward(const TravelGrid& grid, const int32_t* sources_dev, const uint32_t* source_costs_dev,
+                              int64_t num_sources, const uint32_t* cost_dev, int32_t* toward_dev, void* workspace_dev,
+                              hipStream_t stream);
+hipError_t LaunchTracePaths(const int32_t* toward_dev, int64_t cells, const int32_t* starts_dev, int64_t num_starts,
+                            int32_t max_cells, int32_t* paths_dev, int32_t* lengths_dev, uint8_t* status_dev,
+                            hipStream_t stream);
+
 // --- launchers (topology_kernels.hip): holes and voids per component ---
 // One entry per label, the layout of vgt_hip_component_topology_t (include/vgt_hip.h).
 struct ComponentTopologyEntry
