@@ -266,6 +266,9 @@ int vgt_hip_testing_set_host_pipeline_min_voxels(int64_t min_voxels);
  * whatever the number of items: lets the tests and benches run either formulation on any length.  Negative: back to the
  * product's rule (64 rows; the Y pass of launches of at most 1024 items: 128). */
 int vgt_hip_testing_set_short_line_rows(int rows);
+/* At most `workgroups` workgroups per launch of vgt_hip_check_spheres[_dev] (process-wide), so that a few configurations
+ * already make its persistent waves stride; 0 or negative: back to the product's limit. */
+int vgt_hip_testing_set_check_spheres_workgroups(int workgroups);
 /* Pass 1 alone, for a test of the record format itself (csrc/vgt_internal.hpp, ClassRecord): the class records of a
  * device-resident occupancy grid, [x][64-voxel word][y] x 4 uint32 (mask_lo, mask_hi, below2, above2), into records_dev
  * (vgt_hip_testing_class_record_bytes bytes); summary_dev (optional): the 4-byte slab summaries per line, in which case the
@@ -489,6 +492,67 @@ int vgt_hip_cast_segments_dev(vgt_hip_ctx* ctx, const float* field_dev, int64_t 
                               const double* grid_from_world, const double* segments_dev, int64_t num_segments,
                               uint8_t* status_dev, int32_t* hit_index_dev, double* hit_fraction_dev,
                               int32_t* cells_examined_dev, float* min_value_dev, int32_t* min_index_dev);
+
+/* ---- Sphere models checked against an SDF ----
+ * B configurations of a body modelled as S spheres attached to L links: for every configuration, how close the worst
+ * sphere comes to an obstacle, which sphere that is, and which way is out.  The collision check of a planner whose robot
+ * is not a point; forward kinematics stays with the caller (the call takes link poses, not joint angles).  Read-only.
+ * Inputs:
+ *   sphere_xyzr   4 doubles per sphere: the centre in its link's frame and the radius
+ *   sphere_link   one int32 per sphere, a value in [0, L); in any order
+ *   link_poses    [B][L][16] doubles, column-major: world_from_link, the memory of a std::vector<Eigen::Isometry3d> per
+ *                 configuration.  Only the elements 0-2, 4-6, 8-10 and 12-14 are read.
+ *   grid_from_world, rotation   as for vgt_hip_sdf_project_out_of_collision: 16 doubles column-major and 9 doubles
+ *                 row-major, each may be NULL, both host arrays in both forms.
+ * Per (configuration b, sphere s), in double and without contraction:
+ *   w_r       = ((m[r]*x + m[4+r]*y) + m[8+r]*z) + m[12+r] for r = 0, 1, 2, with m the pose of sphere_link[s] in
+ *               configuration b: the order of vgt_hip_cast_segments' transform.
+ *   d         = the estimate of vgt_hip_sdf_estimate_distance at w: the same code, grid_from_world applied as that
+ *               function applies it, the same has-value test (a non-finite w therefore has no value).
+ *   clearance = d - radius.
+ *   gradient  = the coarse gradient, edge gradients on and rotated by `rotation`, of the cell w lies in: what step 3 of
+ *               vgt_hip_sdf_project_out_of_collision takes.  NaN x3 where the sphere has no value or the gradient has none.
+ * Outputs per configuration (`status` is required, every other output may be NULL):
+ *   num_outside (int32)    spheres without a value (not in the grid)
+ *   num_below (int32)      spheres with a value and clearance <= minimum_clearance (the projection's comparison: NaN is
+ *                          never below, +-infinity compare as they are)
+ *   min_clearance (double), min_sphere (int32)   the least non-NaN clearance among the spheres with a value and the index
+ *                          of its sphere, ties to the lowest index; NaN and -1 when there is none
+ *   min_gradient (3 doubles)   `gradient` of min_sphere; NaN x3 when min_sphere == -1
+ *   status (uint8)         1 COLLISION: num_below > 0, or flags & VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION and
+ *                          num_outside > 0;  otherwise 0 CLEAR when min_sphere != -1;  otherwise 2 NO_VALUE: nothing was
+ *                          comparable.
+ * Outputs per sphere (each may be NULL): sphere_clearance [B][S], NaN without a value; sphere_gradient [B][S][3].
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer (ctx, sdf, status; the model's two arrays
+ * when S > 0; link_poses when S > 0 and B > 0), a resolution that is not positive and finite, a NaN minimum_clearance,
+ * an unknown flag bit, a negative extent or count, num_links == 0 with num_spheres > 0, a grid of 2^31 cells or more,
+ * 2^31 or more spheres, links or configurations, B * S >= 2^31; and, for the host form only, a sphere_link outside
+ * [0, L) or a radius that is negative or NaN: the message names the first such sphere ("sphere 17: ...").
+ * The device form cannot look at device memory: there a link outside [0, L) makes that sphere one "without a value",
+ * counted in num_outside, and the kernel forms no address from it; a negative or NaN radius is used as it is.
+ * B == 0, S == 0 and an empty grid succeed.  With S == 0 or an empty grid nothing is comparable: every configuration gets
+ * NaN and -1, num_below 0, num_outside 0 resp. S, and the status the rules above give (NO_VALUE; COLLISION for an empty
+ * grid with S > 0 under VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION); the host form then needs no device. */
+#define VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION 1u
+#define VGT_HIP_SPHERES_CLEAR 0
+#define VGT_HIP_SPHERES_COLLISION 1
+#define VGT_HIP_SPHERES_NO_VALUE 2
+int vgt_hip_check_spheres(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                          const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+                          const int32_t* sphere_link_host, int64_t num_spheres, const double* link_poses_host,
+                          int64_t num_links, int64_t num_configurations, double minimum_clearance, uint32_t flags,
+                          uint8_t* status_host, double* min_clearance_host, int32_t* min_sphere_host,
+                          int32_t* num_below_host, int32_t* num_outside_host, double* min_gradient_host,
+                          double* sphere_clearance_host, double* sphere_gradient_host);
+/* Same with every array on the device except the two transforms (e.g. the field straight after vgt_hip_sdf_dev, the
+ * poses straight out of a batched forward kinematics); enqueued on the context's stream, not blocking. */
+int vgt_hip_check_spheres_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                              double resolution, const double* grid_from_world, const double* rotation,
+                              const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                              const double* link_poses_dev, int64_t num_links, int64_t num_configurations,
+                              double minimum_clearance, uint32_t flags, uint8_t* status_dev, double* min_clearance_dev,
+                              int32_t* min_sphere_dev, int32_t* num_below_dev, int32_t* num_outside_dev,
+                              double* min_gradient_dev, double* sphere_clearance_dev, double* sphere_gradient_dev);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

@@ -80,6 +80,10 @@ SIGNATURES = {
                                      _p, _p, _p, _p, _p, _p]),
     "vgt_hip_cast_segments_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _i32, _int, _f64, ctypes.c_uint32, _p, _p, _i64,
                                          _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_spheres": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _f64,
+                                     ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_spheres_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _f64,
+                                         ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -160,6 +164,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_debug_finalize_check": (_int, [_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _p, _p]),
     "vgt_hip_testing_set_host_pipeline_min_voxels": (_int, [ctypes.c_int64]),
     "vgt_hip_testing_set_short_line_rows": (_int, [_int]),
+    "vgt_hip_testing_set_check_spheres_workgroups": (_int, [_int]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
 }
@@ -185,6 +190,12 @@ SEGMENT_HIT = 1
 SEGMENT_MISSED_GRID = 2
 SEGMENT_INVALID = 3
 
+# flag and statuses of check_spheres (VGT_HIP_SPHERES_*)
+SPHERES_OUTSIDE_IS_COLLISION = 1
+SPHERES_CLEAR = 0
+SPHERES_COLLISION = 1
+SPHERES_NO_VALUE = 2
+
 # selection rules, value classes and cell members of select_cells / Cells.select (VGT_HIP_SELECT_*, VGT_HIP_CLASS_*,
 # VGT_HIP_CELL_MEMBER_*)
 SELECT_ALL = 0
@@ -206,6 +217,12 @@ COMPONENT_TOPOLOGY = np.dtype([(name, np.int32) for name in (
 
 # what Context.cast_segments returns: one entry per segment; min_value / min_index are None unless asked for
 SegmentCasts = collections.namedtuple("SegmentCasts", "status hit_index hit_fraction cells_examined min_value min_index")
+
+
+# what Context.check_spheres returns: one entry per configuration; sphere_clearance [B, S] / sphere_gradient [B, S, 3]
+# are None unless per_sphere
+SphereChecks = collections.namedtuple(
+    "SphereChecks", "status min_clearance min_sphere num_below num_outside min_gradient sphere_clearance sphere_gradient")
 
 
 class VgtHipError(RuntimeError):
@@ -489,6 +506,55 @@ class Context:
             int(bool(unknown_is_filled)), float(threshold), SEGMENT_WALK_THROUGH if walk_through else 0, _ptr(xf),
             _ptr(segments_ptr), int(num_segments), _ptr(status_ptr), _ptr(hit_index_ptr), _ptr(hit_fraction_ptr),
             _ptr(cells_examined_ptr), _ptr(min_value_ptr), _ptr(min_index_ptr)))
+
+    def check_spheres(self, sdf, resolution, spheres_xyzr, sphere_link, link_poses, minimum_clearance=0.0,
+                      outside_is_collision=False, per_sphere=False, grid_from_world=None, rotation=None):
+        """vgt_hip_check_spheres: a model of S spheres (spheres_xyzr [S, 4]: centre in the link's frame and radius;
+        sphere_link [S]) in B configurations, link_poses [B, L, 16] (column-major world_from_link) or [B, L, 4, 4]
+        (world_from_link matrices, transposed to column-major here) -> SphereChecks(status uint8 (SPHERES_*),
+        min_clearance float64, min_sphere int32, num_below int32, num_outside int32, min_gradient [B, 3] float64,
+        sphere_clearance [B, S], sphere_gradient [B, S, 3]); the last two only per_sphere."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        poses = np.asarray(link_poses, dtype=np.float64)
+        if poses.ndim == 4:
+            if poses.shape[2:] != (4, 4):
+                raise ValueError("link_poses must have the shape [B, L, 16] or [B, L, 4, 4]")
+            poses = poses.transpose(0, 1, 3, 2).reshape(poses.shape[0], poses.shape[1], 16)
+        if poses.ndim != 3 or poses.shape[2] != 16:
+            raise ValueError("link_poses must have the shape [B, L, 16] or [B, L, 4, 4]")
+        poses = np.ascontiguousarray(poses)
+        b, links, s = poses.shape[0], poses.shape[1], len(xyzr)
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        out = SphereChecks(np.empty(b, np.uint8), np.empty(b, np.float64), np.empty(b, np.int32), np.empty(b, np.int32),
+                           np.empty(b, np.int32), np.empty((b, 3), np.float64),
+                           np.empty((b, s), np.float64) if per_sphere else None,
+                           np.empty((b, s, 3), np.float64) if per_sphere else None)
+        check(self._lib.vgt_hip_check_spheres(
+            self.handle, _ptr(f), *f.shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(xyzr), _ptr(link), s, _ptr(poses),
+            links, b, float(minimum_clearance), SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0,
+            *[_ptr(a) for a in out]))
+        return out
+
+    def check_spheres_dev(self, sdf_ptr, shape, resolution, spheres_xyzr_ptr, sphere_link_ptr, num_spheres,
+                          link_poses_ptr, num_links, num_configurations, status_ptr, min_clearance_ptr=None,
+                          min_sphere_ptr=None, num_below_ptr=None, num_outside_ptr=None, min_gradient_ptr=None,
+                          sphere_clearance_ptr=None, sphere_gradient_ptr=None, minimum_clearance=0.0,
+                          outside_is_collision=False, grid_from_world=None, rotation=None):
+        """vgt_hip_check_spheres_dev: field, model, poses and outputs on the device (the transforms are host arrays);
+        enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        check(self._lib.vgt_hip_check_spheres_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
+            _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr), int(num_spheres), _ptr(link_poses_ptr), int(num_links),
+            int(num_configurations), float(minimum_clearance), SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0,
+            _ptr(status_ptr), _ptr(min_clearance_ptr), _ptr(min_sphere_ptr), _ptr(num_below_ptr), _ptr(num_outside_ptr),
+            _ptr(min_gradient_ptr), _ptr(sphere_clearance_ptr), _ptr(sphere_gradient_ptr)))
 
     def sdf_coarse_gradient_dev(self, sdf_ptr, shape, resolution, gradient_ptr, has_value_ptr=None,
                                 enable_edge_gradients=False, rotation=None):
@@ -856,6 +922,11 @@ class Context:
         """Testing library only: lines of at most `rows` rows take the short-line kernels whatever the item count
         (0 = sweeps everywhere, negative = back to the product's rule)."""
         check(self._lib.vgt_hip_testing_set_short_line_rows(int(rows)))
+
+    def set_check_spheres_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per check_spheres launch (0 = back
+        to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_check_spheres_workgroups(int(workgroups)))
 
     def set_host_pipeline_min_voxels(self, min_voxels):
         """Testing library only (process-wide there): smallest grid the host-pointer SDF entry points pipeline."""

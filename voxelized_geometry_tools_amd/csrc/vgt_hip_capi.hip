@@ -155,6 +155,8 @@ thread_local std::string g_last_error;
 // What vgt_hip_testing_set_short_line_rows told the line passes (vgt::ShortLineOverride), -1 = nothing.  Only that hook
 // stores to it, and only the testing library has the hook.
 std::atomic<int> g_short_line_override{-1};
+// What vgt_hip_testing_set_check_spheres_workgroups told the sphere-model check, 0 = nothing (the launcher's own limit).
+std::atomic<int> g_check_spheres_workgroups{0};
 
 int Fail(int code, const std::string& msg)
 {
@@ -517,6 +519,73 @@ int CheckSegmentArguments(const vgt_hip_ctx* ctx, const float* field, int64_t nx
   query->flags = flags;
   return VGT_HIP_OK;
 }
+
+// What both sphere-model entry points are called with, and the checks both make before any device work.
+struct CheckSpheresArguments
+{
+  const float* sdf;
+  int64_t nx, ny, nz;
+  double resolution;
+  const double *grid_from_world, *rotation;
+  const double* sphere_xyzr;
+  const int32_t* sphere_link;
+  int64_t num_spheres;
+  const double* link_poses;
+  int64_t num_links, num_configurations;
+  double minimum_clearance;
+  uint32_t flags;
+  vgt::BodyOutputs out;
+
+  int64_t NumCells() const { return nx * ny * nz; }
+  int Check(const vgt_hip_ctx* ctx) const
+  {
+    if (num_spheres < 0 || num_links < 0 || num_configurations < 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the numbers of spheres, links and configurations must not be negative");
+    if (!ctx || !sdf || !out.status || (num_spheres > 0 && (!sphere_xyzr || !sphere_link)) ||
+        (num_spheres > 0 && num_configurations > 0 && !link_poses))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (nx < 0 || ny < 0 || nz < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must not be negative");
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Grid must have uniform, positive resolution");
+    // (extent by extent: the product of three int64 extents can overflow)
+    const int64_t most = 0x7fffffffLL;
+    if (nx > most || ny > most || nz > most || (nx > 0 && ny > 0 && nz > 0 && (nx * ny > most || nx * ny * nz > most)))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere-model checks support grids below 2^31 cells");
+    if (std::isnan(minimum_clearance)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "minimum_clearance must not be NaN");
+    if (flags & ~VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown sphere-model check flag");
+    if (num_links == 0 && num_spheres > 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a model with spheres needs at least one link (num_links == 0)");
+    if (num_spheres > most || num_links > most || num_configurations > most ||
+        num_configurations * num_spheres > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "sphere-model checks support fewer than 2^31 spheres, links and (configuration, sphere) pairs");
+    return VGT_HIP_OK;
+  }
+  // The host form's own check: it can look at the model.
+  int CheckModel() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+    {
+      const double radius = sphere_xyzr[4 * s + 3];
+      if (sphere_link[s] < 0 || sphere_link[s] >= num_links)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(s) + ": link " +
+                                                      std::to_string(sphere_link[s]) + " is not in [0, num_links)");
+      if (!(radius >= 0.0))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "sphere " + std::to_string(s) + ": the radius must not be negative or NaN");
+    }
+    return VGT_HIP_OK;
+  }
+  hipError_t Launch(const float* sdf_dev, const double* xyzr_dev, const int32_t* link_dev, const double* poses_dev,
+                    const vgt::BodyOutputs& out_dev, hipStream_t stream) const
+  {
+    return vgt::LaunchCheckSpheres(sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, xyzr_dev, link_dev,
+                                   num_spheres, poses_dev, num_links, num_configurations, minimum_clearance,
+                                   (flags & VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION) ? 1 : 0, out_dev,
+                                   g_check_spheres_workgroups.load(), stream);
+  }
+};
 
 // Events of the current timing slot (nullptr when no session is active or it is full).
 hipEvent_t* TimingSlot(vgt_hip_ctx* ctx)
@@ -1345,6 +1414,12 @@ int vgt_hip_testing_set_short_line_rows(int rows)
 {
   // 0 ... kShortLineRowsFewItems; negative: back to the defaults
   g_short_line_override.store(rows < 0 ? -1 : (rows > vgt::kShortLineRowsFewItems ? vgt::kShortLineRowsFewItems : rows));
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_check_spheres_workgroups(int workgroups)
+{
+  g_check_spheres_workgroups.store(workgroups > 0 ? workgroups : 0);
   return VGT_HIP_OK;
 }
 
@@ -2653,6 +2728,91 @@ int vgt_hip_cast_segments(vgt_hip_ctx* ctx, const float* field_host, int64_t nx,
     const vgt::SegmentOutputs out{status.dev(),         hit_index.dev(), hit_fraction.dev(),
                                   cells_examined.dev(), min_value.dev(), min_index.dev()};
     return HipResult(what, vgt::LaunchCastSegments(field.dev(), grid, query, segments.dev(), num_segments, out, s));
+  });
+}
+
+int vgt_hip_check_spheres_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                              double resolution, const double* grid_from_world, const double* rotation,
+                              const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                              const double* link_poses_dev, int64_t num_links, int64_t num_configurations,
+                              double minimum_clearance, uint32_t flags, uint8_t* status_dev, double* min_clearance_dev,
+                              int32_t* min_sphere_dev, int32_t* num_below_dev, int32_t* num_outside_dev,
+                              double* min_gradient_dev, double* sphere_clearance_dev, double* sphere_gradient_dev)
+{
+  const CheckSpheresArguments a{sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_dev,
+                                sphere_link_dev, num_spheres, link_poses_dev, num_links, num_configurations,
+                                minimum_clearance, flags,
+                                {status_dev, min_clearance_dev, min_sphere_dev, num_below_dev, num_outside_dev,
+                                 min_gradient_dev, sphere_clearance_dev, sphere_gradient_dev}};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_configurations == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  // (no spheres, or an empty grid: the kernel writes NO_VALUE and reads neither the field nor the model)
+  VGT_TRY_HIP(a.Launch(sdf_dev, sphere_xyzr_dev, sphere_link_dev, link_poses_dev, a.out, ctx->stream), "check spheres");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_check_spheres(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                          const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+                          const int32_t* sphere_link_host, int64_t num_spheres, const double* link_poses_host,
+                          int64_t num_links, int64_t num_configurations, double minimum_clearance, uint32_t flags,
+                          uint8_t* status_host, double* min_clearance_host, int32_t* min_sphere_host,
+                          int32_t* num_below_host, int32_t* num_outside_host, double* min_gradient_host,
+                          double* sphere_clearance_host, double* sphere_gradient_host)
+{
+  const CheckSpheresArguments a{sdf_host, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_host,
+                                sphere_link_host, num_spheres, link_poses_host, num_links, num_configurations,
+                                minimum_clearance, flags,
+                                {status_host, min_clearance_host, min_sphere_host, num_below_host, num_outside_host,
+                                 min_gradient_host, sphere_clearance_host, sphere_gradient_host}};
+  int rc = a.Check(ctx);
+  if (rc == VGT_HIP_OK) rc = a.CheckModel();
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_configurations == 0) return VGT_HIP_OK;
+  const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+  if (num_spheres == 0 || a.NumCells() == 0)
+  {
+    // nothing is comparable: the answer needs no device
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t i = 0; i < b; i++)
+    {
+      status_host[i] = (num_spheres > 0 && (flags & VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION)) ? VGT_HIP_SPHERES_COLLISION
+                                                                                            : VGT_HIP_SPHERES_NO_VALUE;
+      if (min_clearance_host) min_clearance_host[i] = nan;
+      if (min_sphere_host) min_sphere_host[i] = -1;
+      if (num_below_host) num_below_host[i] = 0;
+      if (num_outside_host) num_outside_host[i] = static_cast<int32_t>(num_spheres);
+      for (int k = 0; k < 3 && min_gradient_host; k++) min_gradient_host[3 * i + static_cast<size_t>(k)] = nan;
+    }
+    for (size_t i = 0; i < b * s && sphere_clearance_host; i++) sphere_clearance_host[i] = nan;
+    for (size_t i = 0; i < b * s * 3 && sphere_gradient_host; i++) sphere_gradient_host[i] = nan;
+    return VGT_HIP_OK;
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "check spheres";
+  // (twelve arrays, and a staging holds eight: the inputs in one, the outputs in a second one inside its body)
+  vgt::HostStaging inputs;
+  const auto sdf = inputs.In(sdf_host, static_cast<size_t>(a.NumCells()));
+  const auto xyzr = inputs.In(sphere_xyzr_host, s * 4);
+  const auto link = inputs.In(sphere_link_host, s);
+  const auto poses = inputs.In(link_poses_host, b * static_cast<size_t>(num_links) * 16);
+  return inputs.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    vgt::HostStaging outputs;
+    const auto status = outputs.Out(status_host, b);
+    const auto min_clearance = outputs.Out(min_clearance_host, b);
+    const auto min_sphere = outputs.Out(min_sphere_host, b);
+    const auto num_below = outputs.Out(num_below_host, b);
+    const auto num_outside = outputs.Out(num_outside_host, b);
+    const auto min_gradient = outputs.Out(min_gradient_host, b * 3);
+    const auto sphere_clearance = outputs.Out(sphere_clearance_host, b * s);
+    const auto sphere_gradient = outputs.Out(sphere_gradient_host, b * s * 3);
+    return outputs.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+      const vgt::BodyOutputs out{status.dev(),      min_clearance.dev(), min_sphere.dev(),       num_below.dev(),
+                                 num_outside.dev(), min_gradient.dev(),  sphere_clearance.dev(), sphere_gradient.dev()};
+      return HipResult(what, a.Launch(sdf.dev(), xyzr.dev(), link.dev(), poses.dev(), out, stream));
+    });
   });
 }
 

@@ -470,6 +470,31 @@ hipError_t LaunchCastSegments(const float* field_dev, const SegmentGrid& grid, c
                               const double* segments_dev, int64_t num_segments, const SegmentOutputs& out,
                               hipStream_t stream);
 
+// --- launcher (body_kernels.hip): sphere models checked against an SDF ---
+// Inputs, outputs and statuses: include/vgt_hip.h, vgt_hip_check_spheres.  Grids of 0 to 2^31 - 1 cells, fewer than 2^31
+// spheres, links and (configuration, sphere) pairs.  status_dev is required, every other output may be nullptr.
+struct BodyOutputs
+{
+  uint8_t* status;
+  double* min_clearance;
+  int32_t* min_sphere;
+  int32_t* num_below;
+  int32_t* num_outside;
+  double* min_gradient;
+  double* sphere_clearance;
+  double* sphere_gradient;
+};
+// The width of a configuration's lane segment: log2 of the least power of two >= min(num_spheres, 64).
+int CheckSpheresWidthLog2(int64_t num_spheres);
+// max_workgroups: 0 = the launcher's own limit (a testing build can make it small, so that few configurations already
+// stride: vgt_hip_testing_set_check_spheres_workgroups).  The two transforms are host arrays (or nullptr).
+hipError_t LaunchCheckSpheres(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                              const double* grid_from_world_host, const double* rotation_host,
+                              const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                              const double* link_poses_dev, int64_t num_links, int64_t num_configurations,
+                              double minimum_clearance, int outside_is_collision, const BodyOutputs& out,
+                              int max_workgroups, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
