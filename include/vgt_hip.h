@@ -805,10 +805,23 @@ int vgt_hip_cells_extract_surface(vgt_hip_ctx* ctx, vgt_hip_cells* cells, double
  * launch order, on where atomics land or on how often a tile is revisited.
  *   method    cost is relaxed by tiles of 8 x 8 x 16 cells (Z fastest) in rounds, one launch each; after a round the
  *             host reads ONE word, "some tile is active", and stops when it is zero.  A round in which anything fell
- *             lowers at least one cell of a field of integers bounded below, so the rounds end.  The loop is bounded all
- *             the same: a tile is re-run only because one of its at most 26 neighbours or a seed flagged it, so after
- *             tiles * 27 + 2 rounds with something still active the call ends with VGT_HIP_ERR_RUNTIME.  That cannot
- *             happen in a correct build; the bound is there so that a defect ends the call instead of spinning.
+ *             lowers at least one cell of a field of integers bounded below, so the rounds end.  How many there are
+ *             depends on the grid, not on the number of tiles: a tile is flagged only by a seed or by one of its at
+ *             most 26 neighbours, but by the same neighbour once for EVERY round in which that one lowers a cell they
+ *             share, and a corridor may cross one face between two tiles dozens of times.  The loop is bounded by
+ *             cells + 2 rounds.  Proof: call a reached cell of order h when h is the least number of moves from one
+ *             tile into another on any of its least-cost paths (from a contributing source, initial cost included).
+ *             After round k every cell of order below k holds its final cost.  k = 1: a cell of order 0 has a
+ *             least-cost path inside its tile from a source there, the seed flagged that tile, and a run relaxes its
+ *             tile to the fixed point over what it read.  k -> k + 1: on such a path of a cell c of order k let u -> v
+ *             be the last move into another tile; u has order below k and lies in the halo of c's tile T.  The round
+ *             r <= k that stored u's final cost (or the seed, r = 0) flagged T for round r + 1 <= k + 1, which reads
+ *             that cost -- a kernel boundary lies between -- and lowers v and the rest of the path, all inside T, to
+ *             their final costs; no later run raises anything.  A path with a repeated cell is not least-cost
+ *             (weights are positive), so it has fewer moves than the grid has cells: every order is at most cells - 1,
+ *             every cell is final after cells rounds, and one more round, flagged by the last stores, lowers nothing
+ *             and flags nobody.  With something still active after cells + 2 rounds the call ends with
+ *             VGT_HIP_ERR_RUNTIME: only a defect gets there, and the bound ends the call instead of spinning.
  *   vgt_hip_travel_cost        field, sources and outputs in host memory; blocking.
  *   vgt_hip_travel_cost_dev    everything in device memory (e.g. the output of vgt_hip_sdf_dev); only num_reached is a
  *                              host pointer.  workspace_dev: what vgt_hip_travel_cost_workspace_bytes says for the grid (0

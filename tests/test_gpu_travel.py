@@ -214,6 +214,132 @@ def test_device_form_with_an_exact_workspace(ctx, torch):
     assert (cost.cpu().numpy().view(np.uint32) == SENTINEL).all()
 
 
+class _DeviceRun:
+    """The device form on buffers that stay: sentinel-filled outputs, a workspace of exactly the stated size."""
+
+    def __init__(self, ctx, torch, field, weights, flags, sources, source_costs=None):
+        self.ctx, self.shape = ctx, field.shape
+        self.weights, self.flags = weights, flags
+        self.need = capi.travel_cost_workspace_bytes(self.shape)
+        self.field = torch.from_numpy(np.ascontiguousarray(field, dtype=np.float32)).cuda()
+        self.sources = torch.from_numpy(np.asarray(sources, dtype=np.int32).reshape(-1)).cuda()
+        costs = None if source_costs is None else np.asarray(source_costs, dtype=np.uint32).view(np.int32)
+        self.costs = None if costs is None else torch.from_numpy(costs).cuda()
+        self.cost = torch.empty(self.shape, dtype=torch.int32, device="cuda")
+        self.toward = torch.empty(self.shape, dtype=torch.int32, device="cuda")
+        self.workspace = torch.empty((self.need,), dtype=torch.uint8, device="cuda")
+
+    def __call__(self):
+        """-> (cost, toward, num_reached, the `rounds` word of the workspace's header)"""
+        import torch
+        self.cost.fill_(SENTINEL)
+        self.toward.fill_(SENTINEL)
+        self.workspace.fill_(0x5A)
+        torch.cuda.synchronize()
+        reached = self.ctx.travel_cost_dev(
+            self.field.data_ptr(), self.shape, self.sources.data_ptr(), self.sources.numel(), self.cost.data_ptr(),
+            self.workspace.data_ptr(), self.need, toward_ptr=self.toward.data_ptr(),
+            source_costs_ptr=None if self.costs is None else self.costs.data_ptr(), weights=self.weights,
+            no_corner_cutting=bool(self.flags & R.NO_CORNER_CUTTING))
+        head = self.workspace[:32].cpu().numpy()
+        assert int(head[16:24].view(np.uint64)[0]) == reached
+        return (self.cost.cpu().numpy().view(np.uint32), self.toward.cpu().numpy(), reached,
+                int(head[8:12].view(np.uint32)[0]))
+
+
+@pytest.mark.parametrize("n", [16, 32])
+def test_corridor_that_crosses_tile_faces_hundreds_of_times(ctx, torch, n):
+    """C.zigzag_chain(n): one corridor that changes tile 31 times per face, so a tile is flagged by ONE neighbour 31
+    times.  The rounds model (R.tile_rounds; tests/test_travel_ref.py) needs 467 rounds for n = 16 and 963 for n = 32,
+    more than the tiles * 27 + 2 = 434 and 866 the host loop allowed at first, and a halo read that sees a value of the
+    same launch can save a round only where two tiles are active at once: 14 rounds at n = 16, about 30 at n = 32."""
+    occ = C.zigzag_chain(n)
+    tiles = n
+    cells = int((occ == 0).sum())
+    # host form
+    want = _check(ctx, occ, (1, 0, 0), 0, [0])
+    assert want[2] == cells and int(want[0].reshape(-1)[C.zigzag_end(n)]) == cells - 1
+    _check(ctx, occ, (10, 14, 17), R.NO_CORNER_CUTTING, [0])
+    # device form: the same, in more rounds than 27 per tile and no more than the bound (vgt_hip.h, method)
+    cost, toward, reached, rounds = _DeviceRun(ctx, torch, occ, (1, 0, 0), 0, [0])()
+    print("zigzag_chain(%d): %d rounds on the device, tiles * 27 + 2 = %d" % (n, rounds, tiles * 27 + 2))
+    assert np.array_equal(cost, want[0]) and np.array_equal(toward, want[1]) and reached == want[2]
+    assert rounds > tiles * 27 + 2
+    assert rounds <= occ.size + 2
+    # the path from the corridor's last cell is the corridor in reverse
+    end = C.zigzag_end(n)
+    paths, lengths, status = ctx.trace_paths(toward, [end], cells, fill=-9)
+    assert status[0] == R.TRACE_OK and lengths[0] == cells
+    assert np.array_equal(want[0].reshape(-1)[paths[0]], np.arange(cells - 1, -1, -1, dtype=np.uint32))
+    for g, w in zip((paths, lengths, status), R.trace_paths(want[1], [end], cells, fill=-9)):
+        assert g.dtype == w.dtype and np.array_equal(g, w)
+    short = ctx.trace_paths(toward, [end], cells - 1, fill=-9)
+    assert short[2][0] == R.TRACE_TRUNCATED and short[1][0] == cells - 1
+    for g, w in zip(short, R.trace_paths(want[1], [end], cells - 1, fill=-9)):
+        assert np.array_equal(g, w)
+
+
+# The second source of test_cells_lowered_again_by_a_cheaper_front, cell (4, 32, 32): its front reaches the cells round
+# it in the first rounds, at its initial cost and more, and the front from cell 0 lowers them again when it arrives.
+SECOND_SOURCE = (4 * 64 + 32) * 64 + 32
+
+
+@pytest.mark.parametrize("case", ["open", "blocked", "blocked-cut"])
+def test_cells_lowered_again_by_a_cheaper_front(ctx, torch, case):
+    """open: two fronts on a free grid, against the closed form.  blocked: 30 % blocked cells and the corner rule; there
+    cell 0 reaches no other cell (the rule bars every move out of it), so one front alone re-enters tiles through the
+    maze, which still lowers 9132 cells twice or more in the model.  blocked-cut: the same grid with corners cut, where
+    the two sources are 466 apart; an initial cost of 300 gives each front about half of the 23 089 reached cells
+    (60 would leave cell 0 one in six), and the model lowers 10 873 cells twice or more."""
+    shape = (8, 64, 64)  # 32 tiles
+    second_cost = 300 if case == "blocked-cut" else 60
+    sources, costs = [0, SECOND_SOURCE], [0, second_cost]
+    if case == "open":
+        occ, weights, flags = np.zeros(shape, np.float32), (1, 0, 0), 0
+    else:
+        occ, weights = C.random_occupancy(shape, 0.3), (10, 14, 17)
+        flags = R.NO_CORNER_CUTTING if case == "blocked" else 0
+    # what the case exercises, by the rounds model: cells that a later round lowers a second time
+    _, model_cost, writes, _ = R.tile_rounds(R.passable(occ), weights, flags, sources, costs, tile=C.TILE)
+    again = writes >= 2
+    want = C.expected(occ, weights, flags, sources, costs)
+    assert np.array_equal(model_cost, want[0])
+    if case == "open":
+        x, y, z = np.indices(shape)
+        closed_form = np.minimum(x + y + z, second_cost + abs(x - 4) + abs(y - 32) + abs(z - 32))
+        assert np.array_equal(want[0], closed_form.astype(np.uint32))
+        tiles = {(a // C.TILE[0], b // C.TILE[1], c // C.TILE[2]) for a, b, c in zip(*np.nonzero(again))}
+        assert int(again.sum()) >= 10000 and len(tiles) >= 10
+    else:
+        assert int(again.sum()) > 1000
+        assert want[1].reshape(-1)[SECOND_SOURCE] == SECOND_SOURCE
+    if case == "blocked-cut":  # each front keeps thousands of cells: those that the other source alone leaves dearer
+        from_first = C.expected(occ, weights, flags, sources[:1])[0]
+        from_second = C.expected(occ, weights, flags, sources[1:], costs[1:])[0]
+        assert int((from_first < from_second).sum()) > 5000 and int((from_second < from_first).sum()) > 5000
+    _check(ctx, occ, weights, flags, sources, costs)
+    cost, toward, reached, _ = _DeviceRun(ctx, torch, occ, weights, flags, sources, costs)()
+    assert np.array_equal(cost, want[0]) and np.array_equal(toward, want[1]) and reached == want[2]
+
+
+@pytest.mark.parametrize("flags", [0, 1], ids=["cut", "nocut"])
+@pytest.mark.parametrize("shape", [(72, 64, 80), (33, 41, 70)], ids=["360tiles", "150tiles-partial"])
+def test_hundreds_of_tiles_active_at_once(ctx, torch, shape, flags):
+    """Hundreds of workgroups in one launch, so halos are read while their owners, on other XCDs too, rewrite them; the
+    result is the fixed point all the same, and the same on a second call on the same buffers."""
+    occ = C.random_occupancy(shape, 0.3)
+    tiles = int(np.prod([-(-shape[i] // C.TILE[i]) for i in range(3)]))
+    assert tiles == (360 if shape[0] == 72 else 150)
+    sources, costs = [0, occ.size - 1, int(C.random_sources(shape, 1)[0])], [0, 25, 7]
+    want = C.expected_large(occ, (10, 14, 17), flags, sources, costs)
+    assert want[2] > occ.size // 2
+    run = _DeviceRun(ctx, torch, occ, (10, 14, 17), flags, sources, costs)
+    first = run()
+    assert np.array_equal(first[0], want[0]) and np.array_equal(first[1], want[1]) and first[2] == want[2]
+    second = run()
+    assert np.array_equal(second[0], first[0]) and np.array_equal(second[1], first[1]) and second[2] == first[2]
+
+
 @pytest.mark.parametrize("dtype", [capi.TAGGED_OBJECT_CELL, capi.TAGGED_OBJECT_COMPONENT_CELL], ids=["tagged8", "tagged16"])
 def test_cells_form_on_a_tagged_map(ctx, dtype):
     shape = (9, 17, 20)

@@ -117,6 +117,73 @@ def test_spiral_is_one_corridor():
     assert len(reached) > 9 * (5 * 33 + 4)
 
 
+@pytest.mark.parametrize("n,rounds", [(4, 95), (16, 467), (32, 963)])
+def test_zigzag_chain_is_one_corridor_that_needs_more_rounds_than_27_per_tile(n, rounds):
+    occ = C.zigzag_chain(n)
+    assert occ.shape == (C.TILE[0], C.TILE[1] * n, C.TILE[2]) and occ.dtype == np.float32
+    free = R.passable(occ)
+    cells = int(free.sum())
+    assert cells == 7 + 98 * (n - 1) + 12 * (n - 2)
+    got_rounds, cost, writes, most_active = R.tile_rounds(free, (1, 0, 0), 0, [0], tile=C.TILE)
+    assert cost.dtype == np.uint32 and np.array_equal(cost, R.bellman_ford(free, (1, 0, 0), 0, [0]))
+    if n == 4:
+        assert np.array_equal(cost, R.dijkstra(free, (1, 0, 0), 0, [0]))
+    # one corridor without branches: every free cell is reached, and every length up to the longest occurs once
+    reached = np.sort(cost[cost != U])
+    assert np.array_equal(cost != U, free) and np.array_equal(reached, np.arange(cells))
+    assert int(cost.reshape(-1)[C.zigzag_end(n)]) == cells - 1
+    # it changes tile 31 times per face between two tiles
+    path = np.argsort(cost.reshape(-1), kind="stable")[:cells]
+    tile_of = np.unravel_index(path, occ.shape)[1] // C.TILE[1]
+    assert int(np.count_nonzero(np.diff(tile_of))) == 31 * (n - 1)
+    once = free.copy()
+    once.flat[0] = False  # (the source is seeded, not lowered)
+    assert np.array_equal(writes, once.astype(np.int64)) and most_active == 2  # every other cell is lowered once
+    # the rounds of the model, and what the host loop allowed before: tiles * 27 + 2
+    assert got_rounds == rounds
+    assert (got_rounds > n * 27 + 2) == (n >= 16)
+    assert got_rounds <= occ.size + 2
+
+
+@pytest.mark.parametrize("case", ["serpentine", "spiral"])
+def test_tile_rounds_reaches_the_same_field(case):
+    occ = C.serpentine() if case == "serpentine" else C.spiral()
+    free = R.passable(occ)
+    for weights, flags in (((1, 0, 0), 0), ((10, 14, 17), 0), ((10, 14, 17), 1)):
+        rounds, cost, writes, most_active = R.tile_rounds(free, weights, flags, [0], tile=C.TILE)
+        assert np.array_equal(cost, C.expected(occ, weights, flags, [0])[0]), (weights, flags)
+        assert rounds > 1 and most_active >= 1 and int(writes.max()) >= 1
+        assert np.array_equal(writes > 0, (cost != U) & (np.arange(cost.size).reshape(cost.shape) != 0))
+
+
+def test_tile_rounds_with_sources_costs_and_a_limit():
+    shape = (17, 10, 33)
+    occ = C.random_occupancy(shape, 0.3)
+    free = R.passable(occ)
+    sources, costs = [0, occ.size - 1, -4, occ.size // 2], [5, 0, 0, 900]
+    for limit in (R.NO_LIMIT, 400):
+        rounds, cost, writes, _ = R.tile_rounds(free, (10, 14, 17), 1, sources, costs, limit, tile=C.TILE)
+        assert np.array_equal(cost, C.expected(occ, (10, 14, 17), 1, sources, costs, limit)[0])
+    # another tile size gives the same field
+    assert np.array_equal(R.tile_rounds(free, (10, 14, 17), 1, sources, costs, 400, tile=(4, 5, 7))[1], cost)
+    # no contributing source: no round
+    rounds, cost, writes, most_active = R.tile_rounds(free, (1, 0, 0), 0, [-1, occ.size])
+    assert (rounds, most_active) == (0, 0) and (cost == U).all() and not writes.any()
+
+
+@pytest.mark.parametrize("shape", C.SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_graph_cost_agrees_with_bellman_ford(shape):
+    occ = C.random_occupancy(shape, 0.3)
+    free = R.passable(occ)
+    n = occ.size
+    sources, costs = [0, n - 1, int(C.random_sources(shape, 1)[0]), n - 1, -1, n], [0, 25, 7, 30, 0, 0]
+    for weights, flags in (((10, 14, 17), 0), ((10, 14, 17), 1), ((1, 0, 0), 0), ((5, 0, 7), 1)):
+        for limit in (R.NO_LIMIT, 60):
+            got = R.graph_cost(free, weights, flags, sources, costs, limit)
+            assert got.dtype == np.uint32 and got.shape == shape
+            assert np.array_equal(got, R.bellman_ford(free, weights, flags, sources, costs, limit)), (weights, flags, limit)
+
+
 def test_limits_and_wrap():
     free = np.ones((1, 1, 4), bool)
     top = R.NO_LIMIT - 65535

@@ -71,6 +71,35 @@ def spiral(shape=(17, 10, 33)):
     return occ
 
 
+def zigzag_chain(n_tiles):
+    """8 x 8 * n_tiles x 16, a chain of tiles along Y, blocked but for ONE corridor without branches that crosses every
+    face between two tiles 31 times: the rows x = 0, 2, 4, 6 on both sides of the face run along Z with every fourth
+    cell blocked, on the two sides in turn, so that the corridor changes side every second cell.  A tile therefore hears
+    of a lowered face cell 31 times per face, not once; the source is cell 0 and the last cell is zigzag_end()."""
+    tx, ty, tz = TILE
+    occ = np.ones((tx, ty * n_tiles, tz), dtype=np.float32)
+    z = np.arange(tz)
+    occ[0, 0:ty - 1, 0] = 0.0                                 # lead-in to the first face
+    for j in range(n_tiles - 1):
+        a, b = ty * j + ty - 1, ty * j + ty                   # the last row of tile j, the first of tile j + 1
+        for x in (0, 2, 4, 6):
+            occ[x, a, z[z % 4 != 1]] = 0.0
+            occ[x, b, z[z % 4 != 3]] = 0.0
+        occ[1, a, tz - 1] = occ[3, a, 0] = occ[5, a, tz - 1] = 0.0   # from one row to the next, on side a
+        occ[6, a, 0] = 1.0                                    # the last row ends on side b, after 7 crossings
+        if j < n_tiles - 2:                                   # on to the next face
+            occ[6, b + 1:b + 4, 0] = 0.0
+            occ[0:7, b + 3, 0] = 0.0
+            occ[0, b + 3:b + 7, 0] = 0.0
+    return occ
+
+
+def zigzag_end(n_tiles):
+    """Linear index of the last cell of zigzag_chain(n_tiles)'s corridor: (6, first row of the last tile, 0)."""
+    tx, ty, tz = TILE
+    return (6 * ty * n_tiles + ty * (n_tiles - 1)) * tz
+
+
 @functools.lru_cache(maxsize=None)
 def _expected(key):
     field, weights, flags, sources, source_costs, cost_limit, mode, unknown_is_filled, threshold = _CASES[key]
@@ -97,3 +126,29 @@ def expected(field, weights, flags=0, sources=(), source_costs=None, cost_limit=
                        None if costs is None else np.asarray(costs, dtype=np.int64), int(cost_limit), int(mode),
                        bool(unknown_is_filled), float(threshold))
     return _expected(key)
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_large(key):
+    field, weights, flags, sources, source_costs = _LARGE[key]
+    free = R.passable(field)
+    cost = R.graph_cost(free, weights, flags, sources, source_costs)
+    toward = R.toward(free, weights, flags, cost, sources, source_costs)
+    cost.setflags(write=False)
+    toward.setflags(write=False)
+    return cost, toward, int(np.count_nonzero(cost != R.UNREACHED))
+
+
+_LARGE = {}
+
+
+def expected_large(field, weights, flags=0, sources=(), source_costs=None):
+    """expected() for grids of hundreds of tiles (occupancy mode, no limit): the cost from R.graph_cost, which is scipy's
+    Dijkstra where scipy imports and R.bellman_ford otherwise, `toward` by the same rule.  Computed once per case."""
+    field = np.ascontiguousarray(field, dtype=np.float32)
+    sources = np.asarray(sources, dtype=np.int64).reshape(-1)
+    costs = None if source_costs is None else tuple(int(c) for c in source_costs)
+    key = (field.shape, field.tobytes(), tuple(int(w) for w in weights), int(flags), tuple(int(s) for s in sources), costs)
+    if key not in _LARGE:
+        _LARGE[key] = (field, key[2], int(flags), sources, None if costs is None else np.asarray(costs, dtype=np.int64))
+    return _expected_large(key)

@@ -1,6 +1,8 @@
 """The definition of vgt_hip_travel_cost (include/vgt_hip.h) restated twice in numpy: a heap Dijkstra written as a loop
 and a vectorised Bellman-Ford of shifted-array minima iterated to the fixed point; the `toward` rule; the path follower
-of vgt_hip_trace_paths.  Nothing here is shared with the library."""
+of vgt_hip_trace_paths.  For grids of hundreds of tiles, graph_cost (scipy's Dijkstra when scipy imports).  tile_rounds
+models the rounds in which the library relaxes tiles, to choose inputs and to say what they exercise.  Nothing here is
+shared with the library."""
 import heapq
 import itertools
 
@@ -116,25 +118,142 @@ def allowed_moves(free, weights, flags):
 
 
 def bellman_ford(free, weights, flags, sources, source_costs=None, cost_limit=NO_LIMIT):
-    """uint32 cost by shifted-array minima iterated to the fixed point, in int64 with a large 'infinity'."""
+    """uint32 cost by shifted-array minima iterated to the fixed point, in int64 with a large 'infinity'.  Every sweep
+    takes all its candidates from the previous sweep's field; it covers the bounding box, grown by one cell, of the cells
+    the previous sweep lowered, since no other cell has a neighbour that changed (a long corridor needs thousands of
+    sweeps that each lower one cell)."""
+    shape = free.shape
     inf = np.int64(1) << 40
-    cost = np.full(free.shape, inf, dtype=np.int64)
-    flat = cost.reshape(-1)
+    padded = np.full(tuple(s + 2 for s in shape), inf, dtype=np.int64)  # a rim of 'infinity' round the grid
+    cost = padded[1:-1, 1:-1, 1:-1]
     for s, c0 in _contributing(free, sources, source_costs, cost_limit).items():
-        flat[s] = min(flat[s], c0)
+        xyz = np.unravel_index(s, shape)
+        cost[xyz] = min(cost[xyz], c0)
     moves = allowed_moves(free, weights, flags)
+    lo, hi = (0, 0, 0), shape
     while True:
-        new = cost.copy()
+        box = tuple(slice(lo[i], hi[i]) for i in range(3))
+        old = cost[box]
+        new = old.copy()
         for d, ok in moves.items():
             w = int(weights[sum(1 for v in d if v) - 1])
-            cand = _shifted(cost, d, inf) + w
-            cand[~ok | (cand > cost_limit)] = inf
+            cand = padded[tuple(slice(lo[i] + 1 + d[i], hi[i] + 1 + d[i]) for i in range(3))] + w
+            cand[~ok[box] | (cand > cost_limit)] = inf
             np.minimum(new, cand, out=new)
-        if np.array_equal(new, cost):
+        lowered = np.nonzero(new < old)
+        if lowered[0].size == 0:
             break
-        cost = new
+        cost[box] = new
+        lo, hi = (tuple(max(lo[i] + int(lowered[i].min()) - 1, 0) for i in range(3)),
+                  tuple(min(lo[i] + int(lowered[i].max()) + 2, shape[i]) for i in range(3)))
     out = np.where(cost >= inf, UNREACHED, cost).astype(np.uint32)
     return out
+
+
+def graph_cost(free, weights, flags, sources, source_costs=None, cost_limit=NO_LIMIT):
+    """uint32 cost for grids too large for the two forms above: the allowed moves as a sparse directed graph and scipy's
+    Dijkstra from one extra node joined to every contributing source, where scipy imports; bellman_ford otherwise."""
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import dijkstra as graph_dijkstra
+    except ImportError:
+        return bellman_ford(free, weights, flags, sources, source_costs, cost_limit)
+    n = free.size
+    index = np.arange(n, dtype=np.int64).reshape(free.shape)
+    rows, cols, vals = [], [], []
+    for d, ok in allowed_moves(free, weights, flags).items():
+        rows.append(index[ok])
+        cols.append(_shifted(index, d, -1)[ok])
+        vals.append(np.full(rows[-1].size, float(weights[sum(1 for v in d if v) - 1])))
+    # the extra node n; its edges carry init + 1 (an entry of 0 would not be an edge), taken off again below
+    init = _contributing(free, sources, source_costs, cost_limit)
+    rows.append(np.full(len(init), n, dtype=np.int64))
+    cols.append(np.fromiter(init.keys(), dtype=np.int64, count=len(init)))
+    vals.append(np.fromiter(init.values(), dtype=np.float64, count=len(init)) + 1.0)
+    graph = coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n + 1, n + 1)).tocsr()
+    dist = graph_dijkstra(graph, directed=True, indices=[n], min_only=True)[:n] - 1.0  # (integers below 2^53: exact)
+    # (every prefix of a least-cost path within the limit is within the limit: cutting afterwards is the definition)
+    reached = np.isfinite(dist) & (dist <= cost_limit)
+    out = np.full(n, UNREACHED, dtype=np.uint32)
+    out[reached] = dist[reached].astype(np.uint32)
+    return out.reshape(free.shape)
+
+
+def tile_rounds(free, weights, flags, sources, source_costs=None, cost_limit=NO_LIMIT, tile=(8, 8, 16)):
+    """A model of HOW the library reaches the cost field, not of the field: tiles relaxed in rounds.  In
+    a round every flagged tile reads its cells and a one-cell halo from a snapshot of the previous round's costs, relaxes
+    its own cells to the fixed point, and stores the cells it lowered; a lowered cell on a face, an edge or a corner of
+    its tile flags, for the next round, the neighbouring tiles that see it in their halo; a contributing source flags
+    its tile and those neighbours for the first round.  -> (rounds, cost uint32, writes, most_active): the number of
+    rounds with a flagged tile, the field after the last, per cell the number of rounds that lowered it, and the most
+    tiles flagged in one round.  The device may see a value stored in the same round and then needs fewer rounds, so
+    its count is never compared for equality; this serves to choose inputs and to state what they exercise."""
+    shape = free.shape
+    inf = np.int64(1) << 40
+    counts = tuple(-(-shape[i] // tile[i]) for i in range(3))
+    moves = allowed_moves(free, weights, flags)
+    padded = np.full(tuple(s + 2 for s in shape), inf, dtype=np.int64)  # a rim of 'infinity': halo cells off the grid
+    cost = padded[1:-1, 1:-1, 1:-1]
+    writes = np.zeros(shape, dtype=np.int64)
+
+    def flag_neighbours(flagged, t, lowered, with_itself):
+        """`lowered`: bool over the cells of tile t (clipped to the grid)."""
+        where = np.nonzero(lowered)
+        if where[0].size == 0:
+            return
+        for s in itertools.product((-1, 0, 1), repeat=3):
+            if s == (0, 0, 0) and not with_itself:
+                continue
+            other = tuple(t[i] + s[i] for i in range(3))
+            if not all(0 <= other[i] < counts[i] for i in range(3)):
+                continue
+            on = np.ones(where[0].size, dtype=bool)
+            for i in range(3):
+                if s[i]:
+                    on &= where[i] == (0 if s[i] < 0 else tile[i] - 1)
+            if on.any():
+                flagged.add(other)
+
+    flagged = set()
+    for s, c0 in _contributing(free, sources, source_costs, cost_limit).items():
+        xyz = tuple(int(v) for v in np.unravel_index(s, shape))
+        cost[xyz] = min(cost[xyz], c0)
+        t = tuple(xyz[i] // tile[i] for i in range(3))
+        one = np.zeros(tile, dtype=bool)
+        one[tuple(xyz[i] - t[i] * tile[i] for i in range(3))] = True
+        flag_neighbours(flagged, t, one, True)
+
+    rounds = most_active = 0
+    while flagged:
+        rounds += 1
+        most_active = max(most_active, len(flagged))
+        snapshot = padded.copy()
+        flagged_next = set()
+        for t in sorted(flagged):
+            lo = tuple(t[i] * tile[i] for i in range(3))
+            hi = tuple(min(lo[i] + tile[i], shape[i]) for i in range(3))
+            own_box = tuple(slice(lo[i], hi[i]) for i in range(3))
+            local = snapshot[tuple(slice(lo[i], hi[i] + 2) for i in range(3))].copy()  # the tile and its halo
+            own = local[1:-1, 1:-1, 1:-1]
+            before = own.copy()
+            steps = [(local[tuple(slice(1 + d[i], 1 + d[i] + hi[i] - lo[i]) for i in range(3))],
+                      int(weights[sum(1 for v in d if v) - 1]), ~ok[own_box]) for d, ok in moves.items()]
+            while True:
+                new = own.copy()
+                for neighbour, w, barred in steps:  # (`neighbour` is a view of `local`: it follows `own`)
+                    cand = neighbour + w
+                    cand[barred | (cand > cost_limit)] = inf
+                    np.minimum(new, cand, out=new)
+                if np.array_equal(new, own):
+                    break
+                own[...] = new
+            lowered = own < before
+            cost[own_box][lowered] = own[lowered]
+            writes[own_box] += lowered
+            flag_neighbours(flagged_next, t, lowered, False)
+        flagged = flagged_next
+    out = np.where(cost >= inf, UNREACHED, cost).astype(np.uint32)
+    return rounds, out, writes, most_active
 
 
 def toward(free, weights, flags, cost, sources, source_costs=None, cost_limit=NO_LIMIT):

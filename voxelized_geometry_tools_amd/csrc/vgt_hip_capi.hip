@@ -3641,15 +3641,16 @@ int RunTravelCost(hipStream_t s, const void* field_dev, int source, int unknown_
   auto* const status_dev = reinterpret_cast<vgt::TravelStatus*>(static_cast<char*>(workspace_dev) + w.status_offset);
   hipError_t err = vgt::LaunchTravelSeed(field_dev, source, unknown_is_filled, threshold, grid, sources_dev,
                                          source_costs_dev, num_sources, cost_dev, workspace_dev, s);
-  // (see vgt_hip.h: a tile runs again only when a neighbour or a seed flagged it)
-  const int64_t most_rounds = w.tiles * 27 + 2;
+  // (see vgt_hip.h, method: after round k every cell with a least-cost path of fewer than k tile changes is final, and a
+  // path visits a cell once, so it changes tile fewer times than the grid has cells)
+  const int64_t most_rounds = static_cast<int64_t>(grid.nx) * grid.ny * grid.nz + 2;
   int64_t round = 0;
   for (bool active = num_sources > 0; active && err == hipSuccess; round++)
   {
     if (round == most_rounds)
     {
       (void)hipStreamSynchronize(s);
-      return Fail(VGT_HIP_ERR_RUNTIME, "[travel cost] tiles are still active after tiles * 27 + 2 rounds");
+      return Fail(VGT_HIP_ERR_RUNTIME, "[travel cost] tiles are still active after cells + 2 rounds");
     }
     err = vgt::LaunchTravelRound(grid, cost_dev, workspace_dev, round, s);
     uint32_t next_active = 0;
