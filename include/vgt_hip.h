@@ -269,6 +269,14 @@ int vgt_hip_testing_set_short_line_rows(int rows);
 /* At most `workgroups` workgroups per launch of vgt_hip_check_spheres[_dev] (process-wide), so that a few configurations
  * already make its persistent waves stride; 0 or negative: back to the product's limit. */
 int vgt_hip_testing_set_check_spheres_workgroups(int workgroups);
+/* The same for the launches of vgt_hip_rasterize_spheres[_dev] and vgt_hip_spheres_cover_points[_dev], so that small
+ * inputs already make their persistent waves and workgroups take several trips. */
+int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups);
+/* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
+ * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
+ * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
+ * product's kernel. */
+int vgt_hip_testing_set_sphere_volume_counters(uint64_t* counters_dev);
 /* Pass 1 alone, for a test of the record format itself (csrc/vgt_internal.hpp, ClassRecord): the class records of a
  * device-resident occupancy grid, [x][64-voxel word][y] x 4 uint32 (mask_lo, mask_hi, below2, above2), into records_dev
  * (vgt_hip_testing_class_record_bytes bytes); summary_dev (optional): the 4-byte slab summaries per line, in which case the
@@ -553,6 +561,82 @@ int vgt_hip_check_spheres_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx
                               double minimum_clearance, uint32_t flags, uint8_t* status_dev, double* min_clearance_dev,
                               int32_t* min_sphere_dev, int32_t* num_below_dev, int32_t* num_outside_dev,
                               double* min_gradient_dev, double* sphere_clearance_dev, double* sphere_gradient_dev);
+
+/* ---- Sphere models into voxel grids and onto point clouds: swept volumes, self-filter ----
+ * The same body the other way round: which cells of a grid, or which points of a cloud, the spheres of B configurations
+ * cover, and the least configuration that does.  Over the cells of a grid that is the swept volume of a motion (a
+ * reservation, the overlap of two plans, a time-stamped occupancy); over the points of a depth cloud it is the
+ * self-filter in front of the voxelizer.  The model and the poses are those of vgt_hip_check_spheres: sphere_xyzr [S][4]
+ * doubles, sphere_link [S] int32, link_poses [B][L][16] doubles column-major of which only the elements 0-2, 4-6, 8-10 and
+ * 12-14 are read.  Everything in double and without contraction:
+ *   w_r       = ((m[r]*x + m[4+r]*y) + m[8+r]*z) + m[12+r] for r = 0, 1, 2, with m the pose of sphere_link[s] in
+ *               configuration b: the expression of vgt_hip_check_spheres.
+ *   R         = radius + padding; `padding` is one double per call, finite, possibly negative.
+ *   usable    a sphere with a link in [0, L), a finite w and a finite R >= 0 (in the grid form also a finite centre c in
+ *             the grid frame).  A sphere that is not usable covers nothing: this rule, and not the comparison below,
+ *             decides every non-finite case.
+ *   covers(q) ((dx*dx + dy*dy) + dz*dz) <= R*R with d_a = q_a - c_a.  R == 0 covers a location that equals the centre.
+ * The answer is a minimum over a set, so it does not depend on the order of the work.
+ *
+ * Grid form.  nx x ny x nz cells at `resolution`, linear index x*ny*nz + y*nz + z, fewer than 2^31 cells.
+ *   grid_from_world   16 doubles column-major, or NULL for the grid's own frame (a host array in both forms)
+ *   c_a               = M[a]*w0 + M[4+a]*w1 + M[8+a]*w2 + M[12+a], left to right (the order of the SDF queries'
+ *                     grid_from_world); c = w with NULL
+ *   q_a               = (i_a + 0.5) * resolution: the centre of cell (i_x, i_y, i_z)
+ *   first_configuration [cell] (int32)   first_configuration_base + b for the least b with a sphere that covers the
+ *                     cell, -1 where there is none.  first_configuration_base >= 0 and base + B <= 2^31 - 1.
+ *   Without VGT_HIP_SPHERES_KEEP the call first sets every entry to -1.  With it the array is input and output: an entry
+ *   ends as the UNSIGNED minimum of what it held and what this call finds (-1 is the greatest unsigned value), so a
+ *   motion can be rasterised in several calls with rising bases, in any order, with the same result.  The host form
+ *   uploads the array first.
+ *
+ * Point form.  points_xyz [N][3] float32, the voxelizer's format; world_from_points 16 doubles column-major (the cloud's
+ * origin transform, a host array in both forms) or NULL.  Each coordinate is converted to double, then
+ *   q_r = ((T[r]*px + T[4+r]*py) + T[8+r]*pz) + T[12+r], or q = p with NULL,
+ * and covers(q) is tested against c = w in the world frame; no grid is involved.  A point with a non-finite coordinate
+ * or a non-finite q is covered by nothing.  Every output may be NULL, but not all of them:
+ *   first_configuration [N] (int32)   the least b that covers the point, or -1 (no base here)
+ *   first_sphere [N] (int32)          the least s of that b that covers it, or -1
+ *   filtered_xyz [N][3] (float32)     the point's own three floats bit for bit where nothing covers it, a quiet NaN in
+ *                                     all three where something does; may be the input array itself.  The raycast entry
+ *                                     points skip non-finite points, so this is a self-filtered cloud as it stands.
+ *
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work, outputs untouched: a NULL required pointer (ctx; the model's two
+ * arrays when S > 0; link_poses when S > 0 and B > 0; first_configuration in the grid form; points when N > 0 and at
+ * least one output in the point form), a resolution that is not positive and finite, a NaN or infinite padding, an
+ * unknown flag bit (the point form knows none), a negative extent or count, num_links == 0 with num_spheres > 0, a grid
+ * of 2^31 cells or more, 2^31 or more spheres, links, configurations or points, B * S >= 2^31, a
+ * first_configuration_base that is negative or with base + B > 2^31 - 1; and, for the host forms only, a sphere_link
+ * outside [0, L) or a radius that is negative or NaN: the message names the first such sphere ("sphere 17: ...").
+ * The device forms cannot look at device memory: there a radius that makes R negative or NaN, or a link outside
+ * [0, L), makes the sphere not usable by the rule above, and the kernel forms no address from such a link.
+ * B == 0, S == 0, N == 0 and an empty grid succeed.  With B == 0 or S == 0 the grid form still writes -1 everywhere
+ * unless VGT_HIP_SPHERES_KEEP, the point form still writes -1 and the plain copy (the host forms then need no device). */
+#define VGT_HIP_SPHERES_KEEP 1u
+int vgt_hip_rasterize_spheres(vgt_hip_ctx* ctx, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                              const double* grid_from_world, const double* sphere_xyzr_host,
+                              const int32_t* sphere_link_host, int64_t num_spheres, const double* link_poses_host,
+                              int64_t num_links, int64_t num_configurations, double padding,
+                              int64_t first_configuration_base, uint32_t flags, int32_t* first_configuration_host);
+/* Same with the model, the poses and the output on the device; enqueued on the context's stream, not blocking. */
+int vgt_hip_rasterize_spheres_dev(vgt_hip_ctx* ctx, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                  const double* grid_from_world, const double* sphere_xyzr_dev,
+                                  const int32_t* sphere_link_dev, int64_t num_spheres, const double* link_poses_dev,
+                                  int64_t num_links, int64_t num_configurations, double padding,
+                                  int64_t first_configuration_base, uint32_t flags, int32_t* first_configuration_dev);
+int vgt_hip_spheres_cover_points(vgt_hip_ctx* ctx, const float* points_xyz_host, int64_t num_points,
+                                 const double* world_from_points, const double* sphere_xyzr_host,
+                                 const int32_t* sphere_link_host, int64_t num_spheres, const double* link_poses_host,
+                                 int64_t num_links, int64_t num_configurations, double padding, uint32_t flags,
+                                 int32_t* first_configuration_host, int32_t* first_sphere_host, float* filtered_xyz_host);
+/* Same with the cloud, the model, the poses and the outputs on the device (e.g. filtered_xyz_dev straight into
+ * vgt_hip_raycast_points_f32_dev); enqueued on the context's stream, not blocking. */
+int vgt_hip_spheres_cover_points_dev(vgt_hip_ctx* ctx, const float* points_xyz_dev, int64_t num_points,
+                                     const double* world_from_points, const double* sphere_xyzr_dev,
+                                     const int32_t* sphere_link_dev, int64_t num_spheres, const double* link_poses_dev,
+                                     int64_t num_links, int64_t num_configurations, double padding, uint32_t flags,
+                                     int32_t* first_configuration_dev, int32_t* first_sphere_dev,
+                                     float* filtered_xyz_dev);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

@@ -84,6 +84,14 @@ SIGNATURES = {
                                      ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_check_spheres_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _i64, _i64, _f64,
                                          ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_rasterize_spheres": (_int, [_p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _p, _i64, _i64, _f64, _i64,
+                                         ctypes.c_uint32, _p]),
+    "vgt_hip_rasterize_spheres_dev": (_int, [_p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _p, _i64, _i64, _f64, _i64,
+                                             ctypes.c_uint32, _p]),
+    "vgt_hip_spheres_cover_points": (_int, [_p, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _f64, ctypes.c_uint32,
+                                            _p, _p, _p]),
+    "vgt_hip_spheres_cover_points_dev": (_int, [_p, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _f64, ctypes.c_uint32,
+                                                _p, _p, _p]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -165,6 +173,8 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_host_pipeline_min_voxels": (_int, [ctypes.c_int64]),
     "vgt_hip_testing_set_short_line_rows": (_int, [_int]),
     "vgt_hip_testing_set_check_spheres_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_sphere_volume_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
 }
@@ -195,6 +205,8 @@ SPHERES_OUTSIDE_IS_COLLISION = 1
 SPHERES_CLEAR = 0
 SPHERES_COLLISION = 1
 SPHERES_NO_VALUE = 2
+# flag of rasterize_spheres (VGT_HIP_SPHERES_KEEP)
+SPHERES_KEEP = 1
 
 # selection rules, value classes and cell members of select_cells / Cells.select (VGT_HIP_SELECT_*, VGT_HIP_CLASS_*,
 # VGT_HIP_CELL_MEMBER_*)
@@ -223,6 +235,27 @@ SegmentCasts = collections.namedtuple("SegmentCasts", "status hit_index hit_frac
 # are None unless per_sphere
 SphereChecks = collections.namedtuple(
     "SphereChecks", "status min_clearance min_sphere num_below num_outside min_gradient sphere_clearance sphere_gradient")
+
+
+# what Context.spheres_cover_points returns: one entry per point; filtered [N, 3] float32 is None unless asked for
+PointCover = collections.namedtuple("PointCover", "first_configuration first_sphere filtered")
+
+
+def _sphere_model(spheres_xyzr, sphere_link, link_poses):
+    """(xyzr [S, 4] float64, link [S] int32, poses [B, L, 16] float64) as the sphere-model calls take them; poses may
+    come as [B, L, 4, 4] world_from_link matrices."""
+    xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+    link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+    if len(link) != len(xyzr):
+        raise ValueError("sphere_link must hold one link per sphere")
+    poses = np.asarray(link_poses, dtype=np.float64)
+    if poses.ndim == 4:
+        if poses.shape[2:] != (4, 4):
+            raise ValueError("link_poses must have the shape [B, L, 16] or [B, L, 4, 4]")
+        poses = poses.transpose(0, 1, 3, 2).reshape(poses.shape[0], poses.shape[1], 16)
+    if poses.ndim != 3 or poses.shape[2] != 16:
+        raise ValueError("link_poses must have the shape [B, L, 16] or [B, L, 4, 4]")
+    return xyzr, link, np.ascontiguousarray(poses)
 
 
 class VgtHipError(RuntimeError):
@@ -555,6 +588,68 @@ class Context:
             int(num_configurations), float(minimum_clearance), SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0,
             _ptr(status_ptr), _ptr(min_clearance_ptr), _ptr(min_sphere_ptr), _ptr(num_below_ptr), _ptr(num_outside_ptr),
             _ptr(min_gradient_ptr), _ptr(sphere_clearance_ptr), _ptr(sphere_gradient_ptr)))
+
+    def rasterize_spheres(self, shape, resolution, spheres_xyzr, sphere_link, link_poses, padding=0.0, base=0, into=None,
+                          grid_from_world=None):
+        """vgt_hip_rasterize_spheres: the cells of a grid of `shape` that the model's spheres (as for check_spheres;
+        radius + padding) cover in B configurations -> first_configuration int32 of `shape`: base + the least b that
+        covers the cell, -1 where none does.  into: an int32 array of `shape` that is kept (VGT_HIP_SPHERES_KEEP) and
+        lowered in place as an unsigned minimum -- the result of an earlier call, for a motion given in pieces."""
+        xyzr, link, poses = _sphere_model(spheres_xyzr, sphere_link, link_poses)
+        shape = tuple(int(c) for c in shape)
+        if len(shape) != 3:
+            raise ValueError("shape must be (nx, ny, nz)")
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        if into is None:
+            out = np.empty(tuple(max(c, 0) for c in shape), np.int32)
+        else:
+            out = into
+            if not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and
+                    out.flags.writeable and out.shape == shape):
+                raise ValueError("into must be a writeable C-contiguous int32 array of the grid's shape")
+        check(self._lib.vgt_hip_rasterize_spheres(
+            self.handle, *shape, float(resolution), _ptr(xf), _ptr(xyzr), _ptr(link), len(xyzr), _ptr(poses),
+            poses.shape[1], poses.shape[0], float(padding), int(base), SPHERES_KEEP if into is not None else 0,
+            _ptr(out)))
+        return out
+
+    def rasterize_spheres_dev(self, shape, resolution, spheres_xyzr_ptr, sphere_link_ptr, num_spheres, link_poses_ptr,
+                              num_links, num_configurations, first_configuration_ptr, padding=0.0, base=0, keep=False,
+                              grid_from_world=None):
+        """vgt_hip_rasterize_spheres_dev: model, poses and the int32 output on the device (the transform is a host
+        array); enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        check(self._lib.vgt_hip_rasterize_spheres_dev(
+            self.handle, *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(spheres_xyzr_ptr),
+            _ptr(sphere_link_ptr), int(num_spheres), _ptr(link_poses_ptr), int(num_links), int(num_configurations),
+            float(padding), int(base), SPHERES_KEEP if keep else 0, _ptr(first_configuration_ptr)))
+
+    def spheres_cover_points(self, points, spheres_xyzr, sphere_link, link_poses, padding=0.0, world_from_points=None,
+                             filtered=False):
+        """vgt_hip_spheres_cover_points: points [N, 3] float32 (under world_from_points, 16 doubles column-major or 4 x 4
+        transposed by the caller) against the model in B configurations -> PointCover(first_configuration int32,
+        first_sphere int32, filtered): the least (b, s) that covers each point or (-1, -1); filtered=True also gives
+        the cloud with the covered points set to NaN, which the raycast entry points skip."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        xyzr, link, poses = _sphere_model(spheres_xyzr, sphere_link, link_poses)
+        xf = None if world_from_points is None else np.ascontiguousarray(world_from_points, dtype=np.float64).reshape(16)
+        n = len(pts)
+        out = PointCover(np.empty(n, np.int32), np.empty(n, np.int32), np.empty((n, 3), np.float32) if filtered else None)
+        check(self._lib.vgt_hip_spheres_cover_points(
+            self.handle, _ptr(pts), n, _ptr(xf), _ptr(xyzr), _ptr(link), len(xyzr), _ptr(poses), poses.shape[1],
+            poses.shape[0], float(padding), 0, *[_ptr(a) for a in out]))
+        return out
+
+    def spheres_cover_points_dev(self, points_ptr, num_points, spheres_xyzr_ptr, sphere_link_ptr, num_spheres,
+                                 link_poses_ptr, num_links, num_configurations, first_configuration_ptr=None,
+                                 first_sphere_ptr=None, filtered_ptr=None, padding=0.0, world_from_points=None):
+        """vgt_hip_spheres_cover_points_dev: cloud, model, poses and outputs on the device (the transform is a host
+        array; filtered_ptr may be points_ptr); enqueued on the context's stream."""
+        xf = None if world_from_points is None else np.ascontiguousarray(world_from_points, dtype=np.float64).reshape(16)
+        check(self._lib.vgt_hip_spheres_cover_points_dev(
+            self.handle, _ptr(points_ptr), int(num_points), _ptr(xf), _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr),
+            int(num_spheres), _ptr(link_poses_ptr), int(num_links), int(num_configurations), float(padding), 0,
+            _ptr(first_configuration_ptr), _ptr(first_sphere_ptr), _ptr(filtered_ptr)))
 
     def sdf_coarse_gradient_dev(self, sdf_ptr, shape, resolution, gradient_ptr, has_value_ptr=None,
                                 enable_edge_gradients=False, rotation=None):
@@ -927,6 +1022,16 @@ class Context:
         """Testing library only (process-wide there): at most `workgroups` workgroups per check_spheres launch (0 = back
         to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_check_spheres_workgroups(int(workgroups)))
+
+    def set_sphere_volume_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per rasterize_spheres and
+        spheres_cover_points launch (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_sphere_volume_workgroups(int(workgroups)))
+
+    def set_sphere_volume_counters(self, counters_ptr):
+        """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
+        adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
+        check(self._lib.vgt_hip_testing_set_sphere_volume_counters(_ptr(counters_ptr)))
 
     def set_host_pipeline_min_voxels(self, min_voxels):
         """Testing library only (process-wide there): smallest grid the host-pointer SDF entry points pipeline."""

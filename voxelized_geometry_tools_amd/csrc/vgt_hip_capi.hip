@@ -157,6 +157,11 @@ thread_local std::string g_last_error;
 std::atomic<int> g_short_line_override{-1};
 // What vgt_hip_testing_set_check_spheres_workgroups told the sphere-model check, 0 = nothing (the launcher's own limit).
 std::atomic<int> g_check_spheres_workgroups{0};
+// The same from vgt_hip_testing_set_sphere_volume_workgroups, for the sphere rasterizer and the point cover.
+std::atomic<int> g_sphere_volume_workgroups{0};
+// What vgt_hip_testing_set_sphere_volume_counters gave: three uint64 on the device that the sphere rasterizer adds its
+// work counts to (a counting kernel), nullptr = nothing (the product's kernel).
+std::atomic<unsigned long long*> g_sphere_volume_counters{nullptr};
 
 int Fail(int code, const std::string& msg)
 {
@@ -584,6 +589,143 @@ struct CheckSpheresArguments
                                    num_spheres, poses_dev, num_links, num_configurations, minimum_clearance,
                                    (flags & VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION) ? 1 : 0, out_dev,
                                    g_check_spheres_workgroups.load(), stream);
+  }
+};
+
+// What the four sphere-volume entry points share: the model, the poses and the padding, and the checks all of them make
+// before any device work.
+struct SphereVolumeArguments
+{
+  const double* sphere_xyzr;
+  const int32_t* sphere_link;
+  int64_t num_spheres;
+  const double* link_poses;
+  int64_t num_links, num_configurations;
+  double padding;
+
+  // (after the form's own null checks, so that "null" comes first as elsewhere)
+  int CheckCounts() const
+  {
+    if (num_spheres < 0 || num_links < 0 || num_configurations < 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the numbers of spheres, links and configurations must not be negative");
+    return VGT_HIP_OK;
+  }
+  bool MissingModel() const
+  {
+    return (num_spheres > 0 && (!sphere_xyzr || !sphere_link)) ||
+           (num_spheres > 0 && num_configurations > 0 && !link_poses);
+  }
+  int Check() const
+  {
+    if (!std::isfinite(padding)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "padding must be finite");
+    if (num_links == 0 && num_spheres > 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a model with spheres needs at least one link (num_links == 0)");
+    const int64_t most = 0x7fffffffLL;
+    if (num_spheres > most || num_links > most || num_configurations > most ||
+        num_configurations * num_spheres > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "sphere volumes support fewer than 2^31 spheres, links and (configuration, sphere) pairs");
+    return VGT_HIP_OK;
+  }
+  // The host forms' own check: they can look at the model.
+  int CheckModel() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+    {
+      const double radius = sphere_xyzr[4 * s + 3];
+      if (sphere_link[s] < 0 || sphere_link[s] >= num_links)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(s) + ": link " +
+                                                      std::to_string(sphere_link[s]) + " is not in [0, num_links)");
+      if (!(radius >= 0.0))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "sphere " + std::to_string(s) + ": the radius must not be negative or NaN");
+    }
+    return VGT_HIP_OK;
+  }
+  vgt::SphereVolumeModel Model(const double* xyzr_dev, const int32_t* link_dev, const double* poses_dev) const
+  {
+    return vgt::SphereVolumeModel{xyzr_dev,
+                                  link_dev,
+                                  poses_dev,
+                                  static_cast<int>(num_spheres),
+                                  static_cast<int>(num_links),
+                                  static_cast<int>(num_configurations),
+                                  padding};
+  }
+};
+
+// The grid form's arguments and checks (both entry points).
+struct RasterizeSpheresArguments
+{
+  int64_t nx, ny, nz;
+  double resolution;
+  const double* grid_from_world;
+  SphereVolumeArguments body;
+  int64_t base;
+  uint32_t flags;
+  int32_t* first_configuration;
+
+  int64_t NumCells() const { return nx * ny * nz; }
+  bool Keep() const { return (flags & VGT_HIP_SPHERES_KEEP) != 0; }
+  int Check(const vgt_hip_ctx* ctx) const
+  {
+    int rc = body.CheckCounts();
+    if (rc != VGT_HIP_OK) return rc;
+    if (!ctx || !first_configuration || body.MissingModel()) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (nx < 0 || ny < 0 || nz < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must not be negative");
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Grid must have uniform, positive resolution");
+    // (extent by extent: the product of three int64 extents can overflow)
+    const int64_t most = 0x7fffffffLL;
+    if (nx > most || ny > most || nz > most || (nx > 0 && ny > 0 && nz > 0 && (nx * ny > most || nx * ny * nz > most)))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere volumes support grids below 2^31 cells");
+    if (flags & ~VGT_HIP_SPHERES_KEEP) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown sphere-volume flag");
+    rc = body.Check();
+    if (rc != VGT_HIP_OK) return rc;
+    if (base < 0 || base > most - body.num_configurations)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "first_configuration_base must not be negative, and base + configurations at most 2^31 - 1");
+    return VGT_HIP_OK;
+  }
+  hipError_t Launch(const double* xyzr_dev, const int32_t* link_dev, const double* poses_dev, int32_t* first_dev,
+                    hipStream_t stream) const
+  {
+    return vgt::LaunchRasterizeSpheres(nx, ny, nz, resolution, grid_from_world,
+                                       body.Model(xyzr_dev, link_dev, poses_dev), base, Keep(), first_dev,
+                                       g_sphere_volume_workgroups.load(), g_sphere_volume_counters.load(), stream);
+  }
+};
+
+// The point form's arguments and checks (both entry points).
+struct CoverPointsArguments
+{
+  const float* points;
+  int64_t num_points;
+  const double* world_from_points;
+  SphereVolumeArguments body;
+  uint32_t flags;
+  int32_t *first_configuration, *first_sphere;
+  float* filtered;
+
+  int Check(const vgt_hip_ctx* ctx) const
+  {
+    int rc = body.CheckCounts();
+    if (rc != VGT_HIP_OK) return rc;
+    if (num_points < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the number of points must not be negative");
+    if (!ctx || (num_points > 0 && !points) || (!first_configuration && !first_sphere && !filtered) ||
+        body.MissingModel())
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_points > 0x7fffffffLL) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere volumes support fewer than 2^31 points");
+    if (flags) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown sphere-volume flag");
+    return body.Check();
+  }
+  hipError_t Launch(const float* points_dev, const double* xyzr_dev, const int32_t* link_dev, const double* poses_dev,
+                    int32_t* first_configuration_dev, int32_t* first_sphere_dev, float* filtered_dev,
+                    hipStream_t stream) const
+  {
+    return vgt::LaunchCoverPoints(points_dev, num_points, world_from_points, body.Model(xyzr_dev, link_dev, poses_dev),
+                                  first_configuration_dev, first_sphere_dev, filtered_dev,
+                                  g_sphere_volume_workgroups.load(), stream);
   }
 };
 
@@ -1420,6 +1562,18 @@ int vgt_hip_testing_set_short_line_rows(int rows)
 int vgt_hip_testing_set_check_spheres_workgroups(int workgroups)
 {
   g_check_spheres_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups)
+{
+  g_sphere_volume_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_sphere_volume_counters(uint64_t* counters_dev)
+{
+  g_sphere_volume_counters.store(reinterpret_cast<unsigned long long*>(counters_dev));
   return VGT_HIP_OK;
 }
 
@@ -2813,6 +2967,125 @@ int vgt_hip_check_spheres(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, i
                                  num_outside.dev(), min_gradient.dev(),  sphere_clearance.dev(), sphere_gradient.dev()};
       return HipResult(what, a.Launch(sdf.dev(), xyzr.dev(), link.dev(), poses.dev(), out, stream));
     });
+  });
+}
+
+int vgt_hip_rasterize_spheres_dev(vgt_hip_ctx* ctx, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                  const double* grid_from_world, const double* sphere_xyzr_dev,
+                                  const int32_t* sphere_link_dev, int64_t num_spheres, const double* link_poses_dev,
+                                  int64_t num_links, int64_t num_configurations, double padding,
+                                  int64_t first_configuration_base, uint32_t flags, int32_t* first_configuration_dev)
+{
+  const RasterizeSpheresArguments a{nx, ny, nz, resolution, grid_from_world,
+                                    {sphere_xyzr_dev, sphere_link_dev, num_spheres, link_poses_dev, num_links,
+                                     num_configurations, padding},
+                                    first_configuration_base, flags, first_configuration_dev};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  // an empty grid, or nothing to lower in an array that is kept: nothing to do
+  if (a.NumCells() == 0 || (a.Keep() && (num_spheres == 0 || num_configurations == 0))) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(a.Launch(sphere_xyzr_dev, sphere_link_dev, link_poses_dev, first_configuration_dev, ctx->stream),
+              "rasterize spheres");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_rasterize_spheres(vgt_hip_ctx* ctx, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                              const double* grid_from_world, const double* sphere_xyzr_host,
+                              const int32_t* sphere_link_host, int64_t num_spheres, const double* link_poses_host,
+                              int64_t num_links, int64_t num_configurations, double padding,
+                              int64_t first_configuration_base, uint32_t flags, int32_t* first_configuration_host)
+{
+  const RasterizeSpheresArguments a{nx, ny, nz, resolution, grid_from_world,
+                                    {sphere_xyzr_host, sphere_link_host, num_spheres, link_poses_host, num_links,
+                                     num_configurations, padding},
+                                    first_configuration_base, flags, first_configuration_host};
+  int rc = a.Check(ctx);
+  if (rc == VGT_HIP_OK) rc = a.body.CheckModel();
+  if (rc != VGT_HIP_OK) return rc;
+  const size_t cells = static_cast<size_t>(a.NumCells());
+  if (cells == 0) return VGT_HIP_OK;
+  if (num_spheres == 0 || num_configurations == 0)
+  {
+    // nothing covers anything: the answer needs no device
+    for (size_t i = 0; i < cells && !a.Keep(); i++) first_configuration_host[i] = -1;
+    return VGT_HIP_OK;
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "rasterize spheres";
+  const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+  vgt::HostStaging staging;
+  const auto xyzr = staging.In(sphere_xyzr_host, s * 4);
+  const auto link = staging.In(sphere_link_host, s);
+  const auto poses = staging.In(link_poses_host, b * static_cast<size_t>(num_links) * 16);
+  const auto first = a.Keep() ? staging.InOut(first_configuration_host, cells) : staging.Out(first_configuration_host, cells);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    return HipResult(what, a.Launch(xyzr.dev(), link.dev(), poses.dev(), first.dev(), stream));
+  });
+}
+
+int vgt_hip_spheres_cover_points_dev(vgt_hip_ctx* ctx, const float* points_xyz_dev, int64_t num_points,
+                                     const double* world_from_points, const double* sphere_xyzr_dev,
+                                     const int32_t* sphere_link_dev, int64_t num_spheres, const double* link_poses_dev,
+                                     int64_t num_links, int64_t num_configurations, double padding, uint32_t flags,
+                                     int32_t* first_configuration_dev, int32_t* first_sphere_dev,
+                                     float* filtered_xyz_dev)
+{
+  const CoverPointsArguments a{points_xyz_dev, num_points, world_from_points,
+                               {sphere_xyzr_dev, sphere_link_dev, num_spheres, link_poses_dev, num_links,
+                                num_configurations, padding},
+                               flags, first_configuration_dev, first_sphere_dev, filtered_xyz_dev};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_points == 0) return VGT_HIP_OK;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  // (no spheres or no configurations: the kernel writes -1 and the plain copy and reads neither the model nor the poses)
+  VGT_TRY_HIP(a.Launch(points_xyz_dev, sphere_xyzr_dev, sphere_link_dev, link_poses_dev, first_configuration_dev,
+                       first_sphere_dev, filtered_xyz_dev, ctx->stream),
+              "spheres cover points");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_spheres_cover_points(vgt_hip_ctx* ctx, const float* points_xyz_host, int64_t num_points,
+                                 const double* world_from_points, const double* sphere_xyzr_host,
+                                 const int32_t* sphere_link_host, int64_t num_spheres, const double* link_poses_host,
+                                 int64_t num_links, int64_t num_configurations, double padding, uint32_t flags,
+                                 int32_t* first_configuration_host, int32_t* first_sphere_host, float* filtered_xyz_host)
+{
+  const CoverPointsArguments a{points_xyz_host, num_points, world_from_points,
+                               {sphere_xyzr_host, sphere_link_host, num_spheres, link_poses_host, num_links,
+                                num_configurations, padding},
+                               flags, first_configuration_host, first_sphere_host, filtered_xyz_host};
+  int rc = a.Check(ctx);
+  if (rc == VGT_HIP_OK) rc = a.body.CheckModel();
+  if (rc != VGT_HIP_OK) return rc;
+  if (num_points == 0) return VGT_HIP_OK;
+  const size_t n = static_cast<size_t>(num_points);
+  if (num_spheres == 0 || num_configurations == 0)
+  {
+    // nothing covers anything: the answer needs no device
+    for (size_t i = 0; i < n && first_configuration_host; i++) first_configuration_host[i] = -1;
+    for (size_t i = 0; i < n && first_sphere_host; i++) first_sphere_host[i] = -1;
+    if (filtered_xyz_host && filtered_xyz_host != points_xyz_host)
+      std::memmove(filtered_xyz_host, points_xyz_host, n * 3 * sizeof(float));
+    return VGT_HIP_OK;
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "spheres cover points";
+  const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+  vgt::HostStaging staging;
+  const auto points = staging.In(points_xyz_host, n * 3);
+  const auto xyzr = staging.In(sphere_xyzr_host, s * 4);
+  const auto link = staging.In(sphere_link_host, s);
+  const auto poses = staging.In(link_poses_host, b * static_cast<size_t>(num_links) * 16);
+  const auto first_configuration = staging.Out(first_configuration_host, n);
+  const auto first_sphere = staging.Out(first_sphere_host, n);
+  const auto filtered = staging.Out(filtered_xyz_host, n * 3);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    return HipResult(what, a.Launch(points.dev(), xyzr.dev(), link.dev(), poses.dev(), first_configuration.dev(),
+                                    first_sphere.dev(), filtered.dev(), stream));
   });
 }
 

@@ -495,6 +495,31 @@ hipError_t LaunchCheckSpheres(const float* sdf_dev, int64_t nx, int64_t ny, int6
                               double minimum_clearance, int outside_is_collision, const BodyOutputs& out,
                               int max_workgroups, hipStream_t stream);
 
+// --- launchers (body_volume_kernels.hip): sphere models into grids and onto point clouds ---
+// Rules and outputs: include/vgt_hip.h, vgt_hip_rasterize_spheres / vgt_hip_spheres_cover_points.  The model as above.
+struct SphereVolumeModel
+{
+  const double* xyzr;   // [S][4]
+  const int32_t* link;  // [S]
+  const double* poses;  // [B][L][16], column-major
+  int num_spheres, num_links, num_configurations;
+  double padding;
+};
+// Fills first_configuration_dev with -1 unless `keep`, then lowers it.  Grids of 0 to 2^31 - 1 cells, B * S < 2^31,
+// 0 <= base <= 2^31 - 1 - B.  max_workgroups: 0 = the launcher's own limit
+// (vgt_hip_testing_set_sphere_volume_workgroups).  grid_from_world_host: 16 doubles or nullptr.  counters_dev: nullptr, or
+// (a testing build's counting run, vgt_hip_testing_set_sphere_volume_counters) three uint64 to which the launch adds the
+// (cell, sphere) tests it made, those that covered, and the atomics it issued.
+hipError_t LaunchRasterizeSpheres(int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                  const double* grid_from_world_host, const SphereVolumeModel& model, int64_t base,
+                                  bool keep, int32_t* first_configuration_dev, int max_workgroups,
+                                  unsigned long long* counters_dev, hipStream_t stream);
+// Each output may be nullptr; filtered_xyz_dev may be points_xyz_dev.  world_from_points_host: 16 doubles or nullptr.
+hipError_t LaunchCoverPoints(const float* points_xyz_dev, int64_t num_points, const double* world_from_points_host,
+                             const SphereVolumeModel& model, int32_t* first_configuration_dev,
+                             int32_t* first_sphere_dev, float* filtered_xyz_dev, int max_workgroups,
+                             hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
