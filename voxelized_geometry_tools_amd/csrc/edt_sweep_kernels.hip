@@ -47,9 +47,11 @@
 //     handing lower halves of second sweeps to idle workgroups, a packed-word form of sweep 1 (fewer instructions per row,
 //     hardly less time: a row costs its dependent chain, not its instruction count).
 //
-// The kernels are bound by instruction issue and by the latency of their dependent chains, not by HBM: rows are
-// processed kBand at a time (registers), the code below keeps rare paths (refills, exact final conversion) out of
-// the straight-line code, and register and LDS use are sized for kWaves waves per SIMD.
+// The kernels are bound by the latency of their dependent chains and by what their waves wait for (a third of their
+// cycles in s_waitcnt: profiles/r8/sweep_waits.md), not by HBM and not by instruction issue: rows are processed kBand at a
+// time (registers), the code below keeps rare paths (refills, exact final conversion) out of the straight-line code,
+// values of loads issued long ago are taken over where the source says (TakeLoaded) and not where a full drain of the
+// store queue stands in front of them, and register and LDS use are sized for kWaves waves per SIMD.
 #include "edt_device.hpp"
 #include "edt_line_geom.hpp"
 
@@ -104,6 +106,8 @@ static_assert(kWord % kBand == 0 && kBand % 2 == 0, "sizes");
 // Full bands of lines with class changes, by the copy of sweep 2's band code they ran (the emulation's drivers read them;
 // product builds count nothing): [0] with candidates after the second vote, [1] without, [2] with candidates after the first.
 uint64_t class_band_tally[3] = {0, 0, 0};
+// Sweep 1's checks of the ring, per lane, and those that spilled a chunk (a check spills one chunk or none: asserted there).
+uint64_t ring_checks = 0, ring_spills = 0;
 #endif
 
 
@@ -331,6 +335,25 @@ __device__ __forceinline__ uint32_t SpreadLaneMask(uint64_t mask_uniform, [[mayb
 #endif
 }
 
+// The values of vector loads issued long ago are taken over HERE.  Where such a value moves from one variable to another
+// across a loop's back edge the compiler places the copy -- and the s_waitcnt in front of it -- where it likes: at the end
+// of the loop body, behind the stores the body has just issued, as a full drain (vmcnt(0): stores count in vmcnt and the
+// wait for a load that the compiler cannot place among them is for everything).  Opaque to the compiler, so the copy and
+// its wait stand where this is written, and every later use of the value is a use of a register, not of a load.
+__device__ __forceinline__ void TakeLoaded([[maybe_unused]] uint32_t& v)
+{
+#ifndef VGT_HOST_EMULATION
+  asm volatile("" : "+v"(v));
+#endif
+}
+__device__ __forceinline__ void TakeLoaded(uint4& v)
+{
+  TakeLoaded(v.x);
+  TakeLoaded(v.y);
+  TakeLoaded(v.z);
+  TakeLoaded(v.w);
+}
+
 __device__ __forceinline__ uint32_t LowBits(int bits)  // bits in [0, 32]
 {
   return (bits >= 32) ? ~0u : ((1u << bits) - 1u);
@@ -405,6 +428,7 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   using Entry = typename C::Entry;
   // the Y pass reads class records, the X pass the Y pass's int32 field
   constexpr bool kRecords = std::is_same<InT, ClassRecord>::value;
+  constexpr bool kTakeSignWords = kFinal;  // sweep 2 takes its sign words over band by band (X pass)
   static_assert(!(kRecords && kFinal), "records feed the Y pass");
   constexpr int kRing = RingShape<kPacked>::kRing;
   constexpr int kChunk = RingShape<kPacked>::kChunk;
@@ -609,19 +633,25 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
         }
       }
       // Common (in the X pass at nearly every check, for some lanes): a ring without room for kChunk more pushes spills
-      // its oldest chunk.
-      while (__builtin_amdgcn_ballot_w64(D - L > (static_cast<uint32_t>(kRing - kChunk) << kShift)) != 0ull)
+      // its oldest chunk.  ONE chunk is always enough, so this is an exec-masked `if` and not a loop: every check leaves
+      // at most kRing - kChunk entries in the ring (the first finds four; a commit above adds kChunk to at most
+      // 2 kChunk), at most kChunk pushes follow before the next check, and one chunk less is kRing - kChunk again.
+      if (D - L > (static_cast<uint32_t>(kRing - kChunk) << kShift))
       {
-        if (D - L > (static_cast<uint32_t>(kRing - kChunk) << kShift))
-        {
-          Entry buf[kChunk];
-          Entry* const slots = chunk_in_ring(L);
+        Entry buf[kChunk];
+        Entry* const slots = chunk_in_ring(L);
 #pragma unroll
-          for (int j = 0; j < kChunk; j++) buf[j] = chunk_slot(slots, L, j);
-          StoreChunk(spill_ptr(L), buf);
-          L += kChunkSlots;
-        }
+        for (int j = 0; j < kChunk; j++) buf[j] = chunk_slot(slots, L, j);
+        StoreChunk(spill_ptr(L), buf);
+        L += kChunkSlots;
+#ifdef VGT_HOST_EMULATION
+        ring_spills++;
+#endif
       }
+#ifdef VGT_HOST_EMULATION
+      ring_checks++;
+      assert(D - L <= (static_cast<uint32_t>(kRing - kChunk) << kShift));  // never a second chunk at one check
+#endif
     };
 
     int din = kFar;          // distance from the row below this word to the nearest row of the other class below it
@@ -776,6 +806,7 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
         site(q, __mul24(f, f) + q * q, f2 < 2u * static_cast<uint32_t>(kInf16));
       };
       uint4 blk0 = load_block(0), blk1 = load_block(kBlock), blk2 = load_block(2 * kBlock);
+      TakeLoaded(blk0);  // (inside the loop the block at work is registers on every path: its rows wait for nothing)
       uint64_t marks = 0, filled = 0;
       constexpr uint32_t kBandMask = kBand >= 32 ? ~0u : ((1u << (kBand % 32)) - 1u);
       for (int r0 = 0; r0 < n; r0 += kBand)
@@ -783,16 +814,7 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
         __builtin_assume(r0 >= 0 && r0 < 16384);
         const int in_block = r0 & (kBlock - 1);
         const int block_first = r0 - in_block;
-        if (in_block == 0)
-        {
-          if (r0 != 0)
-          {
-            blk0 = blk1;
-            blk1 = blk2;
-            blk2 = load_block(r0 + 2 * kBlock);
-          }
-          block_marks(blk0, r0, marks, filled);
-        }
+        if (in_block == 0) block_marks(blk0, r0, marks, filled);
         const uint32_t band_marks = static_cast<uint32_t>(marks >> in_block) & kBandMask;
         const uint32_t band_filled = static_cast<uint32_t>(filled >> in_block) & kBandMask;
         uint32_t bits;  // sign bits of this band, in the top kBand bits
@@ -825,6 +847,24 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
             }
           }
         }
+        // The block's last band: the next two blocks move up and the one after them is requested.  In front of the sign
+        // word's store, so that the wait for a block requested 64 rows ago is not a wait for a store issued just now.
+        // Two regions with conditions the compiler cannot tell to be the same one: in ONE region the moves become copies at
+        // its end, behind the load, which then goes into registers of its own and is copied -- that is, waited for -- on the
+        // spot (a round trip to memory every 64 rows).  Apart, it goes straight into the registers the third block left.
+        int moves_up = static_cast<int>(in_block + kBand == kBlock && r0 + kBand < n);
+        if (moves_up)
+        {
+          blk0 = blk1;
+          blk1 = blk2;
+          TakeLoaded(blk0);
+          TakeLoaded(blk1);
+        }
+#ifndef VGT_HOST_EMULATION
+        asm volatile("" : "+v"(moves_up));
+        moves_up = __builtin_amdgcn_readfirstlane(moves_up);
+#endif
+        if (moves_up) blk2 = load_block(r0 + kBand + 2 * kBlock);
         band_done(r0, bits);
       }
     }
@@ -1033,6 +1073,14 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
     uint2 info_below = make_uint2(0u, 0u);
     if (nwords > 1) info_below = LoadPair(wave_info + static_cast<int64_t>(nwords - 2) * kWaveSize + lane);
     uint2 info_next = make_uint2(0u, 0u);
+    // (the first band needs both at once; taken over here, the loop below sees registers on every path)
+    if constexpr (kTakeSignWords)
+    {
+      TakeLoaded(info.x);
+      TakeLoaded(info.y);
+      TakeLoaded(info_below.x);
+      TakeLoaded(info_below.y);
+    }
     uint32_t xdn_word = 0, xup_word = 0;
     VGT_GLOBAL OutT* row_out = UniformPointer(GlobalPointer(wave_out + static_cast<int64_t>(n - 1) * rstride));  // row being evaluated
     const int last_band = (n - 1) / kBand * kBand;
@@ -1050,7 +1098,6 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
           info = info_below;
           info_below = info_next;
         }
-        if (w > 1) info_next = LoadPair(wave_info + static_cast<int64_t>(w - 2) * kWaveSize + lane);
         if (classes)
         {
           const uint32_t sw = info.x;
@@ -1061,6 +1108,17 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
           if (r0 == last_band) xup_word &= ~(1u << (valid - 1));      // nothing above the last row
         }
       }
+      // X pass: the word two below this band's is requested by EVERY band of a word (the same pair again) and taken over at
+      // the band's end (see rows()): request and wait stand in one stretch of code with the band's row stores between
+      // them, which the compiler can count.  (A request per word is copied at the loop's end, where the copies of the band
+      // code have joined, behind a wait for everything: a drain of the row stores per band.  That is what the Y pass
+      // still does: there the take-over measured slower, see profiles/r8/sweep_waits.md.)
+      const bool word_begins = sub + kBand == kWord || r0 == last_band;
+      [[maybe_unused]] uint2 info_fresh = make_uint2(0u, 0u);
+      if constexpr (kTakeSignWords)
+        info_fresh = LoadPair(wave_info + static_cast<int64_t>(max(r0 / kWord - 2, 0)) * kWaveSize + lane);
+      else if (word_begins && r0 >= 2 * kWord)
+        info_next = LoadPair(wave_info + static_cast<int64_t>(r0 / kWord - 2) * kWaveSize + lane);
       const uint32_t swb = info.x >> sub;  // bit k: class of row r0 + k
       // distances to the nearest row of the other class below, for 8 rows at a time (dp[k & 7]): counted upwards from
       // the carry of the word and the class changes below the group
@@ -1230,6 +1288,16 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
               row_out = UniformPointer(row_out - rstride);
             }
           }
+        }
+        // The sign word requested at the top of this band is taken over here, inside the band's own copy of the code: the
+        // compiler counts the row stores issued since on every path through a full band, and the wait leaves them in
+        // flight.  (Left to the compiler the value is copied at the loop's end, where the copies of the band code have
+        // joined -- the partial band's with no store it can count -- and the wait is for everything: a drain per band.)
+        if constexpr (kTakeSignWords)
+        {
+          TakeLoaded(info_fresh.x);
+          TakeLoaded(info_fresh.y);
+          if (word_begins) info_next = info_fresh;
         }
       };
       bool small_band = false;
