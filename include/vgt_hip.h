@@ -272,6 +272,9 @@ int vgt_hip_testing_set_check_spheres_workgroups(int workgroups);
 /* The same for the launches of vgt_hip_rasterize_spheres[_dev] and vgt_hip_spheres_cover_points[_dev], so that small
  * inputs already make their persistent waves and workgroups take several trips. */
 int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups);
+/* The same for the evaluation launches of vgt_hip_align_points[_dev], so that a few (pose, 4096-point block) items
+ * already make its persistent workgroups take several trips. */
+int vgt_hip_testing_set_align_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
  * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
  * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
@@ -637,6 +640,107 @@ int vgt_hip_spheres_cover_points_dev(vgt_hip_ctx* ctx, const float* points_xyz_d
                                      int64_t num_links, int64_t num_configurations, double padding, uint32_t flags,
                                      int32_t* first_configuration_dev, int32_t* first_sphere_dev,
                                      float* filtered_xyz_dev);
+
+/* ---- Point clouds aligned to an SDF, batched over pose hypotheses ----
+ * Where is the sensor with respect to the map?  A cloud of N points, B initial poses, a signed distance field: every
+ * pose is evaluated (how far from `target_distance` the field is at the transformed points), refined by up to K damped
+ * Gauss-Newton steps on that residual, and returned with its score.  K = 0 only scores: the measurement model of a
+ * particle filter.  Read-only on the field and the cloud; nothing is synchronised with the host between iterations.
+ * Inputs:
+ *   points_xyz    [N][3] float32, the voxelizer's format (as vgt_hip_spheres_cover_points takes it).  A point with a
+ *                 non-finite coordinate is skipped: it is counted nowhere and contributes +0.0.
+ *   poses         [B][16] doubles, column-major: world_from_points per hypothesis (as link_poses of
+ *                 vgt_hip_check_spheres).  Elements 0-2, 4-6, 8-10 and 12-14 are read and refined; 3, 7, 11 and 15 are
+ *                 handed through to poses_out as they came.
+ *   grid_from_world, rotation   as for vgt_hip_check_spheres: 16 doubles column-major and 9 doubles row-major, each may
+ *                 be NULL, host arrays in both forms.
+ *   pivot         3 doubles (host array in both forms), the point about which rotations are taken, in the poses' frame;
+ *                 NULL = the origin.  The grid's centre keeps translation and rotation decoupled.
+ *
+ * THE DEFINITION.  Everything in double, without contraction, every operator rounded on its own.
+ * evaluate(m): per point p = (x, y, z), widened to double:
+ *   w_r   = ((m[r]*x + m[4+r]*y) + m[8+r]*z) + m[12+r] for r = 0, 1, 2: the expression of vgt_hip_check_spheres.
+ *   d     = the estimate of vgt_hip_sdf_estimate_distance at w (the same code; grid_from_world applied as there).  A
+ *           finite point without a value (w not in the grid, or not finite) counts in num_outside.
+ *   g     = the gradient OF THAT INTERPOLANT, from its eight corner values c_abc (a, b, c in {m, p}: lower / upper index
+ *           along x, y, z, after the half-cell correction) and its weights tx, ty, tz, with
+ *           Lerp(a, b, t) = a*(1 - t) + b*t, low_x = (lower_x + 0.5)*resolution, ex = (low_x + resolution) - low_x,
+ *           tx = (g_x - low_x)/ex (g_x: w in the grid frame), likewise along y and z -- all as the estimate forms them:
+ *             gx = Lerp(Lerp(c_pmm - c_mmm, c_ppm - c_mpm, ty), Lerp(c_pmp - c_mmp, c_ppp - c_mpp, ty), tz) / ex
+ *             gy = Lerp(Lerp(c_mpm - c_mmm, c_ppm - c_pmm, tx), Lerp(c_mpp - c_mmp, c_ppp - c_pmp, tx), tz) / ey
+ *             gz = Lerp(Lerp(c_mmp - c_mmm, c_pmp - c_pmm, tx), Lerp(c_mpp - c_mpm, c_ppp - c_ppm, tx), ty) / ez
+ *           An axis whose two indices coincide (the grid's faces) gives a component of 0.  With `rotation`:
+ *           g <- (R[0]*gx + R[1]*gy + R[2]*gz, R[3]*gx + ..., R[6]*gx + ...), as the coarse gradient is rotated.
+ *   r     = d - target_distance.
+ *   used  iff the point has a value, r, gx, gy and gz are finite and |r| <= max_residual.  A point with a value that is
+ *           not used counts in num_rejected.  num_used + num_outside + num_rejected = the number of finite points.
+ *   q     = w - pivot (pivot = 0 when NULL).
+ *   J     = (gx, gy, gz, q_y*gz - q_z*gy, q_z*gx - q_x*gz, q_x*gy - q_y*gx): the derivative of d under the left
+ *           perturbation T' = Exp(v, omega) T about the pivot.
+ *   terms 28 per used point: H_jk = J_j*J_k for j <= k, row-major (21); b_j = J_j*r (6); e = r*r (1).  A point that is
+ *           not used, or skipped, contributes +0.0 to each.
+ * tree_sum: each of the 28 terms is summed over the points, in point order, by ONE tree, whatever the launch geometry
+ *   and the device: the list is cut into groups of 64 consecutive entries, the last padded with +0.0; a group is
+ *   reduced by  for h in 32, 16, 8, 4, 2, 1: v[i] = v[i] + v[i + h] for i < h;  while more than one group sum is left,
+ *   the procedure repeats on the list of group sums.  No floating-point atomics.
+ * solve: A = H (symmetric) with A_jj = H_jj*(1 + damping); A = L D L^T without pivoting, column by column:
+ *   for j = 0..5:  D_j = A_jj, then for k = 0..j-1 in turn D_j = D_j - (L_jk*L_jk)*D_k;
+ *                  for i = j+1..5:  L_ij = A_ij, then for k = 0..j-1 in turn L_ij = L_ij - (L_ik*L_jk)*D_k; L_ij = L_ij/D_j
+ *   y_i = b_i, then for k = 0..i-1 in turn y_i = y_i - L_ik*y_k  (i = 0..5);   z_i = y_i/D_i;
+ *   x_i = z_i, then for k = i+1..5 in turn x_i = x_i - L_ki*x_k  (i = 5..0);   delta = (v, omega) = -x.
+ *   A D_j that is not > 0, or a delta with a component that is not finite: VGT_HIP_ALIGN_DEGENERATE.
+ * update (a Cayley retraction: no sin / cos): a = omega*0.5, s = 1 + ((a_x*a_x + a_y*a_y) + a_z*a_z), f = 2/s,
+ *   D = I + f*([a]x + [a]x^2), formed as
+ *     D00 = 1 - f*(a_y*a_y + a_z*a_z)   D01 = f*(a_x*a_y - a_z)           D02 = f*(a_x*a_z + a_y)
+ *     D10 = f*(a_x*a_y + a_z)           D11 = 1 - f*(a_x*a_x + a_z*a_z)   D12 = f*(a_y*a_z - a_x)
+ *     D20 = f*(a_x*a_z - a_y)           D21 = f*(a_y*a_z + a_x)           D22 = 1 - f*(a_x*a_x + a_y*a_y)
+ *   m'[4c+r] = (D_r0*m[4c] + D_r1*m[4c+1]) + D_r2*m[4c+2] for c = 0, 1, 2;  u = t - pivot (t_r = m[12+r]);
+ *   m'[12+r] = (((D_r0*u_0 + D_r1*u_1) + D_r2*u_2) + pivot_r) + v_r.
+ * loop, per pose: evaluate the initial pose; then up to K = max_iterations times: solve, update, evaluate.  After EVERY
+ *   evaluation, in this order: num_used < min_points stops the pose as VGT_HIP_ALIGN_TOO_FEW; a pose whose last update
+ *   had max|v_r| <= translation_tolerance and max|omega_r| <= rotation_tolerance stops as VGT_HIP_ALIGN_CONVERGED (it
+ *   has then been evaluated once more, at the pose it returns); a pose that has taken its K steps stops as
+ *   VGT_HIP_ALIGN_ITERATION_LIMIT (with K = 0: straight after the first evaluation); otherwise it is solved, which may
+ *   stop it as VGT_HIP_ALIGN_DEGENERATE.  A pose that stops is returned exactly as it stood at that evaluation, and
+ *   costs no further gathers.
+ * Outputs per pose (`status` is required, every other output may be NULL):
+ *   poses_out [16] (may be the input array), status (uint8), num_used / num_outside / num_rejected (int32),
+ *   sum_squared (double: e), evaluations (int32), normal_equations [27] (H's 21 entries, then b), last_step [6] (the
+ *   last delta applied; zeros when none was).  The counts, sum_squared and normal_equations are those of the last
+ *   evaluation, which is the one AT the returned pose.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any HIP call, outputs untouched: a NULL required pointer (ctx, sdf, points, poses,
+ * status; the workspace in the device form), N == 0, B == 0 or an empty grid, a negative extent or count, a grid of 2^31
+ * cells or more, N or B of 2^31 or more, B * ceil(N / 4096) >= 2^31, a resolution that is not positive and finite,
+ * max_iterations outside [0, 10000], min_points < 6, a damping that is negative or not finite, a max_residual that is
+ * NaN or not positive (+infinity is allowed), a target_distance or a pivot that is not finite, a tolerance that is
+ * negative or NaN, a workspace that is too small.
+ * The device form takes vgt_hip_align_points_workspace_bytes(N, B) bytes of scratch (0 for sizes the call refuses): the
+ * poses in progress, a flag per pose, and the partial sums [B][ceil(N / 4096)][32] doubles. */
+#define VGT_HIP_ALIGN_CONVERGED 0
+#define VGT_HIP_ALIGN_ITERATION_LIMIT 1
+#define VGT_HIP_ALIGN_DEGENERATE 2
+#define VGT_HIP_ALIGN_TOO_FEW 3
+int vgt_hip_align_points(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                         const double* grid_from_world, const double* rotation, const float* points_xyz_host,
+                         int64_t num_points, const double* poses_host, int64_t num_poses, const double* pivot,
+                         int32_t max_iterations, int32_t min_points, double damping, double max_residual,
+                         double target_distance, double translation_tolerance, double rotation_tolerance,
+                         double* poses_out_host, uint8_t* status_host, int32_t* num_used_host, int32_t* num_outside_host,
+                         int32_t* num_rejected_host, double* sum_squared_host, int32_t* evaluations_host,
+                         double* normal_equations_host, double* last_step_host);
+/* Same with the field, the cloud, the poses and the outputs on the device (the two transforms and the pivot stay host
+ * arrays); enqueued on the context's stream, not blocking.  The workspace must stay untouched until the call is done. */
+size_t vgt_hip_align_points_workspace_bytes(int64_t num_points, int64_t num_poses);
+int vgt_hip_align_points_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                             double resolution, const double* grid_from_world, const double* rotation,
+                             const float* points_xyz_dev, int64_t num_points, const double* poses_dev,
+                             int64_t num_poses, const double* pivot, int32_t max_iterations, int32_t min_points,
+                             double damping, double max_residual, double target_distance,
+                             double translation_tolerance, double rotation_tolerance, double* poses_out_dev,
+                             uint8_t* status_dev, int32_t* num_used_dev, int32_t* num_outside_dev,
+                             int32_t* num_rejected_dev, double* sum_squared_dev, int32_t* evaluations_dev,
+                             double* normal_equations_dev, double* last_step_dev, void* workspace_dev,
+                             size_t workspace_bytes);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

@@ -92,6 +92,11 @@ SIGNATURES = {
                                             _p, _p, _p]),
     "vgt_hip_spheres_cover_points_dev": (_int, [_p, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _f64, ctypes.c_uint32,
                                                 _p, _p, _p]),
+    "vgt_hip_align_points": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _p, _i64, _p, _i32, _i32, _f64,
+                                    _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_align_points_workspace_bytes": (_sz, [_i64, _i64]),
+    "vgt_hip_align_points_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _p, _i64, _p, _i32, _i32, _f64,
+                                        _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -174,6 +179,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_short_line_rows": (_int, [_int]),
     "vgt_hip_testing_set_check_spheres_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_align_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
@@ -207,6 +213,11 @@ SPHERES_COLLISION = 1
 SPHERES_NO_VALUE = 2
 # flag of rasterize_spheres (VGT_HIP_SPHERES_KEEP)
 SPHERES_KEEP = 1
+# statuses of align_points (VGT_HIP_ALIGN_*)
+ALIGN_CONVERGED = 0
+ALIGN_ITERATION_LIMIT = 1
+ALIGN_DEGENERATE = 2
+ALIGN_TOO_FEW = 3
 
 # selection rules, value classes and cell members of select_cells / Cells.select (VGT_HIP_SELECT_*, VGT_HIP_CLASS_*,
 # VGT_HIP_CELL_MEMBER_*)
@@ -239,6 +250,25 @@ SphereChecks = collections.namedtuple(
 
 # what Context.spheres_cover_points returns: one entry per point; filtered [N, 3] float32 is None unless asked for
 PointCover = collections.namedtuple("PointCover", "first_configuration first_sphere filtered")
+
+
+# what Context.align_points returns: one entry per pose; poses [B, 16] column-major, normal_equations [B, 27] (H's 21
+# entries row-major over j <= k, then b), last_step [B, 6]
+CloudAlignment = collections.namedtuple(
+    "CloudAlignment",
+    "poses status num_used num_outside num_rejected sum_squared evaluations normal_equations last_step")
+
+
+def _cloud_poses(poses):
+    """[B, 16] float64 column-major world_from_points; poses may come as [B, 4, 4] matrices."""
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.ndim == 3:
+        if poses.shape[1:] != (4, 4):
+            raise ValueError("poses must have the shape [B, 16] or [B, 4, 4]")
+        poses = poses.transpose(0, 2, 1).reshape(poses.shape[0], 16)
+    if poses.ndim != 2 or poses.shape[1] != 16:
+        raise ValueError("poses must have the shape [B, 16] or [B, 4, 4]")
+    return np.ascontiguousarray(poses)
 
 
 def _sphere_model(spheres_xyzr, sphere_link, link_poses):
@@ -651,6 +681,52 @@ class Context:
             int(num_spheres), _ptr(link_poses_ptr), int(num_links), int(num_configurations), float(padding), 0,
             _ptr(first_configuration_ptr), _ptr(first_sphere_ptr), _ptr(filtered_ptr)))
 
+    def align_points(self, sdf, resolution, points, poses, max_iterations=10, min_points=6, damping=0.0,
+                     max_residual=float("inf"), target_distance=0.0, translation_tolerance=0.0, rotation_tolerance=0.0,
+                     pivot=None, grid_from_world=None, rotation=None):
+        """vgt_hip_align_points: a cloud [N, 3] float32 under B pose hypotheses (poses [B, 16] column-major
+        world_from_points, or [B, 4, 4] matrices, transposed here) against an SDF: each pose scored and refined by up to
+        max_iterations damped Gauss-Newton steps (0: scored only) -> CloudAlignment(poses [B, 16], status uint8
+        (ALIGN_*), num_used, num_outside, num_rejected int32, sum_squared float64, evaluations int32, normal_equations
+        [B, 27], last_step [B, 6]).  pivot: 3 doubles in the poses' frame (None: the origin)."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be (nx, ny, nz)")
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        start = _cloud_poses(poses)
+        b = len(start)
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        about = None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+        out = CloudAlignment(np.empty((b, 16), np.float64), np.empty(b, np.uint8), np.empty(b, np.int32),
+                             np.empty(b, np.int32), np.empty(b, np.int32), np.empty(b, np.float64),
+                             np.empty(b, np.int32), np.empty((b, 27), np.float64), np.empty((b, 6), np.float64))
+        check(self._lib.vgt_hip_align_points(
+            self.handle, _ptr(f), *f.shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(pts), len(pts), _ptr(start), b,
+            _ptr(about), int(max_iterations), int(min_points), float(damping), float(max_residual),
+            float(target_distance), float(translation_tolerance), float(rotation_tolerance), *[_ptr(a) for a in out]))
+        return out
+
+    def align_points_dev(self, sdf_ptr, shape, resolution, points_ptr, num_points, poses_ptr, num_poses, status_ptr,
+                         workspace_ptr, workspace_bytes, poses_out_ptr=None, num_used_ptr=None, num_outside_ptr=None,
+                         num_rejected_ptr=None, sum_squared_ptr=None, evaluations_ptr=None, normal_equations_ptr=None,
+                         last_step_ptr=None, max_iterations=10, min_points=6, damping=0.0, max_residual=float("inf"),
+                         target_distance=0.0, translation_tolerance=0.0, rotation_tolerance=0.0, pivot=None,
+                         grid_from_world=None, rotation=None):
+        """vgt_hip_align_points_dev: field, cloud, poses, outputs and the workspace (align_points_workspace_bytes) on
+        the device, the transforms and the pivot host arrays; poses_out_ptr may be poses_ptr; enqueued on the context's
+        stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        about = None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+        check(self._lib.vgt_hip_align_points_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
+            _ptr(points_ptr), int(num_points), _ptr(poses_ptr), int(num_poses), _ptr(about), int(max_iterations),
+            int(min_points), float(damping), float(max_residual), float(target_distance), float(translation_tolerance),
+            float(rotation_tolerance), _ptr(poses_out_ptr), _ptr(status_ptr), _ptr(num_used_ptr), _ptr(num_outside_ptr),
+            _ptr(num_rejected_ptr), _ptr(sum_squared_ptr), _ptr(evaluations_ptr), _ptr(normal_equations_ptr),
+            _ptr(last_step_ptr), _ptr(workspace_ptr), int(workspace_bytes)))
+
     def sdf_coarse_gradient_dev(self, sdf_ptr, shape, resolution, gradient_ptr, has_value_ptr=None,
                                 enable_edge_gradients=False, rotation=None):
         """vgt_hip_sdf_coarse_gradient_dev: field and outputs (3 doubles and, optionally, a byte per voxel) on the
@@ -1028,6 +1104,11 @@ class Context:
         spheres_cover_points launch (0 = back to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_sphere_volume_workgroups(int(workgroups)))
 
+    def set_align_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per evaluation launch of
+        align_points (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_align_workgroups(int(workgroups)))
+
     def set_sphere_volume_counters(self, counters_ptr):
         """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
         adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
@@ -1230,6 +1311,11 @@ def sdf_batch_workspace_bytes(batch, shape):
 def nearest_workspace_bytes(shape):
     """Workspace of Context.nearest_dev; 0 for an empty or over-limit grid."""
     return int(load().vgt_hip_nearest_workspace_bytes(*[int(s) for s in shape]))
+
+
+def align_points_workspace_bytes(num_points, num_poses):
+    """Workspace of Context.align_points_dev; 0 for sizes the call refuses."""
+    return int(load().vgt_hip_align_points_workspace_bytes(int(num_points), int(num_poses)))
 
 
 def sdf_workspace_bytes(shape, variant=0):

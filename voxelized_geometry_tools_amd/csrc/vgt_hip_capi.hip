@@ -157,6 +157,8 @@ thread_local std::string g_last_error;
 std::atomic<int> g_short_line_override{-1};
 // What vgt_hip_testing_set_check_spheres_workgroups told the sphere-model check, 0 = nothing (the launcher's own limit).
 std::atomic<int> g_check_spheres_workgroups{0};
+// The same from vgt_hip_testing_set_align_workgroups, for the evaluation launches of the cloud alignment.
+std::atomic<int> g_align_workgroups{0};
 // The same from vgt_hip_testing_set_sphere_volume_workgroups, for the sphere rasterizer and the point cover.
 std::atomic<int> g_sphere_volume_workgroups{0};
 // What vgt_hip_testing_set_sphere_volume_counters gave: three uint64 on the device that the sphere rasterizer adds its
@@ -524,6 +526,63 @@ int CheckSegmentArguments(const vgt_hip_ctx* ctx, const float* field, int64_t nx
   query->flags = flags;
   return VGT_HIP_OK;
 }
+
+// What both cloud-alignment entry points are called with, and the checks both make before any device work.
+struct AlignPointsArguments
+{
+  const float* sdf;
+  int64_t nx, ny, nz;
+  double resolution;
+  const double *grid_from_world, *rotation;
+  const float* points;
+  int64_t num_points;
+  const double* poses;
+  int64_t num_poses;
+  const double* pivot;
+  int32_t max_iterations, min_points;
+  double damping, max_residual, target_distance, translation_tolerance, rotation_tolerance;
+  vgt::AlignOutputs out;
+
+  int64_t NumCells() const { return nx * ny * nz; }
+  int Check(const vgt_hip_ctx* ctx) const
+  {
+    if (nx < 0 || ny < 0 || nz < 0 || num_points < 0 || num_poses < 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents and the numbers of points and poses must not be negative");
+    if (!ctx || !sdf || !points || !poses || !out.status) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (nx == 0 || ny == 0 || nz == 0 || num_points == 0 || num_poses == 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "cloud alignment needs a grid, a cloud and poses that are not empty");
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Grid must have uniform, positive resolution");
+    const int64_t most = 0x7fffffffLL;
+    if (nx > most || ny > most || nz > most || nx * ny > most || nx * ny * nz > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "cloud alignment supports grids below 2^31 cells");
+    if (vgt::AlignWorkspaceBytes(num_points, num_poses) == 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "cloud alignment supports fewer than 2^31 points, poses and (pose, 4096-point block) pairs");
+    if (max_iterations < 0 || max_iterations > 10000)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "max_iterations must be in [0, 10000]");
+    if (min_points < 6) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "min_points must be at least 6");
+    if (!(damping >= 0.0) || !std::isfinite(damping))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "damping must be finite and not negative");
+    if (!(max_residual > 0.0)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "max_residual must be positive (or +infinity)");
+    if (!std::isfinite(target_distance)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "target_distance must be finite");
+    if (!(translation_tolerance >= 0.0) || !(rotation_tolerance >= 0.0))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the tolerances must not be negative or NaN");
+    if (pivot && !(std::isfinite(pivot[0]) && std::isfinite(pivot[1]) && std::isfinite(pivot[2])))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the pivot must be finite");
+    return VGT_HIP_OK;
+  }
+  hipError_t Launch(const float* sdf_dev, const float* points_dev, const double* poses_dev,
+                    const vgt::AlignOutputs& out_dev, void* workspace_dev, hipStream_t stream) const
+  {
+    const vgt::AlignOptions options{max_iterations,        min_points,         damping, max_residual, target_distance,
+                                    translation_tolerance, rotation_tolerance,
+                                    {pivot ? pivot[0] : 0.0, pivot ? pivot[1] : 0.0, pivot ? pivot[2] : 0.0}};
+    return vgt::LaunchAlignPoints(sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, points_dev, num_points,
+                                  poses_dev, num_poses, options, out_dev, workspace_dev, g_align_workgroups.load(),
+                                  stream);
+  }
+};
 
 // What both sphere-model entry points are called with, and the checks both make before any device work.
 struct CheckSpheresArguments
@@ -1568,6 +1627,12 @@ int vgt_hip_testing_set_check_spheres_workgroups(int workgroups)
 int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups)
 {
   g_sphere_volume_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_align_workgroups(int workgroups)
+{
+  g_align_workgroups.store(workgroups > 0 ? workgroups : 0);
   return VGT_HIP_OK;
 }
 
@@ -3086,6 +3151,86 @@ int vgt_hip_spheres_cover_points(vgt_hip_ctx* ctx, const float* points_xyz_host,
   return staging.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
     return HipResult(what, a.Launch(points.dev(), xyzr.dev(), link.dev(), poses.dev(), first_configuration.dev(),
                                     first_sphere.dev(), filtered.dev(), stream));
+  });
+}
+
+/* ---------------------- point clouds aligned to an SDF ---------------------- */
+
+size_t vgt_hip_align_points_workspace_bytes(int64_t num_points, int64_t num_poses)
+{
+  return vgt::AlignWorkspaceBytes(num_points, num_poses);
+}
+
+int vgt_hip_align_points_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                             double resolution, const double* grid_from_world, const double* rotation,
+                             const float* points_xyz_dev, int64_t num_points, const double* poses_dev,
+                             int64_t num_poses, const double* pivot, int32_t max_iterations, int32_t min_points,
+                             double damping, double max_residual, double target_distance,
+                             double translation_tolerance, double rotation_tolerance, double* poses_out_dev,
+                             uint8_t* status_dev, int32_t* num_used_dev, int32_t* num_outside_dev,
+                             int32_t* num_rejected_dev, double* sum_squared_dev, int32_t* evaluations_dev,
+                             double* normal_equations_dev, double* last_step_dev, void* workspace_dev,
+                             size_t workspace_bytes)
+{
+  const AlignPointsArguments a{sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, points_xyz_dev, num_points,
+                               poses_dev, num_poses, pivot, max_iterations, min_points, damping, max_residual,
+                               target_distance, translation_tolerance, rotation_tolerance,
+                               {poses_out_dev, status_dev, num_used_dev, num_outside_dev, num_rejected_dev,
+                                sum_squared_dev, evaluations_dev, normal_equations_dev, last_step_dev}};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  if (!workspace_dev) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (workspace_bytes < vgt::AlignWorkspaceBytes(num_points, num_poses))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "cloud-alignment workspace too small");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(a.Launch(sdf_dev, points_xyz_dev, poses_dev, a.out, workspace_dev, ctx->stream), "align points");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_align_points(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                         const double* grid_from_world, const double* rotation, const float* points_xyz_host,
+                         int64_t num_points, const double* poses_host, int64_t num_poses, const double* pivot,
+                         int32_t max_iterations, int32_t min_points, double damping, double max_residual,
+                         double target_distance, double translation_tolerance, double rotation_tolerance,
+                         double* poses_out_host, uint8_t* status_host, int32_t* num_used_host, int32_t* num_outside_host,
+                         int32_t* num_rejected_host, double* sum_squared_host, int32_t* evaluations_host,
+                         double* normal_equations_host, double* last_step_host)
+{
+  const AlignPointsArguments a{sdf_host, nx, ny, nz, resolution, grid_from_world, rotation, points_xyz_host, num_points,
+                               poses_host, num_poses, pivot, max_iterations, min_points, damping, max_residual,
+                               target_distance, translation_tolerance, rotation_tolerance,
+                               {poses_out_host, status_host, num_used_host, num_outside_host, num_rejected_host,
+                                sum_squared_host, evaluations_host, normal_equations_host, last_step_host}};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "align points";
+  const size_t n = static_cast<size_t>(num_points), b = static_cast<size_t>(num_poses);
+  // (thirteen arrays, and a staging holds eight: the inputs, the workspace and the poses in one, the other outputs in a
+  // second one inside its body)
+  vgt::HostStaging inputs;
+  const auto sdf = inputs.In(sdf_host, static_cast<size_t>(a.NumCells()));
+  const auto points = inputs.In(points_xyz_host, n * 3);
+  const auto poses = inputs.In(poses_host, b * 16);
+  const auto poses_out = inputs.Out(poses_out_host, b * 16);
+  const auto workspace = inputs.Scratch<void>(vgt::AlignWorkspaceBytes(num_points, num_poses));
+  return inputs.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    vgt::HostStaging outputs;
+    const auto status = outputs.Out(status_host, b);
+    const auto num_used = outputs.Out(num_used_host, b);
+    const auto num_outside = outputs.Out(num_outside_host, b);
+    const auto num_rejected = outputs.Out(num_rejected_host, b);
+    const auto sum_squared = outputs.Out(sum_squared_host, b);
+    const auto evaluations = outputs.Out(evaluations_host, b);
+    const auto normal_equations = outputs.Out(normal_equations_host, b * 27);
+    const auto last_step = outputs.Out(last_step_host, b * 6);
+    return outputs.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+      const vgt::AlignOutputs out{poses_out.dev(),   status.dev(),      num_used.dev(),
+                                  num_outside.dev(), num_rejected.dev(), sum_squared.dev(),
+                                  evaluations.dev(), normal_equations.dev(), last_step.dev()};
+      return HipResult(what, a.Launch(sdf.dev(), points.dev(), poses.dev(), out, workspace.dev(), stream));
+    });
   });
 }
 

@@ -520,6 +520,35 @@ hipError_t LaunchCoverPoints(const float* points_xyz_dev, int64_t num_points, co
                              int32_t* first_sphere_dev, float* filtered_xyz_dev, int max_workgroups,
                              hipStream_t stream);
 
+// --- launcher (align_kernels.hip): point clouds aligned to an SDF ---
+// The definition, every output and the statuses: include/vgt_hip.h, vgt_hip_align_points.
+struct AlignOptions
+{
+  int max_iterations, min_points;
+  double damping, max_residual, target_distance, translation_tolerance, rotation_tolerance;
+  double pivot[3];
+};
+struct AlignOutputs
+{
+  double* poses;
+  uint8_t* status;
+  int32_t *num_used, *num_outside, *num_rejected;
+  double* sum_squared;
+  int32_t* evaluations;
+  double* normal_equations;
+  double* last_step;
+};
+// 0 for sizes the launcher does not take: N or B outside [1, 2^31), B * ceil(N / 4096) >= 2^31.
+size_t AlignWorkspaceBytes(int64_t num_points, int64_t num_poses);
+// Enqueues the whole loop (1 + max_iterations evaluations, each followed by the solve) on `stream`.  out.status is
+// required; out.poses may be poses_dev.  max_workgroups: 0 = the launcher's own limit for the evaluation
+// (vgt_hip_testing_set_align_workgroups).  The two transforms are host arrays (or nullptr).
+hipError_t LaunchAlignPoints(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                             const double* grid_from_world_host, const double* rotation_host,
+                             const float* points_xyz_dev, int64_t num_points, const double* poses_dev,
+                             int64_t num_poses, const AlignOptions& options, const AlignOutputs& out,
+                             void* workspace_dev, int max_workgroups, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
