@@ -275,6 +275,10 @@ int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups);
 /* The same for the evaluation launches of vgt_hip_align_points[_dev], so that a few (pose, 4096-point block) items
  * already make its persistent workgroups take several trips. */
 int vgt_hip_testing_set_align_workgroups(int workgroups);
+/* The same for the launches of vgt_hip_forward_kinematics[_dev] (workgroups of 64 configurations) and
+ * vgt_hip_clearance_joint_gradient[_dev], so that a few hundred configurations already make their persistent waves
+ * stride. */
+int vgt_hip_testing_set_kinematics_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
  * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
  * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
@@ -741,6 +745,141 @@ int vgt_hip_align_points_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx,
                              int32_t* num_rejected_dev, double* sum_squared_dev, int32_t* evaluations_dev,
                              double* normal_equations_dev, double* last_step_dev, void* workspace_dev,
                              size_t workspace_bytes);
+
+/* ---- Forward kinematics: joint values to link poses, and clearance gradients back to joint space ----
+ * The producer of the link_poses [B][L][16] that vgt_hip_check_spheres, vgt_hip_rasterize_spheres and
+ * vgt_hip_spheres_cover_points take, and the way back: what the check says about the worst sphere (or about every
+ * sphere) as a gradient with respect to the joint values.
+ *
+ * A kinematic tree of L links, described once by host arrays (validated and uploaded by vgt_hip_kinematics_create; the
+ * handle serves any number of calls and is destroyed by vgt_hip_kinematics_destroy, before or after its context):
+ *   parent [L] (int32)       -1: the link hangs on the base; otherwise a value in [0, i): links are topologically ordered
+ *   joint_type [L] (int32)   VGT_HIP_JOINT_FIXED 0, VGT_HIP_JOINT_REVOLUTE 1, VGT_HIP_JOINT_PRISMATIC 2
+ *   joint_index [L] (int32)  the column of joint_values the link reads, in [0, J); ignored for FIXED links; several links
+ *                            may read one column (mimic joints)
+ *   axis [L][3] (double)     in the joint frame, used as it is (unit length is the caller's business)
+ *   origin [L][16] (double)  parent_from_joint, column-major (the URDF <origin>); only the elements 0-2, 4-6, 8-10 and
+ *                            12-14 are read
+ * VGT_HIP_ERR_INVALID_ARGUMENT, *out_tree NULL, before any device work: a NULL pointer, L <= 0 or L >= 2^31, J < 0, and
+ * -- the message names the first offending link, e.g. "link 5: parent 7 is not below 5" -- a parent outside [-1, i), an
+ * unknown joint type, a joint_index outside [0, J) on a link that is not FIXED (so also J == 0 with such a link).
+ * A floating base needs no special case: three prismatic and three revolute links.
+ *
+ * vgt_hip_forward_kinematics.  joint_values [B][J] doubles; world_from_base 16 doubles column-major (elements 0-2, 4-6,
+ * 8-10, 12-14 are read), a host array in both forms, may be NULL; joint_limits [J][2] doubles (lower, upper), a host array
+ * in both forms, may be NULL.  THE DEFINITION, everything in double, without contraction, every operator rounded on its
+ * own:
+ * sin / cos of a revolute value q (plain arithmetic, so that every implementation gives the same bits):
+ *   k     = rint(q * 0x1.45f306dc9c883p-1)                     (round to nearest even; 2/pi)
+ *   r     = ((q - k*P1) - k*P2) - k*P3   with P1 = 0x1.921fb54400000p+0, P2 = 0x1.0b4611a600000p-34,
+ *           P3 = 0x1.3198a2e037073p-69   (pi/2 in two pieces of 33 bits and the rounded rest)
+ *   z     = r*r
+ *   ps    = S17; ps = ps*z + S15; ... ; ps = ps*z + S3         S_n = (-1)^((n-1)/2) / n!, correctly rounded
+ *   sin_r = r + (r*z)*ps
+ *   pc    = C16; pc = pc*z + C14; ... ; pc = pc*z + C2         C_n = (-1)^(n/2) / n!, correctly rounded
+ *   cos_r = 1 + z*pc
+ *   (sin, cos) by k & 3 with k as int64: 0 (sin_r, cos_r); 1 (cos_r, -sin_r); 2 (-sin_r, -cos_r); 3 (-cos_r, sin_r).
+ *   q = 0 gives exactly (0, 1): a zero joint leaves the pose untouched bit for bit.  Within 4 * 2^-53 absolute of a
+ *   correctly rounded sin / cos for |q| <= 2^20 (tests/test_kinematics_ref.py measures 2 * 2^-53).
+ * rotation of a revolute link about axis (x, y, z), v = 1 - c:
+ *   R00 = c + (x*x)*v      R01 = (x*y)*v - z*s    R02 = (x*z)*v + y*s
+ *   R10 = (x*y)*v + z*s    R11 = c + (y*y)*v      R12 = (y*z)*v - x*s
+ *   R20 = (x*z)*v - y*s    R21 = (y*z)*v + x*s    R22 = c + (z*z)*v          the translation is zero
+ * product A.B of two 3 x 4 transforms:
+ *   rotation (A_r0*B_0c + A_r1*B_1c) + A_r2*B_2c;  translation ((A_r0*t_0 + A_r1*t_1) + A_r2*t_2) + tA_r  (t: B's)
+ * pose of link i:  F = P . origin_i, with P the pose of parent[i], or world_from_base for parent -1; with a NULL base F
+ *   is origin_i's twelve elements as they are, no arithmetic.
+ *   FIXED      T_i = F
+ *   REVOLUTE   the rotation of T_i is that of F . (R, 0) by the product rule; the translation is F's own, unchanged
+ *   PRISMATIC  the rotation is F's, unchanged; the translation is the product rule applied to t = (x*q, y*q, z*q)
+ * Every pose is this one fixed sequence of operations: the answer does not depend on the launch geometry.
+ * Outputs:
+ *   link_poses [B][L][16] doubles column-major; the elements 3, 7, 11, 15 are written as 0, 0, 0, 1: the memory of a
+ *              std::vector<Eigen::Isometry3d>, and what the three sphere-model calls take as it stands
+ *   status [B] uint8, may be NULL: bit VGT_HIP_FK_NOT_COMPUTABLE 1: a link that is not FIXED read a value that is not
+ *              finite, or a REVOLUTE link read |q| > 2^20; the twelve elements of that link are NaN, and so are those
+ *              of every descendant (NaN by arithmetic); every other link is computed.  vgt_hip_check_spheres counts the
+ *              spheres of such links as "without a value".  Bit VGT_HIP_FK_OUTSIDE_LIMITS 2: with limits given, some
+ *              joint_values[b][j] < lower_j or > upper_j for a j in [0, J) (NaN compares false); the poses are computed
+ *              all the same.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer (ctx, tree, link_poses; joint_values
+ * when J > 0), a negative B, B >= 2^31, B * L >= 2^31, a tree of another context.  B == 0 succeeds, and the host form
+ * then needs no device.  The host form blocks; the device form (joint values, poses and status on the device) is
+ * enqueued on the context's stream.  Calls that use one tree are serialised by the context.
+ *
+ * vgt_hip_clearance_joint_gradient.  Inputs: the tree, link_poses as the forward kinematics wrote them, the sphere model
+ * of vgt_hip_check_spheres (sphere_xyzr [S][4], sphere_link [S]) and what the check returned, as exactly one of two pairs
+ * (the other pair NULL):
+ *   worst-sphere form   min_sphere [B] (int32) and min_gradient [B][3]
+ *   summed form         sphere_weight [B][S] (double) and sphere_gradient [B][S][3]
+ * Output: joint_gradient [B][J] doubles.  For sphere s on link k with gradient g: p = the sphere's world centre by
+ * vgt_hip_check_spheres' expression w_r.  Walk i = k, parent[k], ... up to the base; for each link on the way that is
+ * not FIXED, with m the pose of link i:
+ *   a_r  = (m[r]*x + m[4+r]*y) + m[8+r]*z          (x, y, z): axis_i
+ *   REVOLUTE   d_r = p_r - m[12+r];  u = (a1*d2 - a2*d1, a2*d0 - a0*d2, a0*d1 - a1*d0);  term = (g0*u0 + g1*u1) + g2*u2
+ *   PRISMATIC  term = (g0*a0 + g1*a1) + g2*a2
+ * Worst-sphere form: every acc_j starts at +0.0, then acc_j = acc_j + term in walk order for j = joint_index[i], for the
+ *   sphere min_sphere[b].  The whole row is NaN when min_sphere[b] is outside [0, S) or that sphere's link outside
+ *   [0, L).  The result is d min_clearance / d q wherever the worst sphere does not change (for revolute axes of unit
+ *   length: with another length R above is no rotation, and the term is the definition, not a derivative).
+ * Summed form: the spheres in ascending s, each sphere's terms in walk order, acc_j = acc_j + w*term with
+ *   w = sphere_weight[b][s].  A sphere with w == 0, or with a link outside [0, L), is skipped entirely: its NaN gradient
+ *   then does no harm.
+ * That fixed order is the definition.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer (ctx, tree; link_poses, the model's two
+ * arrays and joint_gradient when B > 0 and J > 0), not exactly one complete pair, a negative count, B, S, B * L, B * J
+ * or B * S of 2^31 or more, a tree of another context.  B == 0 and J == 0 succeed without a device; S == 0 gives NaN
+ * rows (worst-sphere form) or +0.0 (summed form). */
+#define VGT_HIP_JOINT_FIXED 0
+#define VGT_HIP_JOINT_REVOLUTE 1
+#define VGT_HIP_JOINT_PRISMATIC 2
+#define VGT_HIP_FK_NOT_COMPUTABLE 1
+#define VGT_HIP_FK_OUTSIDE_LIMITS 2
+typedef struct vgt_hip_kinematics vgt_hip_kinematics;
+int vgt_hip_kinematics_create(vgt_hip_ctx* ctx, int64_t num_links, int64_t num_joints, const int32_t* parent,
+                              const int32_t* joint_type, const int32_t* joint_index, const double* axis,
+                              const double* origin, vgt_hip_kinematics** out_tree);
+void vgt_hip_kinematics_destroy(vgt_hip_kinematics* tree);
+int64_t vgt_hip_kinematics_num_links(const vgt_hip_kinematics* tree);
+int64_t vgt_hip_kinematics_num_joints(const vgt_hip_kinematics* tree);
+/* How many links' poses the forward kinematics keeps in LDS for their descendants: those of the first so many links
+ * that are the parent of a link other than the next one.  A link whose parent is a later such link reads its own
+ * earlier output back; the answer is the same.  A constant of the kernel (csrc/kinematics_kernels.hip), exposed so that
+ * tests build trees on both sides of it. */
+int32_t vgt_hip_kinematics_lds_links(void);
+int vgt_hip_forward_kinematics(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* joint_values_host,
+                               int64_t num_configurations, const double* world_from_base, const double* joint_limits,
+                               double* link_poses_host, uint8_t* status_host);
+int vgt_hip_forward_kinematics_dev(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                                   int64_t num_configurations, const double* world_from_base,
+                                   const double* joint_limits, double* link_poses_dev, uint8_t* status_dev);
+int vgt_hip_clearance_joint_gradient(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* link_poses_host,
+                                     int64_t num_configurations, const double* sphere_xyzr_host,
+                                     const int32_t* sphere_link_host, int64_t num_spheres, const int32_t* min_sphere_host,
+                                     const double* min_gradient_host, const double* sphere_weight_host,
+                                     const double* sphere_gradient_host, double* joint_gradient_host);
+int vgt_hip_clearance_joint_gradient_dev(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* link_poses_dev,
+                                         int64_t num_configurations, const double* sphere_xyzr_dev,
+                                         const int32_t* sphere_link_dev, int64_t num_spheres,
+                                         const int32_t* min_sphere_dev, const double* min_gradient_dev,
+                                         const double* sphere_weight_dev, const double* sphere_gradient_dev,
+                                         double* joint_gradient_dev);
+/* The three in one call, host arrays in and out: vgt_hip_forward_kinematics on joint_values, vgt_hip_check_spheres on
+ * its poses, and -- when joint_gradient_host is not NULL -- the worst-sphere form of vgt_hip_clearance_joint_gradient
+ * on what the check found.  The poses are made and used on the device and never visit the host; every output is what
+ * the three calls give one after the other.  Arguments, outputs and errors as theirs (num_links is the tree's);
+ * fk_status_host (the forward kinematics' status) may be NULL.  B == 0 succeeds without a device.  Blocking. */
+int vgt_hip_check_spheres_from_joints(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz,
+                                      double resolution, const double* grid_from_world, const double* rotation,
+                                      const double* sphere_xyzr_host, const int32_t* sphere_link_host,
+                                      int64_t num_spheres, const vgt_hip_kinematics* tree,
+                                      const double* joint_values_host, int64_t num_configurations,
+                                      const double* world_from_base, const double* joint_limits,
+                                      double minimum_clearance, uint32_t flags, uint8_t* status_host,
+                                      double* min_clearance_host, int32_t* min_sphere_host, int32_t* num_below_host,
+                                      int32_t* num_outside_host, double* min_gradient_host,
+                                      double* sphere_clearance_host, double* sphere_gradient_host,
+                                      uint8_t* fk_status_host, double* joint_gradient_host);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

@@ -97,6 +97,17 @@ SIGNATURES = {
     "vgt_hip_align_points_workspace_bytes": (_sz, [_i64, _i64]),
     "vgt_hip_align_points_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _i64, _p, _i64, _p, _i32, _i32, _f64,
                                         _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz]),
+    "vgt_hip_kinematics_create": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, ctypes.POINTER(_p)]),
+    "vgt_hip_kinematics_destroy": (None, [_p]),
+    "vgt_hip_kinematics_num_links": (_i64, [_p]),
+    "vgt_hip_kinematics_num_joints": (_i64, [_p]),
+    "vgt_hip_kinematics_lds_links": (_i32, []),
+    "vgt_hip_forward_kinematics": (_int, [_p, _p, _p, _i64, _p, _p, _p, _p]),
+    "vgt_hip_forward_kinematics_dev": (_int, [_p, _p, _p, _i64, _p, _p, _p, _p]),
+    "vgt_hip_clearance_joint_gradient": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "vgt_hip_clearance_joint_gradient_dev": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_spheres_from_joints": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p,
+                                                 _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -180,6 +191,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_check_spheres_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_align_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_kinematics_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
@@ -214,6 +226,10 @@ SPHERES_NO_VALUE = 2
 # flag of rasterize_spheres (VGT_HIP_SPHERES_KEEP)
 SPHERES_KEEP = 1
 # statuses of align_points (VGT_HIP_ALIGN_*)
+# joint types of a kinematic tree and the status bits of the forward kinematics (VGT_HIP_JOINT_*, VGT_HIP_FK_*)
+JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1, 2
+FK_NOT_COMPUTABLE = 1
+FK_OUTSIDE_LIMITS = 2
 ALIGN_CONVERGED = 0
 ALIGN_ITERATION_LIMIT = 1
 ALIGN_DEGENERATE = 2
@@ -269,6 +285,40 @@ def _cloud_poses(poses):
     if poses.ndim != 2 or poses.shape[1] != 16:
         raise ValueError("poses must have the shape [B, 16] or [B, 4, 4]")
     return np.ascontiguousarray(poses)
+
+
+# what Context.check_spheres_from_joints returns: SphereChecks' fields, then fk_status [B] uint8 (FK_* bits) and
+# joint_gradient [B, J] (None unless asked for)
+JointSphereChecks = collections.namedtuple("JointSphereChecks", SphereChecks._fields + ("fk_status", "joint_gradient"))
+
+
+def _joint_values(tree, joint_values):
+    """[B, J] float64 for the tree's J columns."""
+    q = np.ascontiguousarray(joint_values, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] != tree.num_joints:
+        raise ValueError("joint_values must have the shape [B, %d]" % tree.num_joints)
+    return q
+
+
+def _base_transform(world_from_base):
+    """16 float64 column-major, or None; a [4, 4] matrix is transposed to column-major."""
+    if world_from_base is None:
+        return None
+    m = np.asarray(world_from_base, dtype=np.float64)
+    if m.shape == (4, 4):
+        m = m.T
+    if m.size != 16:
+        raise ValueError("world_from_base must hold 16 values")
+    return np.ascontiguousarray(m).reshape(16)
+
+
+def _joint_limits(tree, joint_limits):
+    if joint_limits is None:
+        return None
+    limits = np.ascontiguousarray(joint_limits, dtype=np.float64)
+    if limits.shape != (tree.num_joints, 2):
+        raise ValueError("joint_limits must have the shape [%d, 2]" % tree.num_joints)
+    return limits
 
 
 def _sphere_model(spheres_xyzr, sphere_link, link_poses):
@@ -618,6 +668,96 @@ class Context:
             int(num_configurations), float(minimum_clearance), SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0,
             _ptr(status_ptr), _ptr(min_clearance_ptr), _ptr(min_sphere_ptr), _ptr(num_below_ptr), _ptr(num_outside_ptr),
             _ptr(min_gradient_ptr), _ptr(sphere_clearance_ptr), _ptr(sphere_gradient_ptr)))
+
+    def kinematics(self, parent, joint_type, joint_index, axis, origin, num_joints=None):
+        """vgt_hip_kinematics_create: a tree of L links from parent [L], joint_type [L] (JOINT_*), joint_index [L],
+        axis [L, 3] and origin [L, 16] (column-major parent_from_joint) or [L, 4, 4] (matrices, transposed here).
+        num_joints: the number of columns of the joint values; by default 1 + the largest joint_index of a link that is
+        not fixed.  Returns a KinematicTree (close() destroys it)."""
+        return KinematicTree(self, parent, joint_type, joint_index, axis, origin, num_joints)
+
+    def forward_kinematics(self, tree, joint_values, world_from_base=None, joint_limits=None):
+        """vgt_hip_forward_kinematics: joint_values [B, J] -> (link_poses [B, L, 16] float64 column-major, as the
+        sphere-model calls take them, status [B] uint8 of FK_* bits).  world_from_base: 16 doubles column-major or a
+        [4, 4] matrix; joint_limits [J, 2]."""
+        q = _joint_values(tree, joint_values)
+        b = q.shape[0]
+        poses = np.empty((b, tree.num_links, 16), np.float64)
+        status = np.empty(b, np.uint8)
+        check(self._lib.vgt_hip_forward_kinematics(self.handle, tree._handle_or_raise(), _ptr(q), b,
+                                                   _ptr(_base_transform(world_from_base)),
+                                                   _ptr(_joint_limits(tree, joint_limits)), _ptr(poses), _ptr(status)))
+        return poses, status
+
+    def forward_kinematics_dev(self, tree, joint_values_ptr, num_configurations, link_poses_ptr, status_ptr=None,
+                               world_from_base=None, joint_limits=None):
+        """vgt_hip_forward_kinematics_dev: joint values, poses and status on the device (the base transform and the
+        limits are host arrays); enqueued on the context's stream."""
+        check(self._lib.vgt_hip_forward_kinematics_dev(
+            self.handle, tree._handle_or_raise(), _ptr(joint_values_ptr), int(num_configurations),
+            _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)), _ptr(link_poses_ptr),
+            _ptr(status_ptr)))
+
+    def clearance_joint_gradient(self, tree, link_poses, spheres_xyzr, sphere_link, min_sphere=None, min_gradient=None,
+                                 sphere_weight=None, sphere_gradient=None):
+        """vgt_hip_clearance_joint_gradient: what check_spheres returned, mapped to joint space -> joint_gradient [B, J].
+        Exactly one pair: (min_sphere [B], min_gradient [B, 3]) or (sphere_weight [B, S], sphere_gradient [B, S, 3])."""
+        xyzr, link, poses = _sphere_model(spheres_xyzr, sphere_link, link_poses)
+        if poses.shape[1] != tree.num_links:
+            raise ValueError("link_poses must hold the tree's %d links per configuration" % tree.num_links)
+        b, s = poses.shape[0], len(xyzr)
+        ms = None if min_sphere is None else np.ascontiguousarray(min_sphere, dtype=np.int32).reshape(-1)
+        mg = None if min_gradient is None else np.ascontiguousarray(min_gradient, dtype=np.float64).reshape(-1, 3)
+        sw = None if sphere_weight is None else np.ascontiguousarray(sphere_weight, dtype=np.float64).reshape(-1, s)
+        sg = None if sphere_gradient is None else np.ascontiguousarray(sphere_gradient, dtype=np.float64).reshape(-1, s, 3)
+        for a in (ms, mg, sw, sg):
+            if a is not None and len(a) != b:
+                raise ValueError("one entry per configuration")
+        out = np.empty((b, tree.num_joints), np.float64)
+        check(self._lib.vgt_hip_clearance_joint_gradient(
+            self.handle, tree._handle_or_raise(), _ptr(poses), b, _ptr(xyzr), _ptr(link), s, _ptr(ms), _ptr(mg), _ptr(sw),
+            _ptr(sg), _ptr(out)))
+        return out
+
+    def clearance_joint_gradient_dev(self, tree, link_poses_ptr, num_configurations, spheres_xyzr_ptr, sphere_link_ptr,
+                                     num_spheres, joint_gradient_ptr, min_sphere_ptr=None, min_gradient_ptr=None,
+                                     sphere_weight_ptr=None, sphere_gradient_ptr=None):
+        """vgt_hip_clearance_joint_gradient_dev: every array on the device; enqueued on the context's stream."""
+        check(self._lib.vgt_hip_clearance_joint_gradient_dev(
+            self.handle, tree._handle_or_raise(), _ptr(link_poses_ptr), int(num_configurations), _ptr(spheres_xyzr_ptr),
+            _ptr(sphere_link_ptr), int(num_spheres), _ptr(min_sphere_ptr), _ptr(min_gradient_ptr),
+            _ptr(sphere_weight_ptr), _ptr(sphere_gradient_ptr), _ptr(joint_gradient_ptr)))
+
+    def check_spheres_from_joints(self, sdf, resolution, spheres_xyzr, sphere_link, tree, joint_values,
+                                  minimum_clearance=0.0, outside_is_collision=False, per_sphere=False,
+                                  grid_from_world=None, rotation=None, world_from_base=None, joint_limits=None,
+                                  joint_gradient=False):
+        """vgt_hip_check_spheres_from_joints: joint values in, the sphere-model check out.  One call uploads the field,
+        the model and joint_values [B, J] and runs the forward kinematics, the check and -- joint_gradient=True -- the
+        worst-sphere joint gradient on the device; the poses never visit the host.  Returns JointSphereChecks: the
+        fields of SphereChecks, fk_status [B] uint8 and joint_gradient [B, J] (None unless asked for)."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be an (nx, ny, nz) grid")
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        q = _joint_values(tree, joint_values)
+        b, s = q.shape[0], len(xyzr)
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        out = JointSphereChecks(np.empty(b, np.uint8), np.empty(b, np.float64), np.empty(b, np.int32),
+                                np.empty(b, np.int32), np.empty(b, np.int32), np.empty((b, 3), np.float64),
+                                np.empty((b, s), np.float64) if per_sphere else None,
+                                np.empty((b, s, 3), np.float64) if per_sphere else None, np.empty(b, np.uint8),
+                                np.empty((b, tree.num_joints), np.float64) if joint_gradient else None)
+        check(self._lib.vgt_hip_check_spheres_from_joints(
+            self.handle, _ptr(f), *f.shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(xyzr), _ptr(link), s,
+            tree._handle_or_raise(), _ptr(q), b, _ptr(_base_transform(world_from_base)),
+            _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
+            SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0, *[_ptr(a) for a in out]))
+        return out
 
     def rasterize_spheres(self, shape, resolution, spheres_xyzr, sphere_link, link_poses, padding=0.0, base=0, into=None,
                           grid_from_world=None):
@@ -1109,6 +1249,11 @@ class Context:
         align_points (0 = back to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_align_workgroups(int(workgroups)))
 
+    def set_kinematics_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per launch of forward_kinematics
+        and clearance_joint_gradient (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_kinematics_workgroups(int(workgroups)))
+
     def set_sphere_volume_counters(self, counters_ptr):
         """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
         adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
@@ -1322,6 +1467,66 @@ def sdf_workspace_bytes(shape, variant=0):
     """Workspace of the device-resident SDF entry points (variant != 0: a cross-check pipeline of the testing library)."""
     lib = load(testing=int(variant) != 0)
     return int(lib.vgt_hip_sdf_workspace_bytes_for_variant(*[int(s) for s in shape], int(variant)))
+
+
+def kinematics_lds_links():
+    """vgt_hip_kinematics_lds_links: how many links' poses the forward kinematics keeps in LDS (a constant of the kernel)."""
+    return int(load().vgt_hip_kinematics_lds_links())
+
+
+class KinematicTree:
+    """A kinematic tree on the device (vgt_hip_kinematics): made by Context.kinematics, used by forward_kinematics and
+    clearance_joint_gradient any number of times."""
+
+    def __init__(self, ctx, parent, joint_type, joint_index, axis, origin, num_joints=None):
+        self.handle = None
+        parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        joint_type = np.ascontiguousarray(joint_type, dtype=np.int32).reshape(-1)
+        joint_index = np.ascontiguousarray(joint_index, dtype=np.int32).reshape(-1)
+        links = len(parent)
+        axis = np.ascontiguousarray(axis, dtype=np.float64)
+        origin = np.asarray(origin, dtype=np.float64)
+        if origin.ndim == 3:
+            if origin.shape[1:] != (4, 4):
+                raise ValueError("origin must have the shape [L, 16] or [L, 4, 4]")
+            origin = origin.transpose(0, 2, 1).reshape(origin.shape[0], 16)
+        origin = np.ascontiguousarray(origin)
+        if len(joint_type) != links or len(joint_index) != links or axis.shape != (links, 3) or \
+                origin.shape != (links, 16):
+            raise ValueError("a kinematic tree holds one parent, joint type, joint index, axis [3] and origin [16] per link")
+        if num_joints is None:
+            moving = joint_index[joint_type != JOINT_FIXED]
+            num_joints = int(moving.max()) + 1 if len(moving) else 0
+        h = _p()
+        check(ctx._lib.vgt_hip_kinematics_create(ctx.handle, links, int(num_joints), _ptr(parent), _ptr(joint_type),
+                                                 _ptr(joint_index), _ptr(axis), _ptr(origin), ctypes.byref(h)))
+        self._lib = ctx._lib
+        self.handle = h
+        self.num_links = links
+        self.num_joints = int(num_joints)
+        ctx._adopt(self)
+
+    def _handle_or_raise(self):
+        if not self.handle:
+            raise ValueError("the kinematic tree has been closed")
+        return self.handle
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.vgt_hip_kinematics_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class TrackingGrids:

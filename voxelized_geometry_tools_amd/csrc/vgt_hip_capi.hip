@@ -129,6 +129,18 @@ struct vgt_hip_filter
   void* pin = nullptr;
 };
 
+// A kinematic tree on the device (vgt_hip_kinematics_create): the validated link records and room for one call's joint
+// limits.
+struct vgt_hip_kinematics
+{
+  vgt_hip_ctx* ctx = nullptr;
+  int device = -1;
+  int64_t num_links = 0, num_joints = 0;
+  int lds_links = 0;         // the LDS slots of the tree (vgt::AssignKinematicsLdsSlots)
+  vgt::DeviceTemp links;     // [num_links] vgt::KinematicLink
+  vgt::DeviceTemp limits;    // [num_joints][2] doubles: the joint_limits of the call being enqueued
+};
+
 // Device copy of a grid of cell records (occupancy + optional object id) and the buffers the
 // per-object SDF extractions reuse.
 struct vgt_hip_cells
@@ -159,6 +171,8 @@ std::atomic<int> g_short_line_override{-1};
 std::atomic<int> g_check_spheres_workgroups{0};
 // The same from vgt_hip_testing_set_align_workgroups, for the evaluation launches of the cloud alignment.
 std::atomic<int> g_align_workgroups{0};
+// The same from vgt_hip_testing_set_kinematics_workgroups, for the forward kinematics and the joint gradient.
+std::atomic<int> g_kinematics_workgroups{0};
 // The same from vgt_hip_testing_set_sphere_volume_workgroups, for the sphere rasterizer and the point cover.
 std::atomic<int> g_sphere_volume_workgroups{0};
 // What vgt_hip_testing_set_sphere_volume_counters gave: three uint64 on the device that the sphere rasterizer adds its
@@ -1633,6 +1647,12 @@ int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups)
 int vgt_hip_testing_set_align_workgroups(int workgroups)
 {
   g_align_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_kinematics_workgroups(int workgroups)
+{
+  g_kinematics_workgroups.store(workgroups > 0 ? workgroups : 0);
   return VGT_HIP_OK;
 }
 
@@ -4711,6 +4731,371 @@ int vgt_hip_sdf_slab_finish_dev(vgt_hip_ctx* ctx, int64_t nx, int64_t ny, int64_
   }
   if (minmax_dev) VGT_TRY_HIP(vgt::LaunchDecodeMinMax(ws.minmax_enc, minmax_dev, s), "min/max");
   return timer.Finish(s, kernel_ms, 3);
+}
+
+/* ------------------- forward kinematics and the clearance gradient in joint space ------------------- */
+
+namespace
+{
+constexpr int64_t kTwoTo31 = int64_t{1} << 31;
+
+// The checks of the two forward-kinematics entry points; *done: nothing is left to do (B == 0).
+int CheckForwardKinematics(const vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* joint_values,
+                           int64_t num_configurations, const double* link_poses, bool* done)
+{
+  *done = false;
+  if (!ctx || !tree || !link_poses) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_configurations < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "negative number of configurations");
+  if (num_configurations >= kTwoTo31)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "forward kinematics supports fewer than 2^31 configurations");
+  if (num_configurations == 0)
+  {
+    *done = true;  // (before the tree is looked at)
+    return VGT_HIP_OK;
+  }
+  if (tree->ctx != ctx) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree belongs to another context");
+  if (tree->num_joints > 0 && !joint_values) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_configurations * tree->num_links >= kTwoTo31)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "forward kinematics supports fewer than 2^31 (configuration, link) pairs");
+  return VGT_HIP_OK;
+}
+
+// Enqueues one forward kinematics on `stream`; the context's mutex is held (the tree's limits buffer is one per tree).
+hipError_t EnqueueForwardKinematics(const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                                    int64_t num_configurations, const double* world_from_base,
+                                    const double* joint_limits, double* link_poses_dev, uint8_t* status_dev,
+                                    hipStream_t stream)
+{
+  const bool limited = joint_limits && tree->num_joints > 0;
+  if (limited)
+  {
+    // (pageable host memory: the runtime has taken its copy when the call returns)
+    const hipError_t err = hipMemcpyAsync(tree->limits.as<double>(), joint_limits,
+                                          static_cast<size_t>(tree->num_joints) * 2 * sizeof(double),
+                                          hipMemcpyHostToDevice, stream);
+    if (err != hipSuccess) return err;
+  }
+  return vgt::LaunchForwardKinematics(tree->links.as<vgt::KinematicLink>(), tree->num_links, tree->num_joints,
+                                      tree->lds_links, joint_values_dev, num_configurations, world_from_base,
+                                      limited ? tree->limits.as<double>() : nullptr, link_poses_dev, status_dev,
+                                      g_kinematics_workgroups.load(), stream);
+}
+
+struct JointGradientArguments
+{
+  const vgt_hip_kinematics* tree;
+  const double* link_poses;
+  int64_t num_configurations;
+  const double* sphere_xyzr;
+  const int32_t* sphere_link;
+  int64_t num_spheres;
+  const int32_t* min_sphere;
+  const double* min_gradient;
+  const double* sphere_weight;
+  const double* sphere_gradient;
+  double* joint_gradient;
+
+  bool Worst() const { return min_sphere != nullptr; }
+  // *done: nothing is left to do (B == 0 or J == 0).
+  int Check(const vgt_hip_ctx* ctx, bool* done) const
+  {
+    *done = false;
+    if (!ctx || !tree) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    const bool worst = min_sphere && min_gradient, summed = sphere_weight && sphere_gradient;
+    const bool any_worst = min_sphere || min_gradient, any_summed = sphere_weight || sphere_gradient;
+    if (worst == summed || any_worst != worst || any_summed != summed)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "exactly one pair of (min_sphere, min_gradient) and (sphere_weight, sphere_gradient) must be given");
+    if (num_configurations < 0 || num_spheres < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "negative count");
+    if (num_configurations >= kTwoTo31 || num_spheres >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the joint gradient supports fewer than 2^31 configurations and spheres");
+    if (num_configurations == 0)
+    {
+      *done = true;  // (before the tree is looked at)
+      return VGT_HIP_OK;
+    }
+    if (tree->ctx != ctx) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree belongs to another context");
+    if (tree->num_joints == 0)
+    {
+      *done = true;
+      return VGT_HIP_OK;
+    }
+    if (!link_poses || !joint_gradient || (num_spheres > 0 && (!sphere_xyzr || !sphere_link)))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_configurations * tree->num_links >= kTwoTo31 || num_configurations * tree->num_joints >= kTwoTo31 ||
+        num_configurations * num_spheres >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "the joint gradient supports fewer than 2^31 (configuration, link), (configuration, joint) and "
+                  "(configuration, sphere) pairs");
+    return VGT_HIP_OK;
+  }
+  hipError_t Launch(const double* poses_dev, const double* xyzr_dev, const int32_t* link_dev, const int32_t* min_sphere_dev,
+                    const double* min_gradient_dev, const double* weight_dev, const double* gradient_dev,
+                    double* joint_gradient_dev, hipStream_t stream) const
+  {
+    return vgt::LaunchClearanceJointGradient(tree->links.as<vgt::KinematicLink>(), tree->num_links, tree->num_joints,
+                                             poses_dev, num_configurations, xyzr_dev, link_dev, num_spheres,
+                                             min_sphere_dev, min_gradient_dev, weight_dev, gradient_dev,
+                                             joint_gradient_dev, g_kinematics_workgroups.load(), stream);
+  }
+};
+}  // namespace
+
+int vgt_hip_kinematics_create(vgt_hip_ctx* ctx, int64_t num_links, int64_t num_joints, const int32_t* parent,
+                              const int32_t* joint_type, const int32_t* joint_index, const double* axis,
+                              const double* origin, vgt_hip_kinematics** out_tree)
+{
+  if (out_tree) *out_tree = nullptr;
+  if (!ctx || !parent || !joint_type || !joint_index || !axis || !origin || !out_tree)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_links <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a kinematic tree needs at least one link");
+  if (num_links >= kTwoTo31) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a kinematic tree has fewer than 2^31 links");
+  if (num_joints < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "negative number of joints");
+  for (int64_t i = 0; i < num_links; i++)
+  {
+    const std::string name = "link " + std::to_string(i) + ": ";
+    if (parent[i] < -1 || parent[i] >= i)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  name + "parent " + std::to_string(parent[i]) + " is not below " + std::to_string(i));
+    if (joint_type[i] != VGT_HIP_JOINT_FIXED && joint_type[i] != VGT_HIP_JOINT_REVOLUTE &&
+        joint_type[i] != VGT_HIP_JOINT_PRISMATIC)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, name + "joint type " + std::to_string(joint_type[i]) + " is unknown");
+    if (joint_type[i] != VGT_HIP_JOINT_FIXED && (joint_index[i] < 0 || joint_index[i] >= num_joints))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, name + "joint index " + std::to_string(joint_index[i]) +
+                                                    " is not in [0, " + std::to_string(num_joints) + ")");
+  }
+  std::vector<vgt::KinematicLink> links;
+  try
+  {
+    links.resize(static_cast<size_t>(num_links));
+  }
+  catch (const std::bad_alloc&)
+  {
+    return Fail(VGT_HIP_ERR_RUNTIME, "out of host memory");
+  }
+  for (int64_t i = 0; i < num_links; i++)
+  {
+    vgt::KinematicLink& link = links[static_cast<size_t>(i)];
+    link.parent = parent[i];
+    link.joint_type = joint_type[i];
+    link.joint_index = joint_type[i] == VGT_HIP_JOINT_FIXED ? 0 : joint_index[i];
+    link.reserved = 0;
+    for (int k = 0; k < 3; k++) link.axis[k] = axis[3 * i + k];
+    for (int c = 0; c < 4; c++)
+      for (int r = 0; r < 3; r++) link.origin[3 * c + r] = origin[16 * i + 4 * c + r];
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  vgt_hip_kinematics* tree = new (std::nothrow) vgt_hip_kinematics();
+  if (!tree) return Fail(VGT_HIP_ERR_RUNTIME, "out of host memory");
+  tree->ctx = ctx;
+  tree->device = ctx->device;
+  tree->num_links = num_links;
+  tree->num_joints = num_joints;
+  tree->lds_links = vgt::AssignKinematicsLdsSlots(links.data(), num_links);
+  const size_t bytes = links.size() * sizeof(vgt::KinematicLink);
+  hipError_t err = tree->links.Allocate(bytes);
+  if (err == hipSuccess) err = tree->limits.Allocate(static_cast<size_t>(num_joints > 0 ? num_joints : 1) * 2 * sizeof(double));
+  if (err == hipSuccess)
+  {
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    err = hipMemcpyAsync(tree->links.as<void>(), links.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    err = DrainKeepingFirst(ctx->stream, err);  // (`links` goes with this scope)
+  }
+  if (err != hipSuccess)
+  {
+    delete tree;
+    return FailHip("Failed to upload the kinematic tree", err);
+  }
+  AdoptChild(ctx);
+  *out_tree = tree;
+  return VGT_HIP_OK;
+}
+
+void vgt_hip_kinematics_destroy(vgt_hip_kinematics* tree)
+{
+  if (!tree) return;
+  vgt_hip_ctx* const ctx = tree->ctx;
+  const int device = tree->device;
+  // (ReleaseChild waits for the work that may still read the tree; the buffers go after it, the context's record -- the
+  // handle's reference may be its last -- is not touched again)
+  ReleaseChild(ctx, device);
+  delete tree;
+}
+
+int64_t vgt_hip_kinematics_num_links(const vgt_hip_kinematics* tree) { return tree ? tree->num_links : 0; }
+int64_t vgt_hip_kinematics_num_joints(const vgt_hip_kinematics* tree) { return tree ? tree->num_joints : 0; }
+int32_t vgt_hip_kinematics_lds_links(void) { return vgt::kKinematicsLdsLinks; }
+
+int vgt_hip_forward_kinematics_dev(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                                   int64_t num_configurations, const double* world_from_base,
+                                   const double* joint_limits, double* link_poses_dev, uint8_t* status_dev)
+{
+  bool done = false;
+  const int rc = CheckForwardKinematics(ctx, tree, joint_values_dev, num_configurations, link_poses_dev, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(EnqueueForwardKinematics(tree, joint_values_dev, num_configurations, world_from_base, joint_limits,
+                                       link_poses_dev, status_dev, ctx->stream),
+              "forward kinematics");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_forward_kinematics(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* joint_values_host,
+                               int64_t num_configurations, const double* world_from_base, const double* joint_limits,
+                               double* link_poses_host, uint8_t* status_host)
+{
+  bool done = false;
+  const int rc = CheckForwardKinematics(ctx, tree, joint_values_host, num_configurations, link_poses_host, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "forward kinematics";
+  const size_t b = static_cast<size_t>(num_configurations);
+  vgt::HostStaging staging;
+  // (a tree without joints: one double stands in, so that the kernel has an address it never reads)
+  const double none = 0.0;
+  const auto values = tree->num_joints > 0 ? staging.In(joint_values_host, b * static_cast<size_t>(tree->num_joints))
+                                           : staging.In(&none, 1);
+  const auto poses = staging.Out(link_poses_host, b * static_cast<size_t>(tree->num_links) * 16);
+  const auto status = staging.Out(status_host, b);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t s) {
+    return HipResult(what, EnqueueForwardKinematics(tree, values.dev(), num_configurations, world_from_base,
+                                                    joint_limits, poses.dev(), status.dev(), s));
+  });
+}
+
+int vgt_hip_clearance_joint_gradient_dev(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* link_poses_dev,
+                                         int64_t num_configurations, const double* sphere_xyzr_dev,
+                                         const int32_t* sphere_link_dev, int64_t num_spheres,
+                                         const int32_t* min_sphere_dev, const double* min_gradient_dev,
+                                         const double* sphere_weight_dev, const double* sphere_gradient_dev,
+                                         double* joint_gradient_dev)
+{
+  const JointGradientArguments a{tree, link_poses_dev, num_configurations, sphere_xyzr_dev, sphere_link_dev, num_spheres,
+                                 min_sphere_dev, min_gradient_dev, sphere_weight_dev, sphere_gradient_dev,
+                                 joint_gradient_dev};
+  bool done = false;
+  const int rc = a.Check(ctx, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(a.Launch(link_poses_dev, sphere_xyzr_dev, sphere_link_dev, min_sphere_dev, min_gradient_dev,
+                       sphere_weight_dev, sphere_gradient_dev, joint_gradient_dev, ctx->stream),
+              "clearance joint gradient");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_clearance_joint_gradient(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, const double* link_poses_host,
+                                     int64_t num_configurations, const double* sphere_xyzr_host,
+                                     const int32_t* sphere_link_host, int64_t num_spheres, const int32_t* min_sphere_host,
+                                     const double* min_gradient_host, const double* sphere_weight_host,
+                                     const double* sphere_gradient_host, double* joint_gradient_host)
+{
+  const JointGradientArguments a{tree, link_poses_host, num_configurations, sphere_xyzr_host, sphere_link_host,
+                                 num_spheres, min_sphere_host, min_gradient_host, sphere_weight_host,
+                                 sphere_gradient_host, joint_gradient_host};
+  bool done = false;
+  const int rc = a.Check(ctx, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "clearance joint gradient";
+  const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+  vgt::HostStaging staging;
+  const auto poses = staging.In(link_poses_host, b * static_cast<size_t>(tree->num_links) * 16);
+  const auto xyzr = staging.In(sphere_xyzr_host, s * 4);
+  const auto link = staging.In(sphere_link_host, s);
+  const auto min_sphere = staging.In(min_sphere_host, b);
+  const auto min_gradient = staging.In(min_gradient_host, b * 3);
+  const auto weight = staging.In(sphere_weight_host, b * s);
+  const auto gradient = staging.In(sphere_gradient_host, b * s * 3);
+  const auto out = staging.Out(joint_gradient_host, b * static_cast<size_t>(tree->num_joints));
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    return HipResult(what, a.Launch(poses.dev(), xyzr.dev(), link.dev(), min_sphere.dev(), min_gradient.dev(),
+                                    weight.dev(), gradient.dev(), out.dev(), stream));
+  });
+}
+
+int vgt_hip_check_spheres_from_joints(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz,
+                                      double resolution, const double* grid_from_world, const double* rotation,
+                                      const double* sphere_xyzr_host, const int32_t* sphere_link_host,
+                                      int64_t num_spheres, const vgt_hip_kinematics* tree,
+                                      const double* joint_values_host, int64_t num_configurations,
+                                      const double* world_from_base, const double* joint_limits,
+                                      double minimum_clearance, uint32_t flags, uint8_t* status_host,
+                                      double* min_clearance_host, int32_t* min_sphere_host, int32_t* num_below_host,
+                                      int32_t* num_outside_host, double* min_gradient_host,
+                                      double* sphere_clearance_host, double* sphere_gradient_host,
+                                      uint8_t* fk_status_host, double* joint_gradient_host)
+{
+  if (!ctx || !tree || !status_host) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_configurations < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "negative number of configurations");
+  if (num_configurations >= kTwoTo31)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "forward kinematics supports fewer than 2^31 configurations");
+  if (num_configurations == 0) return VGT_HIP_OK;  // (before the tree is looked at)
+  bool done = false;
+  // (the poses stay on the device: the tree itself stands in where the checks ask for a pointer that is not null)
+  const double* const stand_in = reinterpret_cast<const double*>(tree);
+  int rc = CheckForwardKinematics(ctx, tree, joint_values_host, num_configurations, stand_in, &done);
+  if (rc != VGT_HIP_OK) return rc;
+  const CheckSpheresArguments a{sdf_host, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_host,
+                                sphere_link_host, num_spheres, stand_in, tree->num_links, num_configurations,
+                                minimum_clearance, flags,
+                                {status_host, min_clearance_host, min_sphere_host, num_below_host, num_outside_host,
+                                 min_gradient_host, sphere_clearance_host, sphere_gradient_host}};
+  rc = a.Check(ctx);
+  if (rc == VGT_HIP_OK) rc = a.CheckModel();
+  if (rc != VGT_HIP_OK) return rc;
+  const bool with_gradient = joint_gradient_host && tree->num_joints > 0;
+  if (with_gradient && num_configurations * tree->num_joints >= kTwoTo31)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the joint gradient supports fewer than 2^31 (configuration, joint) pairs");
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "check spheres from joints";
+  const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+  const size_t joints = static_cast<size_t>(tree->num_joints);
+  const double none = 0.0;
+  // (ten outputs and seven inputs, and a staging holds eight arrays: three of them, the later ones inside the first one's body)
+  vgt::HostStaging inputs;
+  const auto sdf = inputs.In(sdf_host, static_cast<size_t>(a.NumCells()));
+  const auto xyzr = inputs.In(sphere_xyzr_host, s * 4);
+  const auto link = inputs.In(sphere_link_host, s);
+  const auto values = joints > 0 ? inputs.In(joint_values_host, b * joints) : inputs.In(&none, 1);
+  const auto poses = inputs.Scratch<double>(b * static_cast<size_t>(tree->num_links) * 16 * sizeof(double));
+  // what the gradient reads, when the caller does not want it back
+  vgt::HostStaging::Handle<int32_t> own_min_sphere;
+  vgt::HostStaging::Handle<double> own_min_gradient;
+  if (with_gradient && !min_sphere_host) own_min_sphere = inputs.Scratch<int32_t>(b * sizeof(int32_t));
+  if (with_gradient && !min_gradient_host) own_min_gradient = inputs.Scratch<double>(b * 3 * sizeof(double));
+  return inputs.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    vgt::HostStaging checks;
+    const auto status = checks.Out(status_host, b);
+    const auto min_clearance = checks.Out(min_clearance_host, b);
+    const auto min_sphere = checks.Out(min_sphere_host, b);
+    const auto num_below = checks.Out(num_below_host, b);
+    const auto num_outside = checks.Out(num_outside_host, b);
+    const auto min_gradient = checks.Out(min_gradient_host, b * 3);
+    const auto sphere_clearance = checks.Out(sphere_clearance_host, b * s);
+    const auto sphere_gradient = checks.Out(sphere_gradient_host, b * s * 3);
+    return checks.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+      vgt::HostStaging kinematics;
+      const auto fk_status = kinematics.Out(fk_status_host, b);
+      const auto joint_gradient = kinematics.Out(with_gradient ? joint_gradient_host : nullptr, b * joints);
+      return kinematics.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+        hipError_t err = EnqueueForwardKinematics(tree, values.dev(), num_configurations, world_from_base, joint_limits,
+                                                  poses.dev(), fk_status.dev(), stream);
+        int32_t* const worst = min_sphere_host ? min_sphere.dev() : own_min_sphere.dev();
+        double* const worst_gradient = min_gradient_host ? min_gradient.dev() : own_min_gradient.dev();
+        const vgt::BodyOutputs out{status.dev(),      min_clearance.dev(), worst,                  num_below.dev(),
+                                   num_outside.dev(), worst_gradient,      sphere_clearance.dev(), sphere_gradient.dev()};
+        if (err == hipSuccess) err = a.Launch(sdf.dev(), xyzr.dev(), link.dev(), poses.dev(), out, stream);
+        if (err == hipSuccess && with_gradient)
+          err = vgt::LaunchClearanceJointGradient(tree->links.as<vgt::KinematicLink>(), tree->num_links,
+                                                  tree->num_joints, poses.dev(), num_configurations, xyzr.dev(),
+                                                  link.dev(), num_spheres, worst, worst_gradient, nullptr, nullptr,
+                                                  joint_gradient.dev(), g_kinematics_workgroups.load(), stream);
+        return HipResult(what, err);
+      });
+    });
+  });
 }
 
 }  // extern "C"

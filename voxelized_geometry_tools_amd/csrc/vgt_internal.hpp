@@ -549,6 +549,42 @@ hipError_t LaunchAlignPoints(const float* sdf_dev, int64_t nx, int64_t ny, int64
                              int64_t num_poses, const AlignOptions& options, const AlignOutputs& out,
                              void* workspace_dev, int max_workgroups, hipStream_t stream);
 
+// --- launchers (kinematics_kernels.hip): forward kinematics and the clearance gradient in joint space ---
+// The definition of every output: include/vgt_hip.h, vgt_hip_forward_kinematics / vgt_hip_clearance_joint_gradient.
+// One record per link, as the kernels read it (the host validates and packs the caller's arrays into these).
+struct KinematicLink
+{
+  int32_t parent, joint_type, joint_index;
+  int32_t keep_slot;    // the LDS slot the forward kinematics keeps this link's pose in, -1: none
+  int32_t parent_slot;  // the parent's slot when the parent is not the link just before, -1: none
+  int32_t reserved;
+  double axis[3];
+  double origin[12];  // the twelve used elements, column by column: origin[3 c + r]
+};
+constexpr int kJointFixed = 0, kJointRevolute = 1, kJointPrismatic = 2;
+// The LDS budget of the forward kinematics: the poses of at most this many links, 96 B per lane and link, 6 KiB per
+// link for a workgroup of one wave: 60 KiB.
+constexpr int kKinematicsLdsLinks = 10;
+// Fills keep_slot and parent_slot: a slot for every link that is the parent of a link other than the next one (a parent
+// that is the link just before its child stays in registers), in link order, for the first kKinematicsLdsLinks of them.
+// Returns the number of slots: 0 for a chain.
+int AssignKinematicsLdsSlots(KinematicLink* links_host, int64_t num_links);
+// Fewer than 2^31 links, configurations and (configuration, link) pairs.  world_from_base_host: 16 doubles or nullptr;
+// limits_dev: [J][2] or nullptr; status_dev may be nullptr; lds_links: what AssignKinematicsLdsSlots returned.  max_workgroups: 0 = the launcher's own limit
+// (vgt_hip_testing_set_kinematics_workgroups).
+hipError_t LaunchForwardKinematics(const KinematicLink* links_dev, int64_t num_links, int64_t num_joints, int lds_links,
+                                   const double* joint_values_dev, int64_t num_configurations,
+                                   const double* world_from_base_host, const double* limits_dev, double* link_poses_dev,
+                                   uint8_t* status_dev, int max_workgroups, hipStream_t stream);
+// Exactly one of (min_sphere_dev, min_gradient_dev) and (sphere_weight_dev, sphere_gradient_dev) is given.
+hipError_t LaunchClearanceJointGradient(const KinematicLink* links_dev, int64_t num_links, int64_t num_joints,
+                                        const double* link_poses_dev, int64_t num_configurations,
+                                        const double* sphere_xyzr_dev, const int32_t* sphere_link_dev,
+                                        int64_t num_spheres, const int32_t* min_sphere_dev,
+                                        const double* min_gradient_dev, const double* sphere_weight_dev,
+                                        const double* sphere_gradient_dev, double* joint_gradient_dev,
+                                        int max_workgroups, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
