@@ -279,6 +279,9 @@ int vgt_hip_testing_set_align_workgroups(int workgroups);
  * vgt_hip_clearance_joint_gradient[_dev], so that a few hundred configurations already make their persistent waves
  * stride. */
 int vgt_hip_testing_set_kinematics_workgroups(int workgroups);
+/* The same for the launches of vgt_hip_check_motions[_dev] (one workgroup per motion), so that a few motions already make
+ * its persistent waves stride. */
+int vgt_hip_testing_set_motion_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
  * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
  * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
@@ -880,6 +883,76 @@ int vgt_hip_check_spheres_from_joints(vgt_hip_ctx* ctx, const float* sdf_host, i
                                       int32_t* num_outside_host, double* min_gradient_host,
                                       double* sphere_clearance_host, double* sphere_gradient_host,
                                       uint8_t* fk_status_host, double* joint_gradient_host);
+
+/* ---- Motions between joint configurations checked against an SDF ----
+ * The question a sampling planner asks of an edge: is the straight joint-space motion from q_a to q_b free, where does it
+ * first collide, how close does it come.  A batch of E motions in, one verdict per motion out; the link poses of the
+ * samples are made and used on the device and are never written to memory (csrc/motion_kernels.hip).  Read-only.
+ *
+ * THE DEFINITION.  Motion e has the endpoints a = joint_from[e] and b = joint_to[e] (J doubles each, J the tree's) and a
+ * step count n = num_steps[e], or uniform_steps when num_steps is NULL.  It has n + 1 samples k = 0 ... n, in double,
+ * every operator rounded on its own:
+ *   k == 0       q = a, the bits as given.  With n == 0 this is the only sample and b is not read.
+ *   k == n > 0   q = b, the bits as given (not a + 1*(b - a)).
+ *   otherwise    t = (double)k / (double)n;  q_j = a_j + t * (b_j - a_j).
+ * Interpolation is plain linear: there is no wrap-around for continuous revolute joints.
+ * Per sample: vgt_hip_check_spheres_from_joints with joint_values = q and the same field, grid_from_world, rotation,
+ * model, tree, world_from_base, joint_limits, minimum_clearance and VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION bit would return
+ * status, min_clearance, min_sphere, num_below, num_outside, min_gradient and fk_status; every bit of those seven values
+ * is what that call gives.  Nothing of the kinematics or of the check is restated here.
+ * Considered samples: all of them; with flags & VGT_HIP_MOTION_STOP_AT_COLLISION only the samples 0 ... first_collision
+ * when there is a collision: the later samples then do not exist for any output.
+ * Outputs, one entry per motion; status is required, every other output may be NULL:
+ *   status (uint8)           VGT_HIP_MOTION_COLLISION 1 when a considered sample's status is COLLISION; otherwise
+ *                            VGT_HIP_MOTION_NO_VALUE 2 when one is NO_VALUE (a motion is not clear when a sample could
+ *                            not be judged); otherwise VGT_HIP_MOTION_CLEAR 0.  VGT_HIP_MOTION_INVALID 3: the device
+ *                            form only, below.
+ *   first_collision (int32)  the least k whose sample status is COLLISION, or -1
+ *   min_clearance (double), min_sample (int32), min_sphere (int32)
+ *                            the least non-NaN sample min_clearance among the considered samples; ties under == go to
+ *                            the lowest k (so -0.0 and 0.0 tie); the value written is that sample's own bits, and
+ *                            min_sphere is that sample's.  NaN, -1, -1 when there is no such sample.
+ *   min_gradient [3] (double)  the min_gradient of sample min_sample; NaN x 3 when min_sample == -1
+ *   fk_status (uint8)        the OR of the considered samples' fk_status
+ * Both reductions are total orders on distinct k: the answer does not depend on the launch geometry.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer (ctx, sdf, tree, status; the model's two
+ * arrays when S > 0; the two joint arrays when E > 0 and J > 0); a resolution that is not positive and finite; a NaN
+ * minimum_clearance; an unknown flag bit; negative extents or counts; a negative uniform_steps when num_steps is NULL; a
+ * grid of 2^31 cells or more; E, E * J or S of 2^31 or more; a tree of another context; a tree of more links than the
+ * kernel takes (vgt_hip_motion_tile_samples gives 0; the message gives both numbers).  The host form also looks at its
+ * arrays and names the first offender -- "motion 12: num_steps -3", "sphere 17: ..." --: a num_steps[e] < 0, a
+ * sphere_link outside [0, L), a negative or NaN radius.  The device form cannot look: a motion with n < 0 gets status
+ * INVALID, first_collision -1, min_clearance NaN, min_sample -1, min_sphere -1, min_gradient NaN x 3 and fk_status 0, and
+ * forms no address; a link outside [0, L) makes its sphere "without a value", as in vgt_hip_check_spheres_dev.
+ * E == 0 succeeds without a device.  The host form stages its arrays and blocks; the device form (field, model, joint
+ * arrays, num_steps and outputs on the device; the three transforms / limits are host arrays) is enqueued on the context's
+ * stream, not blocking.  Calls that use one tree are serialised by the context. */
+#define VGT_HIP_MOTION_STOP_AT_COLLISION 2u
+#define VGT_HIP_MOTION_CLEAR 0
+#define VGT_HIP_MOTION_COLLISION 1
+#define VGT_HIP_MOTION_NO_VALUE 2
+#define VGT_HIP_MOTION_INVALID 3
+int vgt_hip_check_motions(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                          const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+                          const int32_t* sphere_link_host, int64_t num_spheres, const vgt_hip_kinematics* tree,
+                          const double* joint_from_host, const double* joint_to_host, const int32_t* num_steps_host,
+                          int32_t uniform_steps, int64_t num_motions, const double* world_from_base,
+                          const double* joint_limits, double minimum_clearance, uint32_t flags, uint8_t* status_host,
+                          int32_t* first_collision_host, double* min_clearance_host, int32_t* min_sample_host,
+                          int32_t* min_sphere_host, double* min_gradient_host, uint8_t* fk_status_host);
+int vgt_hip_check_motions_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                              double resolution, const double* grid_from_world, const double* rotation,
+                              const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                              const vgt_hip_kinematics* tree, const double* joint_from_dev, const double* joint_to_dev,
+                              const int32_t* num_steps_dev, int32_t uniform_steps, int64_t num_motions,
+                              const double* world_from_base, const double* joint_limits, double minimum_clearance,
+                              uint32_t flags, uint8_t* status_dev, int32_t* first_collision_dev,
+                              double* min_clearance_dev, int32_t* min_sample_dev, int32_t* min_sphere_dev,
+                              double* min_gradient_dev, uint8_t* fk_status_dev);
+/* The samples per tile the kernel uses for a tree of so many links: a power of two, at most 64, with 96 * L * T <= 60 KiB
+ * of LDS for the poses of a tile (the build keeps them within 12 KiB where more than one sample fits that: DESIGN.md 4n);
+ * 0: more links than the kernel takes (640), or none.  Exposed so that tests put step counts on both sides of it. */
+int32_t vgt_hip_motion_tile_samples(int64_t num_links);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

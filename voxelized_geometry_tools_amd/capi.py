@@ -108,6 +108,11 @@ SIGNATURES = {
     "vgt_hip_clearance_joint_gradient_dev": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "vgt_hip_check_spheres_from_joints": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p,
                                                  _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_motions": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64, _p,
+                                     _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_motions_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64,
+                                         _p, _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_motion_tile_samples": (_i32, [_i64]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -192,6 +197,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_sphere_volume_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_align_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_kinematics_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_motion_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
@@ -230,6 +236,12 @@ SPHERES_KEEP = 1
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1, 2
 FK_NOT_COMPUTABLE = 1
 FK_OUTSIDE_LIMITS = 2
+# flag and statuses of check_motions (VGT_HIP_MOTION_*)
+MOTION_STOP_AT_COLLISION = 2
+MOTION_CLEAR = 0
+MOTION_COLLISION = 1
+MOTION_NO_VALUE = 2
+MOTION_INVALID = 3
 ALIGN_CONVERGED = 0
 ALIGN_ITERATION_LIMIT = 1
 ALIGN_DEGENERATE = 2
@@ -290,6 +302,11 @@ def _cloud_poses(poses):
 # what Context.check_spheres_from_joints returns: SphereChecks' fields, then fk_status [B] uint8 (FK_* bits) and
 # joint_gradient [B, J] (None unless asked for)
 JointSphereChecks = collections.namedtuple("JointSphereChecks", SphereChecks._fields + ("fk_status", "joint_gradient"))
+
+
+# what Context.check_motions returns: one entry per motion; min_gradient [E, 3]
+MotionChecks = collections.namedtuple(
+    "MotionChecks", "status first_collision min_clearance min_sample min_sphere min_gradient fk_status")
 
 
 def _joint_values(tree, joint_values):
@@ -758,6 +775,64 @@ class Context:
             _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
             SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0, *[_ptr(a) for a in out]))
         return out
+
+    def check_motions(self, sdf, resolution, spheres_xyzr, sphere_link, tree, joint_from, joint_to, num_steps,
+                      minimum_clearance=0.0, outside_is_collision=False, stop_at_collision=False, grid_from_world=None,
+                      rotation=None, world_from_base=None, joint_limits=None):
+        """vgt_hip_check_motions: E straight joint-space motions joint_from [E, J] -> joint_to [E, J] of num_steps steps
+        each (an int for all of them, or an int32 array [E]; a motion has num_steps + 1 samples), every sample checked
+        as check_spheres_from_joints checks a configuration; the poses never leave the device.  Returns
+        MotionChecks(status uint8 (MOTION_*), first_collision int32, min_clearance float64, min_sample int32,
+        min_sphere int32, min_gradient [E, 3] float64, fk_status uint8 (FK_* bits))."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be an (nx, ny, nz) grid")
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        a, b = _joint_values(tree, joint_from), _joint_values(tree, joint_to)
+        if a.shape != b.shape:
+            raise ValueError("joint_from and joint_to must have the same shape")
+        e, s = a.shape[0], len(xyzr)
+        if np.ndim(num_steps) == 0:
+            steps, uniform = None, int(num_steps)
+        else:
+            steps, uniform = np.ascontiguousarray(num_steps, dtype=np.int32).reshape(-1), 0
+            if len(steps) != e:
+                raise ValueError("num_steps must hold one count per motion")
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        out = MotionChecks(np.empty(e, np.uint8), np.empty(e, np.int32), np.empty(e, np.float64), np.empty(e, np.int32),
+                           np.empty(e, np.int32), np.empty((e, 3), np.float64), np.empty(e, np.uint8))
+        flags = (SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0) | \
+            (MOTION_STOP_AT_COLLISION if stop_at_collision else 0)
+        check(self._lib.vgt_hip_check_motions(
+            self.handle, _ptr(f), *f.shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(xyzr), _ptr(link), s,
+            tree._handle_or_raise(), _ptr(a), _ptr(b), _ptr(steps), uniform, e, _ptr(_base_transform(world_from_base)),
+            _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance), flags, *[_ptr(o) for o in out]))
+        return out
+
+    def check_motions_dev(self, sdf_ptr, shape, resolution, spheres_xyzr_ptr, sphere_link_ptr, num_spheres, tree,
+                          joint_from_ptr, joint_to_ptr, num_steps, num_motions, status_ptr, first_collision_ptr=None,
+                          min_clearance_ptr=None, min_sample_ptr=None, min_sphere_ptr=None, min_gradient_ptr=None,
+                          fk_status_ptr=None, minimum_clearance=0.0, outside_is_collision=False,
+                          stop_at_collision=False, grid_from_world=None, rotation=None, world_from_base=None,
+                          joint_limits=None, num_steps_ptr=None):
+        """vgt_hip_check_motions_dev: field, model, joint arrays and outputs on the device (the transforms and the limits
+        are host arrays); num_steps: the step count of every motion, unless num_steps_ptr gives an int32 array [E] on
+        the device; enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        flags = (SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0) | \
+            (MOTION_STOP_AT_COLLISION if stop_at_collision else 0)
+        check(self._lib.vgt_hip_check_motions_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
+            _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr), int(num_spheres), tree._handle_or_raise(),
+            _ptr(joint_from_ptr), _ptr(joint_to_ptr), _ptr(num_steps_ptr), int(num_steps or 0), int(num_motions),
+            _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
+            flags, _ptr(status_ptr), _ptr(first_collision_ptr), _ptr(min_clearance_ptr), _ptr(min_sample_ptr),
+            _ptr(min_sphere_ptr), _ptr(min_gradient_ptr), _ptr(fk_status_ptr)))
 
     def rasterize_spheres(self, shape, resolution, spheres_xyzr, sphere_link, link_poses, padding=0.0, base=0, into=None,
                           grid_from_world=None):
@@ -1254,6 +1329,11 @@ class Context:
         and clearance_joint_gradient (0 = back to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_kinematics_workgroups(int(workgroups)))
 
+    def set_motion_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per launch of check_motions
+        (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_motion_workgroups(int(workgroups)))
+
     def set_sphere_volume_counters(self, counters_ptr):
         """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
         adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
@@ -1472,6 +1552,11 @@ def sdf_workspace_bytes(shape, variant=0):
 def kinematics_lds_links():
     """vgt_hip_kinematics_lds_links: how many links' poses the forward kinematics keeps in LDS (a constant of the kernel)."""
     return int(load().vgt_hip_kinematics_lds_links())
+
+
+def motion_tile_samples(num_links):
+    """vgt_hip_motion_tile_samples: the samples per tile check_motions uses for a tree of so many links; 0: too many."""
+    return int(load().vgt_hip_motion_tile_samples(int(num_links)))
 
 
 class KinematicTree:

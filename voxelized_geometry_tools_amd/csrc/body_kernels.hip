@@ -26,10 +26,7 @@
 // device form only) makes its sphere "without a value" before any pose address is formed; the field is read only through
 // LocateCell's in-grid indices (never for an empty grid, where LocateCell has no cell).
 // (EstimateDistance itself is not called here: the kernel needs the cell between its steps)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
-#include "sdf_sampling.hpp"
-#pragma clang diagnostic pop
+#include "body_check.hpp"
 #include "vgt_internal.hpp"
 
 #include <cmath>
@@ -44,7 +41,6 @@ namespace
 {
 constexpr int kBodyThreads = 256;
 constexpr int kBodyWaves = kBodyThreads / 64;
-constexpr uint8_t kBodyClear = 0, kBodyCollision = 1, kBodyNoValue = 2;
 // LDS per workgroup: the sphere table, 256 * 36 B = 9 KiB.  (With VGT_BODY_STAGE_POSES=1 also 4 waves * 4 KiB of
 // poses, 42 link poses per wave: 25 KiB in all.)
 constexpr int kSphereTableMax = 256;
@@ -66,12 +62,6 @@ struct BodyQuery
   double minimum_clearance;
   int outside_is_collision;
 };
-
-// (clearance, index) of a better than of b: smaller clearance, then smaller index; index < 0 = no candidate
-__device__ __forceinline__ bool BetterSphere(double ca, int ia, double cb, int ib)
-{
-  return ia >= 0 && (ib < 0 || ca < cb || (ca == cb && ia < ib));
-}
 
 template <bool kStagePoses>
 __global__ __launch_bounds__(kBodyThreads) void CheckSpheresKernel(const float* __restrict__ sdf, int nx, int ny, int nz,
@@ -160,21 +150,10 @@ __global__ __launch_bounds__(kBodyThreads) void CheckSpheresKernel(const float* 
         {
           double w[3];
           if (kStagePoses && poses_in_lds)
-          {
-            const double* m = my_poses + (segment * L + link) * 12;
-            for (int r = 0; r < 3; r++) w[r] = ((m[r] * x + m[3 + r] * y) + m[6 + r] * z) + m[9 + r];
-          }
+            SphereCentre(my_poses + (segment * L + link) * 12, 3, 1, x, y, z, w);
           else
-          {
-            const double* m = model.poses + (b * L + link) * 16;
-            for (int r = 0; r < 3; r++) w[r] = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r];
-          }
-          if (LocateCell(nx, ny, nz, resolution, xf, w[0], w[1], w[2], c))
-          {
-            const double d = InterpolateCorners(c, LoadCorners(sdf, ny, nz, resolution, c), resolution);
-            has_value = true;
-            clearance = d - radius;
-          }
+            SphereCentre(model.poses + (b * L + link) * 16, 4, 1, x, y, z, w);
+          has_value = SphereClearance(sdf, nx, ny, nz, resolution, xf, w, radius, c, clearance);
         }
       }
       if (out.sphere_clearance && active) out.sphere_clearance[b * S + s] = clearance;
@@ -202,25 +181,12 @@ __global__ __launch_bounds__(kBodyThreads) void CheckSpheresKernel(const float* 
 
     double winner = best;
     int winner_sphere = best_sphere;
-    for (int offset = width >> 1; offset > 0; offset >>= 1)
-    {
-      const double other = __shfl_xor(winner, offset);
-      const int other_sphere = __shfl_xor(winner_sphere, offset);
-      if (BetterSphere(other, other_sphere, winner, winner_sphere))
-      {
-        winner = other;
-        winner_sphere = other_sphere;
-      }
-    }
+    BestSphereOfSegment(width, winner, winner_sphere);
 
     const bool writer = live && (winner_sphere >= 0 ? best_sphere == winner_sphere : in_segment == 0);
     if (writer)
     {
-      uint8_t status = kBodyNoValue;
-      if (num_below > 0 || (query.outside_is_collision && num_outside > 0))
-        status = kBodyCollision;
-      else if (winner_sphere >= 0)
-        status = kBodyClear;
+      const uint8_t status = SphereModelStatus(num_below, num_outside, query.outside_is_collision, winner_sphere);
       out.status[b] = status;
       if (out.min_clearance) out.min_clearance[b] = winner_sphere >= 0 ? winner : nan;
       if (out.min_sphere) out.min_sphere[b] = winner_sphere;

@@ -30,6 +30,7 @@
 // In bounds by construction: a lane with b >= B forms no address; parent, joint_type and joint_index were validated on
 // the host when the tree was made (parent in [-1, i), joint_index in [0, J) on links that are not fixed); a sphere index
 // or a sphere's link from device memory is compared against [0, S) resp. [0, L) before any address is formed from it.
+#include "kinematics_math.hpp"
 #include "vgt_internal.hpp"
 
 #include <cmath>
@@ -44,60 +45,12 @@ constexpr int kGradientThreads = 256;
 constexpr int kKinematicsMaxWorkgroups = 8192;
 constexpr int kGradientMaxWorkgroups = 2048;
 
-struct KinematicsBase
-{
-  double m[12];  // m[3 c + r]
-  int given;
-};
-
-// sin / cos of include/vgt_hip.h for a finite q with |q| <= 2^20
-__device__ __forceinline__ void SinCos(double q, double& s, double& c)
-{
-  const double k = __builtin_rint(q * 0x1.45f306dc9c883p-1);
-  const double r = ((q - k * 0x1.921fb54400000p+0) - k * 0x1.0b4611a600000p-34) - k * 0x1.3198a2e037073p-69;
-  const double z = r * r;
-  double ps = 0x1.952c77030ad4ap-49;    // 1 / 17!
-  ps = ps * z + -0x1.ae7f3e733b81fp-41;  // -1 / 15!
-  ps = ps * z + 0x1.6124613a86d09p-33;   // 1 / 13!
-  ps = ps * z + -0x1.ae64567f544e4p-26;  // -1 / 11!
-  ps = ps * z + 0x1.71de3a556c734p-19;   // 1 / 9!
-  ps = ps * z + -0x1.a01a01a01a01ap-13;  // -1 / 7!
-  ps = ps * z + 0x1.1111111111111p-7;    // 1 / 5!
-  ps = ps * z + -0x1.5555555555555p-3;   // -1 / 3!
-  const double sin_r = r + (r * z) * ps;
-  double pc = 0x1.ae7f3e733b81fp-45;     // 1 / 16!
-  pc = pc * z + -0x1.93974a8c07c9dp-37;  // -1 / 14!
-  pc = pc * z + 0x1.1eed8eff8d898p-29;   // 1 / 12!
-  pc = pc * z + -0x1.27e4fb7789f5cp-22;  // -1 / 10!
-  pc = pc * z + 0x1.a01a01a01a01ap-16;   // 1 / 8!
-  pc = pc * z + -0x1.6c16c16c16c17p-10;  // -1 / 6!
-  pc = pc * z + 0x1.5555555555555p-5;    // 1 / 4!
-  pc = pc * z + -0x1.0000000000000p-1;   // -1 / 2!
-  const double cos_r = 1.0 + z * pc;
-  const int quadrant = static_cast<int>(static_cast<long long>(k) & 3);
-  s = quadrant == 0 ? sin_r : quadrant == 1 ? cos_r : quadrant == 2 ? -sin_r : -cos_r;
-  c = quadrant == 0 ? cos_r : quadrant == 1 ? -sin_r : quadrant == 2 ? -cos_r : sin_r;
-}
-
-// out = a . b, transforms as twelve doubles m[3 c + r]
-__device__ __forceinline__ void Compose(const double* a, const double* b, double* out)
-{
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-  {
-#pragma unroll
-    for (int c = 0; c < 3; c++) out[3 * c + r] = (a[r] * b[3 * c] + a[3 + r] * b[3 * c + 1]) + a[6 + r] * b[3 * c + 2];
-    out[9 + r] = ((a[r] * b[9] + a[3 + r] * b[10]) + a[6 + r] * b[11]) + a[9 + r];
-  }
-}
-
 __global__ __launch_bounds__(kKinematicsThreads) void ForwardKinematicsKernel(
     const KinematicLink* __restrict__ links, int num_links, int num_joints,
     const double* __restrict__ joint_values, int64_t num_configurations, const KinematicsBase base,
     const double* __restrict__ limits, double* poses, uint8_t* __restrict__ status, int wide_stores)
 {
   extern __shared__ __attribute__((aligned(16))) double tile[];  // [slots][12][64]
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int lane = static_cast<int>(threadIdx.x);
   const int64_t groups = (num_configurations + kKinematicsThreads - 1) / kKinematicsThreads;
   for (int64_t group = blockIdx.x; group < groups; group += gridDim.x)
@@ -105,109 +58,33 @@ __global__ __launch_bounds__(kKinematicsThreads) void ForwardKinematicsKernel(
     const int64_t b = group * kKinematicsThreads + lane;
     if (b >= num_configurations) continue;  // (no barrier anywhere below)
     const double* q = joint_values + b * num_joints;
-    uint8_t bits = 0;
-    if (limits)
-      for (int j = 0; j < num_joints; j++)
-      {
-        const double v = q[j];
-        if (v < limits[2 * j] || v > limits[2 * j + 1]) bits |= 2;
-      }
-    double previous[12];  // the pose of link i - 1
+    const auto joint = [&](int j) { return q[j]; };
+    uint8_t bits = limits ? LimitBits(limits, num_joints, joint) : 0;
+    LinkPose previous;  // the pose of link i - 1
 #pragma unroll
-    for (int e = 0; e < 12; e++) previous[e] = 0.0;
+    for (int e = 0; e < 12; e++) previous.m[e] = 0.0;
     double* line = poses + b * num_links * 16;
     for (int i = 0; i < num_links; i++, line += 16)
     {
       const KinematicLink& link = links[i];
-      const int parent = link.parent;
-      double origin[12], frame[12];
-#pragma unroll
-      for (int e = 0; e < 12; e++) origin[e] = link.origin[e];
-      if (parent < 0 && !base.given)
-      {
-#pragma unroll
-        for (int e = 0; e < 12; e++) frame[e] = origin[e];
-      }
-      else
-      {
-        double from[12];
-        if (parent < 0)
-        {
-#pragma unroll
-          for (int e = 0; e < 12; e++) from[e] = base.m[e];
-        }
-        else if (parent == i - 1)
-        {
-#pragma unroll
-          for (int e = 0; e < 12; e++) from[e] = previous[e];
-        }
-        else if (link.parent_slot >= 0)
+      const LinkPose frame = LinkFrame(link, i, base, previous, [&](int parent) {
+        LinkPose from;
+        if (link.parent_slot >= 0)
         {
           const double* kept = tile + (link.parent_slot * 12) * kKinematicsThreads + lane;
 #pragma unroll
-          for (int e = 0; e < 12; e++) from[e] = kept[e * kKinematicsThreads];
+          for (int e = 0; e < 12; e++) from.m[e] = kept[e * kKinematicsThreads];
         }
         else
         {
           const double* written = poses + (b * num_links + parent) * 16;  // this lane's own earlier line
 #pragma unroll
-          for (int e = 0; e < 12; e++) from[e] = written[4 * (e / 3) + e % 3];
+          for (int e = 0; e < 12; e++) from.m[e] = written[4 * (e / 3) + e % 3];
         }
-        Compose(from, origin, frame);
-      }
-
-      double pose[12];
-#pragma unroll
-      for (int e = 0; e < 12; e++) pose[e] = frame[e];
-      if (link.joint_type != kJointFixed)
-      {
-        const double value = q[link.joint_index];
-        const double x = link.axis[0], y = link.axis[1], z = link.axis[2];
-        const bool finite = fabs(value) <= 0x1.fffffffffffffp+1023;  // (false for NaN)
-        if (link.joint_type == kJointRevolute)
-        {
-          if (finite && fabs(value) <= 0x1p+20)
-          {
-            double s, c;
-            SinCos(value, s, c);
-            const double v = 1.0 - c;
-            double rotation[9];  // rotation[3 c + r]
-            rotation[0] = c + (x * x) * v;
-            rotation[3] = (x * y) * v - z * s;
-            rotation[6] = (x * z) * v + y * s;
-            rotation[1] = (x * y) * v + z * s;
-            rotation[4] = c + (y * y) * v;
-            rotation[7] = (y * z) * v - x * s;
-            rotation[2] = (x * z) * v - y * s;
-            rotation[5] = (y * z) * v + x * s;
-            rotation[8] = c + (z * z) * v;
-#pragma unroll
-            for (int r = 0; r < 3; r++)
-#pragma unroll
-              for (int col = 0; col < 3; col++)
-                pose[3 * col + r] = (frame[r] * rotation[3 * col] + frame[3 + r] * rotation[3 * col + 1]) +
-                                    frame[6 + r] * rotation[3 * col + 2];
-          }
-          else
-          {
-            bits |= 1;
-#pragma unroll
-            for (int e = 0; e < 12; e++) pose[e] = nan;
-          }
-        }
-        else if (finite)
-        {
-          const double t0 = x * value, t1 = y * value, t2 = z * value;
-#pragma unroll
-          for (int r = 0; r < 3; r++) pose[9 + r] = ((frame[r] * t0 + frame[3 + r] * t1) + frame[6 + r] * t2) + frame[9 + r];
-        }
-        else
-        {
-          bits |= 1;
-#pragma unroll
-          for (int e = 0; e < 12; e++) pose[e] = nan;
-        }
-      }
+        return from;
+      });
+      const LinkPose of_link = LinkPoseFromFrame(link, frame, joint, bits);
+      const double* pose = of_link.m;
 
       if (wide_stores)
       {
@@ -237,8 +114,7 @@ __global__ __launch_bounds__(kKinematicsThreads) void ForwardKinematicsKernel(
 #pragma unroll
         for (int e = 0; e < 12; e++) kept[e * kKinematicsThreads] = pose[e];
       }
-#pragma unroll
-      for (int e = 0; e < 12; e++) previous[e] = pose[e];
+      previous = of_link;
     }
     if (status) status[b] = bits;
   }
@@ -362,13 +238,7 @@ hipError_t LaunchForwardKinematics(const KinematicLink* links_dev, int64_t num_l
 {
   if (num_configurations <= 0) return hipSuccess;
   if (lds_links < 0 || lds_links > kKinematicsLdsLinks) return hipErrorInvalidValue;
-  KinematicsBase base{};
-  if (world_from_base_host)
-  {
-    base.given = 1;
-    for (int c = 0; c < 4; c++)
-      for (int r = 0; r < 3; r++) base.m[3 * c + r] = world_from_base_host[4 * c + r];
-  }
+  const KinematicsBase base = MakeKinematicsBase(world_from_base_host);
   const int64_t groups = (num_configurations + kKinematicsThreads - 1) / kKinematicsThreads;
   const int64_t most = max_workgroups > 0 ? max_workgroups : kKinematicsMaxWorkgroups;
   const int64_t workgroups = groups < most ? groups : most;

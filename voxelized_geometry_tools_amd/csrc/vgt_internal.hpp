@@ -585,6 +585,40 @@ hipError_t LaunchClearanceJointGradient(const KinematicLink* links_dev, int64_t 
                                         const double* sphere_gradient_dev, double* joint_gradient_dev,
                                         int max_workgroups, hipStream_t stream);
 
+// --- launcher (motion_kernels.hip): motions between joint configurations checked against an SDF ---
+// The definition of every output: include/vgt_hip.h, vgt_hip_check_motions.  status is required, every other output may
+// be nullptr.
+struct MotionOutputs
+{
+  uint8_t* status;
+  int32_t* first_collision;
+  double* min_clearance;
+  int32_t* min_sample;
+  int32_t* min_sphere;
+  double* min_gradient;
+  uint8_t* fk_status;
+};
+// The samples of a tile for a tree of so many links: a power of two T <= 64 with 96 * L * T <= 60 KiB -- the largest one
+// within the build's VGT_MOTION_MAX_TILE and VGT_MOTION_TILE_BYTES (12 KiB of poses, where more than one sample fits them);
+// 0: more links than the kernel takes (640), or none.
+int MotionTileSamples(int64_t num_links);
+// The dynamic LDS the poses of a tile may take (under the 64 KiB a launch gets without an attribute), what a link takes of
+// it per sample, and so the most links of a tree: 640 (one sample per tile).
+constexpr size_t kMotionPoseBudget = 60 * 1024, kMotionPoseBytesPerLink = 96;
+constexpr int64_t kMotionMaxLinks = static_cast<int64_t>(kMotionPoseBudget / kMotionPoseBytesPerLink);
+// Grids of 0 to 2^31 - 1 cells; fewer than 2^31 spheres, motions and (motion, joint) pairs; a tree MotionTileSamples
+// takes.  Field, model, joint arrays, num_steps (or nullptr: uniform_steps) and outputs on the device; the three
+// transforms are host arrays (or nullptr); limits_dev: [J][2] or nullptr.  max_workgroups: 0 = the launcher's own limit
+// (vgt_hip_testing_set_motion_workgroups).
+hipError_t LaunchCheckMotions(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                              const double* grid_from_world_host, const double* rotation_host,
+                              const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                              const KinematicLink* links_dev, int64_t num_links, int64_t num_joints,
+                              const double* joint_from_dev, const double* joint_to_dev, const int32_t* num_steps_dev,
+                              int32_t uniform_steps, int64_t num_motions, const double* world_from_base_host,
+                              const double* limits_dev, double minimum_clearance, int outside_is_collision,
+                              int stop_at_collision, const MotionOutputs& out, int max_workgroups, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
