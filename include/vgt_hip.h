@@ -282,6 +282,9 @@ int vgt_hip_testing_set_kinematics_workgroups(int workgroups);
 /* The same for the launches of vgt_hip_check_motions[_dev] (one workgroup per motion), so that a few motions already make
  * its persistent waves stride. */
 int vgt_hip_testing_set_motion_workgroups(int workgroups);
+/* The same for the launches of vgt_hip_clearance_cost[_dev] (one workgroup per tile of configurations), so that a few
+ * hundred configurations already make its persistent waves stride. */
+int vgt_hip_testing_set_cost_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
  * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
  * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
@@ -953,6 +956,74 @@ int vgt_hip_check_motions_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx
  * of LDS for the poses of a tile (the build keeps them within 12 KiB where more than one sample fits that: DESIGN.md 4n);
  * 0: more links than the kernel takes (640), or none.  Exposed so that tests put step counts on both sides of it. */
 int32_t vgt_hip_motion_tile_samples(int64_t num_links);
+
+/* ---- The obstacle cost of configurations given as joint values, and its gradient with respect to the joints ----
+ * What an optimiser asks per configuration (CHOMP, STOMP or MPPI roll-outs, collision-aware IK, path smoothing): a cost
+ * that counts EVERY sphere inside a safety margin, not only the worst one, and that cost's gradient in joint space.  B
+ * configurations in, one cost and optionally one gradient row [J] per configuration out; link poses and per-sphere
+ * values are made and used on the device and are never written to memory (csrc/cost_kernels.hip).  A trajectory is
+ * nothing special: [N][W][J] is B = N * W configurations.  Read-only.
+ *
+ * Inputs: as vgt_hip_check_spheres_from_joints -- the field and its extents, resolution, grid_from_world, rotation, the
+ * model, the tree, joint_values [B][J], world_from_base, joint_limits --, then margin and flags (no bit is defined yet).
+ *
+ * THE DEFINITION.  Per (configuration b, sphere s): clearance d and gradient g are exactly what vgt_hip_check_spheres
+ * defines for the poses that vgt_hip_forward_kinematics defines for row b; nothing of either is restated here.  A sphere
+ * "without a value" is one whose d is NaN: a sphere not in the grid, a non-finite centre, a NaN pose from a link that is
+ * not computable, an estimate that is itself NaN (a NaN in the field, infinity minus infinity) and, in the device form, a
+ * link outside [0, L).
+ * The hinge, in double, every operator rounded on its own, with eps = margin; the comparisons in this order:
+ *   d is NaN       no contribution, w = 0
+ *   d < 0          c = (eps * 0.5) - d                        w = -1.0
+ *   d <= eps       t = d - eps;  c = ((t * t) * 0.5) / eps    w = t / eps
+ *   otherwise      c = +0.0                                   w = 0
+ * +-infinity compare as they are.  c is the CHOMP obstacle potential and w = dc/dd; both are continuous at 0 and at eps,
+ * but the bits of the two branches at d == 0 need not agree, which is why the order of the comparisons is part of the
+ * definition (-0.0 < 0 is false: it takes the second branch).
+ * Outputs per configuration; cost is required, every other output may be NULL:
+ *   cost (double)                 acc = +0.0; acc = acc + c_s for s ascending, over the spheres with a value
+ *   joint_gradient [J] (double)   the summed form of vgt_hip_clearance_joint_gradient, to the bit, with
+ *                                 sphere_weight[b][s] = w_s and sphere_gradient = g: the walk, the term and the order are
+ *                                 exactly as the summed form defines them (s ascending, walk order within a sphere, a
+ *                                 sphere skipped when its weight is 0).  One addition: a sphere with w != 0 whose g has a
+ *                                 NaN component is given weight 0 for the gradient; it still counts in cost.
+ *   num_active (int32)            spheres with a value and w != 0
+ *   num_outside (int32)           spheres without a value
+ *   num_without_gradient (int32)  spheres that are active but were skipped in the gradient by the rule above
+ *   fk_status (uint8)             the forward kinematics' status
+ * The order is fixed: no output depends on the launch geometry.  With joint_gradient and num_without_gradient both NULL
+ * (roll-out scoring) no gradient is loaded at all.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer (ctx, sdf, tree, cost; the model's two
+ * arrays when S > 0; joint_values when B > 0 and J > 0); a resolution that is not positive and finite; a margin that is
+ * not positive and finite; an unknown flag bit (any bit); negative extents or counts; a grid of 2^31 cells or more; B, S,
+ * B * J, B * S or B * L of 2^31 or more; a tree of another context; a tree of more links than the kernel takes
+ * (vgt_hip_cost_tile_samples gives 0; the message gives both numbers).  The host form also looks at the model and names
+ * the first offending sphere -- "sphere 17: ..." --: a sphere_link outside [0, L), a negative or NaN radius.  The device
+ * form cannot look: such a link makes its sphere "without a value" and forms no address; a bad radius is used as it is.
+ * B == 0 succeeds without a device.  S == 0 gives cost +0.0, a gradient row of +0.0 and counts 0.  The host form stages
+ * its arrays and blocks; the device form (field, model, joint values and outputs on the device; the three transforms /
+ * limits are host arrays) is enqueued on the context's stream, not blocking.  Calls that use one tree are serialised by
+ * the context. */
+int vgt_hip_clearance_cost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                           const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+                           const int32_t* sphere_link_host, int64_t num_spheres, const vgt_hip_kinematics* tree,
+                           const double* joint_values_host, int64_t num_configurations, const double* world_from_base,
+                           const double* joint_limits, double margin, uint32_t flags, double* cost_host,
+                           double* joint_gradient_host, int32_t* num_active_host, int32_t* num_outside_host,
+                           int32_t* num_without_gradient_host, uint8_t* fk_status_host);
+int vgt_hip_clearance_cost_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                               double resolution, const double* grid_from_world, const double* rotation,
+                               const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                               const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                               int64_t num_configurations, const double* world_from_base, const double* joint_limits,
+                               double margin, uint32_t flags, double* cost_dev, double* joint_gradient_dev,
+                               int32_t* num_active_dev, int32_t* num_outside_dev, int32_t* num_without_gradient_dev,
+                               uint8_t* fk_status_dev);
+/* The configurations per tile the kernel uses for a tree of so many links: a power of two, at most 64, with
+ * 96 * L * T <= 48 KiB of LDS for the poses of a tile (the build keeps them within 6 KiB where more than one
+ * configuration fits that: DESIGN.md 4o); 0: more links than the kernel takes (512), or none.  Exposed so that tests put
+ * batch sizes on both sides of it. */
+int32_t vgt_hip_cost_tile_samples(int64_t num_links);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

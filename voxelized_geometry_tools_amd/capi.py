@@ -113,6 +113,11 @@ SIGNATURES = {
     "vgt_hip_check_motions_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64,
                                          _p, _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_motion_tile_samples": (_i32, [_i64]),
+    "vgt_hip_clearance_cost": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p, _p, _f64,
+                                      ctypes.c_uint32, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_clearance_cost_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p, _p,
+                                          _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_cost_tile_samples": (_i32, [_i64]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -198,6 +203,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_align_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_kinematics_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_motion_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_cost_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
@@ -307,6 +313,11 @@ JointSphereChecks = collections.namedtuple("JointSphereChecks", SphereChecks._fi
 # what Context.check_motions returns: one entry per motion; min_gradient [E, 3]
 MotionChecks = collections.namedtuple(
     "MotionChecks", "status first_collision min_clearance min_sample min_sphere min_gradient fk_status")
+
+
+# what Context.clearance_cost returns: one entry per configuration; joint_gradient [B, J]
+ClearanceCosts = collections.namedtuple(
+    "ClearanceCosts", "cost joint_gradient num_active num_outside num_without_gradient fk_status")
 
 
 def _joint_values(tree, joint_values):
@@ -834,6 +845,49 @@ class Context:
             flags, _ptr(status_ptr), _ptr(first_collision_ptr), _ptr(min_clearance_ptr), _ptr(min_sample_ptr),
             _ptr(min_sphere_ptr), _ptr(min_gradient_ptr), _ptr(fk_status_ptr)))
 
+    def clearance_cost(self, sdf, resolution, spheres_xyzr, sphere_link, tree, joint_values, margin, grid_from_world=None,
+                       rotation=None, world_from_base=None, joint_limits=None, with_gradient=True):
+        """vgt_hip_clearance_cost: the obstacle cost of B configurations joint_values [B, J] -- the hinge of `margin` on
+        the clearance of every sphere, summed -- and its gradient with respect to the joints; poses and per-sphere values
+        never leave the device.  Returns ClearanceCosts(cost float64, joint_gradient [B, J] float64 (None without
+        with_gradient: then no gradient is loaded), num_active int32, num_outside int32, num_without_gradient int32
+        (None without with_gradient), fk_status uint8 (FK_* bits))."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be an (nx, ny, nz) grid")
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        q = _joint_values(tree, joint_values)
+        b, s = q.shape[0], len(xyzr)
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        out = ClearanceCosts(np.empty(b, np.float64), np.empty((b, q.shape[1]), np.float64) if with_gradient else None,
+                             np.empty(b, np.int32), np.empty(b, np.int32),
+                             np.empty(b, np.int32) if with_gradient else None, np.empty(b, np.uint8))
+        check(self._lib.vgt_hip_clearance_cost(
+            self.handle, _ptr(f), *f.shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(xyzr), _ptr(link), s,
+            tree._handle_or_raise(), _ptr(q), b, _ptr(_base_transform(world_from_base)),
+            _ptr(_joint_limits(tree, joint_limits)), float(margin), 0, *[_ptr(o) for o in out]))
+        return out
+
+    def clearance_cost_dev(self, sdf_ptr, shape, resolution, spheres_xyzr_ptr, sphere_link_ptr, num_spheres, tree,
+                           joint_values_ptr, num_configurations, margin, cost_ptr, joint_gradient_ptr=None,
+                           num_active_ptr=None, num_outside_ptr=None, num_without_gradient_ptr=None, fk_status_ptr=None,
+                           grid_from_world=None, rotation=None, world_from_base=None, joint_limits=None, flags=0):
+        """vgt_hip_clearance_cost_dev: field, model, joint values and outputs on the device (the transforms and the limits
+        are host arrays); enqueued on the context's stream.  Without joint_gradient_ptr and num_without_gradient_ptr the
+        cost-only kernel runs."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        check(self._lib.vgt_hip_clearance_cost_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
+            _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr), int(num_spheres), tree._handle_or_raise(),
+            _ptr(joint_values_ptr), int(num_configurations), _ptr(_base_transform(world_from_base)),
+            _ptr(_joint_limits(tree, joint_limits)), float(margin), int(flags), _ptr(cost_ptr), _ptr(joint_gradient_ptr),
+            _ptr(num_active_ptr), _ptr(num_outside_ptr), _ptr(num_without_gradient_ptr), _ptr(fk_status_ptr)))
+
     def rasterize_spheres(self, shape, resolution, spheres_xyzr, sphere_link, link_poses, padding=0.0, base=0, into=None,
                           grid_from_world=None):
         """vgt_hip_rasterize_spheres: the cells of a grid of `shape` that the model's spheres (as for check_spheres;
@@ -1334,6 +1388,11 @@ class Context:
         (0 = back to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_motion_workgroups(int(workgroups)))
 
+    def set_cost_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per launch of clearance_cost
+        (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_cost_workgroups(int(workgroups)))
+
     def set_sphere_volume_counters(self, counters_ptr):
         """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
         adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
@@ -1557,6 +1616,12 @@ def kinematics_lds_links():
 def motion_tile_samples(num_links):
     """vgt_hip_motion_tile_samples: the samples per tile check_motions uses for a tree of so many links; 0: too many."""
     return int(load().vgt_hip_motion_tile_samples(int(num_links)))
+
+
+def cost_tile_samples(num_links):
+    """vgt_hip_cost_tile_samples: the configurations per tile clearance_cost uses for a tree of so many links; 0: too
+    many."""
+    return int(load().vgt_hip_cost_tile_samples(int(num_links)))
 
 
 class KinematicTree:

@@ -175,6 +175,8 @@ std::atomic<int> g_align_workgroups{0};
 std::atomic<int> g_kinematics_workgroups{0};
 // The same from vgt_hip_testing_set_motion_workgroups, for the motion check.
 std::atomic<int> g_motion_workgroups{0};
+// The same from vgt_hip_testing_set_cost_workgroups, for the clearance cost.
+std::atomic<int> g_cost_workgroups{0};
 // The same from vgt_hip_testing_set_sphere_volume_workgroups, for the sphere rasterizer and the point cover.
 std::atomic<int> g_sphere_volume_workgroups{0};
 // What vgt_hip_testing_set_sphere_volume_counters gave: three uint64 on the device that the sphere rasterizer adds its
@@ -1661,6 +1663,12 @@ int vgt_hip_testing_set_kinematics_workgroups(int workgroups)
 int vgt_hip_testing_set_motion_workgroups(int workgroups)
 {
   g_motion_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_cost_workgroups(int workgroups)
+{
+  g_cost_workgroups.store(workgroups > 0 ? workgroups : 0);
   return VGT_HIP_OK;
 }
 
@@ -5293,6 +5301,183 @@ int vgt_hip_check_motions(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, i
       const vgt::MotionOutputs out{status.dev(),     first_collision.dev(), min_clearance.dev(), min_sample.dev(),
                                    min_sphere.dev(), min_gradient.dev(),    fk_status.dev()};
       return HipResult(what, a.Enqueue(sdf.dev(), xyzr.dev(), link.dev(), from.dev(), to.dev(), steps.dev(), out, stream));
+    });
+  });
+}
+
+/* ------------------- the obstacle cost of configurations given as joint values, and its joint gradient ------------------- */
+
+namespace
+{
+// What the two cost entry points share: the arguments and the checks both make before any device work.
+struct ClearanceCostArguments
+{
+  const float* sdf;
+  int64_t nx, ny, nz;
+  double resolution;
+  const double *grid_from_world, *rotation;
+  const double* sphere_xyzr;
+  const int32_t* sphere_link;
+  int64_t num_spheres;
+  const vgt_hip_kinematics* tree;
+  const double* joint_values;
+  int64_t num_configurations;
+  const double *world_from_base, *joint_limits;
+  double margin;
+  uint32_t flags;
+  vgt::CostOutputs out;
+
+  int64_t NumCells() const { return nx * ny * nz; }
+  // *done: nothing is left to do (B == 0).
+  int Check(const vgt_hip_ctx* ctx, bool* done) const
+  {
+    *done = false;
+    if (!ctx || !sdf || !tree || !out.cost || (num_spheres > 0 && (!sphere_xyzr || !sphere_link)))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_spheres < 0 || num_configurations < 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the numbers of spheres and configurations must not be negative");
+    if (nx < 0 || ny < 0 || nz < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must not be negative");
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Grid must have uniform, positive resolution");
+    // (extent by extent: the product of three int64 extents can overflow)
+    const int64_t most = 0x7fffffffLL;
+    if (nx > most || ny > most || nz > most || (nx > 0 && ny > 0 && nz > 0 && (nx * ny > most || nx * ny * nz > most)))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "clearance costs support grids below 2^31 cells");
+    if (!(margin > 0.0) || !std::isfinite(margin))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "margin must be positive and finite");
+    if (flags != 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown clearance cost flag");
+    if (num_spheres > most || num_configurations > most || num_spheres * num_configurations > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "clearance costs support fewer than 2^31 spheres, configurations and (configuration, sphere) pairs");
+    *done = num_configurations == 0;  // (before the tree is looked at)
+    return VGT_HIP_OK;
+  }
+  // What needs the tree (after B == 0, which succeeds before the tree is looked at).
+  int CheckTree(const vgt_hip_ctx* ctx) const
+  {
+    if (tree->ctx != ctx) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree belongs to another context");
+    if (vgt::CostTileSamples(tree->num_links) == 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "clearance costs take trees of at most " +
+                                                    std::to_string(vgt::kCostMaxLinks) + " links, this one has " +
+                                                    std::to_string(tree->num_links));
+    if (tree->num_joints > 0 && !joint_values) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_configurations * tree->num_joints >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "clearance costs support fewer than 2^31 (configuration, joint) pairs");
+    if (num_configurations * tree->num_links >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "clearance costs support fewer than 2^31 (configuration, link) pairs");
+    return VGT_HIP_OK;
+  }
+  // The host form's own checks: it can look at the model (the links once the tree is known).
+  int CheckHostArrays() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+      if (!(sphere_xyzr[4 * s + 3] >= 0.0))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "sphere " + std::to_string(s) + ": the radius must not be negative or NaN");
+    return VGT_HIP_OK;
+  }
+  int CheckHostLinks() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+      if (sphere_link[s] < 0 || sphere_link[s] >= tree->num_links)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(s) + ": link " +
+                                                      std::to_string(sphere_link[s]) + " is not in [0, num_links)");
+    return VGT_HIP_OK;
+  }
+  // Enqueues the call on `stream`; the context's mutex is held (the tree's limits buffer is one per tree).
+  hipError_t Enqueue(const float* sdf_dev, const double* xyzr_dev, const int32_t* link_dev, const double* joints_dev,
+                     const vgt::CostOutputs& out_dev, hipStream_t stream) const
+  {
+    const bool limited = joint_limits && tree->num_joints > 0;
+    if (limited)
+    {
+      // (pageable host memory: the runtime has taken its copy when the call returns)
+      const hipError_t err = hipMemcpyAsync(tree->limits.as<double>(), joint_limits,
+                                            static_cast<size_t>(tree->num_joints) * 2 * sizeof(double),
+                                            hipMemcpyHostToDevice, stream);
+      if (err != hipSuccess) return err;
+    }
+    return vgt::LaunchClearanceCost(sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, xyzr_dev, link_dev,
+                                    num_spheres, tree->links.as<vgt::KinematicLink>(), tree->num_links, tree->num_joints,
+                                    joints_dev, num_configurations, world_from_base,
+                                    limited ? tree->limits.as<double>() : nullptr, margin, out_dev,
+                                    g_cost_workgroups.load(), stream);
+  }
+};
+}  // namespace
+
+int32_t vgt_hip_cost_tile_samples(int64_t num_links) { return vgt::CostTileSamples(num_links); }
+
+int vgt_hip_clearance_cost_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz,
+                               double resolution, const double* grid_from_world, const double* rotation,
+                               const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                               const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                               int64_t num_configurations, const double* world_from_base, const double* joint_limits,
+                               double margin, uint32_t flags, double* cost_dev, double* joint_gradient_dev,
+                               int32_t* num_active_dev, int32_t* num_outside_dev, int32_t* num_without_gradient_dev,
+                               uint8_t* fk_status_dev)
+{
+  const ClearanceCostArguments a{sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_dev,
+                                 sphere_link_dev, num_spheres, tree, joint_values_dev, num_configurations,
+                                 world_from_base, joint_limits, margin, flags,
+                                 {cost_dev, joint_gradient_dev, num_active_dev, num_outside_dev,
+                                  num_without_gradient_dev, fk_status_dev}};
+  bool done = false;
+  int rc = a.Check(ctx, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  rc = a.CheckTree(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(a.Enqueue(sdf_dev, sphere_xyzr_dev, sphere_link_dev, joint_values_dev, a.out, ctx->stream),
+              "clearance cost");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_clearance_cost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                           const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+                           const int32_t* sphere_link_host, int64_t num_spheres, const vgt_hip_kinematics* tree,
+                           const double* joint_values_host, int64_t num_configurations, const double* world_from_base,
+                           const double* joint_limits, double margin, uint32_t flags, double* cost_host,
+                           double* joint_gradient_host, int32_t* num_active_host, int32_t* num_outside_host,
+                           int32_t* num_without_gradient_host, uint8_t* fk_status_host)
+{
+  const ClearanceCostArguments a{sdf_host, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_host,
+                                 sphere_link_host, num_spheres, tree, joint_values_host, num_configurations,
+                                 world_from_base, joint_limits, margin, flags,
+                                 {cost_host, joint_gradient_host, num_active_host, num_outside_host,
+                                  num_without_gradient_host, fk_status_host}};
+  bool done = false;
+  int rc = a.Check(ctx, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  rc = a.CheckHostArrays();
+  if (rc == VGT_HIP_OK) rc = a.CheckTree(ctx);
+  if (rc == VGT_HIP_OK) rc = a.CheckHostLinks();
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "clearance cost";
+  const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+  const size_t joints = static_cast<size_t>(tree->num_joints);
+  // (a tree without joints: one double stands in, so that the kernel has an address it never reads)
+  const double none = 0.0;
+  // (six outputs and four inputs, and a staging holds eight arrays: two of them, the second inside the first one's body)
+  vgt::HostStaging inputs;
+  const auto sdf = inputs.In(sdf_host, static_cast<size_t>(a.NumCells()));
+  const auto xyzr = inputs.In(sphere_xyzr_host, s * 4);
+  const auto link = inputs.In(sphere_link_host, s);
+  const auto values = joints > 0 ? inputs.In(joint_values_host, b * joints) : inputs.In(&none, 1);
+  return inputs.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    vgt::HostStaging outputs;
+    const auto cost = outputs.Out(cost_host, b);
+    const auto joint_gradient = outputs.Out(joint_gradient_host, b * joints);
+    const auto num_active = outputs.Out(num_active_host, b);
+    const auto num_outside = outputs.Out(num_outside_host, b);
+    const auto num_without_gradient = outputs.Out(num_without_gradient_host, b);
+    const auto fk_status = outputs.Out(fk_status_host, b);
+    return outputs.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+      const vgt::CostOutputs out{cost.dev(),        joint_gradient.dev(),       num_active.dev(),
+                                 num_outside.dev(), num_without_gradient.dev(), fk_status.dev()};
+      return HipResult(what, a.Enqueue(sdf.dev(), xyzr.dev(), link.dev(), values.dev(), out, stream));
     });
   });
 }

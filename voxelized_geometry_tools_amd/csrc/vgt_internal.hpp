@@ -619,6 +619,39 @@ hipError_t LaunchCheckMotions(const float* sdf_dev, int64_t nx, int64_t ny, int6
                               const double* limits_dev, double minimum_clearance, int outside_is_collision,
                               int stop_at_collision, const MotionOutputs& out, int max_workgroups, hipStream_t stream);
 
+// --- launcher (cost_kernels.hip): the obstacle cost of configurations given as joint values, and its joint gradient ---
+// The definition of every output: include/vgt_hip.h, vgt_hip_clearance_cost.  cost is required, every other output may
+// be nullptr.
+struct CostOutputs
+{
+  double* cost;
+  double* joint_gradient;
+  int32_t* num_active;
+  int32_t* num_outside;
+  int32_t* num_without_gradient;
+  uint8_t* fk_status;
+};
+// The configurations of a tile for a tree of so many links: a power of two T <= 64 with 96 * L * T <= 48 KiB -- the
+// largest one within the build's VGT_COST_MAX_TILE and VGT_COST_TILE_BYTES (6 KiB of poses, where more than one
+// configuration fits them); 0: more links than the kernel takes (512), or none.
+int CostTileSamples(int64_t num_links);
+// The dynamic LDS the poses of a tile may take, what a link takes of it per configuration, and so the most links of a
+// tree: 512 (one configuration per tile).  Next to 48 KiB of poses the launch needs one pass of the buffer (64 entries of
+// 68 B) and 20 B of resting sums: 53524 B of the 64 KiB a launch gets without an attribute.
+constexpr size_t kCostPoseBudget = 48 * 1024, kCostPoseBytesPerLink = 96;
+constexpr int64_t kCostMaxLinks = static_cast<int64_t>(kCostPoseBudget / kCostPoseBytesPerLink);
+// Grids of 0 to 2^31 - 1 cells; fewer than 2^31 spheres, configurations and (configuration, joint) pairs; a tree
+// CostTileSamples takes.  Field, model, joint values and outputs on the device; the three transforms are host arrays (or
+// nullptr); limits_dev: [J][2] or nullptr.  Without joint_gradient and num_without_gradient the cost-only kernel runs,
+// which loads no gradient.  max_workgroups: 0 = the launcher's own limit (vgt_hip_testing_set_cost_workgroups).
+hipError_t LaunchClearanceCost(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                               const double* grid_from_world_host, const double* rotation_host,
+                               const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                               const KinematicLink* links_dev, int64_t num_links, int64_t num_joints,
+                               const double* joint_values_dev, int64_t num_configurations,
+                               const double* world_from_base_host, const double* limits_dev, double margin,
+                               const CostOutputs& out, int max_workgroups, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
