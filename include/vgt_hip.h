@@ -285,6 +285,8 @@ int vgt_hip_testing_set_motion_workgroups(int workgroups);
 /* The same for the launches of vgt_hip_clearance_cost[_dev] (one workgroup per tile of configurations), so that a few
  * hundred configurations already make its persistent waves stride. */
 int vgt_hip_testing_set_cost_workgroups(int workgroups);
+/* The same for the launches of vgt_hip_check_self_collision[_poses][_dev] (one workgroup per tile of configurations). */
+int vgt_hip_testing_set_self_collision_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
  * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
  * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
@@ -1024,6 +1026,115 @@ int vgt_hip_clearance_cost_dev(vgt_hip_ctx* ctx, const float* sdf_dev, int64_t n
  * configuration fits that: DESIGN.md 4o); 0: more links than the kernel takes (512), or none.  Exposed so that tests put
  * batch sizes on both sides of it. */
 int32_t vgt_hip_cost_tile_samples(int64_t num_links);
+
+/* ---- Self-collision of a sphere model, batched over configurations ----
+ * The calls above ask whether the robot touches the ENVIRONMENT; this one asks whether it touches ITSELF: B
+ * configurations and a list of P sphere pairs in; per configuration a verdict, two counts, the worst pair with its
+ * clearance and direction, and that clearance's gradient with respect to the joints out.  Link poses and sphere centres
+ * are made and used on the device and are never written to memory (csrc/self_collision_kernels.hip).  No field is
+ * involved.  Read-only.  A caller combines this verdict with the environment's.
+ *
+ * The model (sphere_xyzr [S][4], sphere_link [S]) and the tree are exactly those of vgt_hip_check_spheres /
+ * vgt_hip_forward_kinematics.  The pair list is pairs [P][2] int32, each row (a, b) with 0 <= a < b < S; duplicates are
+ * allowed and the order is the caller's (vgt_hip_self_collision_pairs below makes one).
+ *
+ * THE DEFINITION.  Per (configuration, pair p = (a, b)), in double, without contraction, every operator rounded on its
+ * own: ca, cb are the world centres of the spheres a and b -- vgt_hip_check_spheres' expression w_r on the pose that
+ * vgt_hip_forward_kinematics defines (or on the link pose given, in the poses form); nothing of either is restated --,
+ *   e_r = ca_r - cb_r      d2 = (e0 * e0 + e1 * e1) + e2 * e2      dist = sqrt(d2), correctly rounded
+ *   clearance = (dist - ra) - rb
+ * A pair is "without a value" when its clearance is NaN: a NaN pose from a link that is not computable, a NaN centre,
+ * infinity minus infinity and, in the device forms, a sphere index outside [0, S) or a sphere_link outside [0, L) (no
+ * address is formed from such a value).  +-infinity compare as they are.
+ * Outputs per configuration; status is required, every other output may be NULL:
+ *   num_below (int32)           pairs with a value and clearance <= minimum_clearance
+ *   num_without_value (int32)   pairs without a value
+ *   min_clearance (double), min_pair (int32, an index into pairs)
+ *                               the least non-NaN clearance and the index of its pair; ties under == go to the lowest p;
+ *                               NaN and -1 when there is none
+ *   min_direction [3] (double)  n_r = e_r / dist of min_pair: three divisions, as arithmetic gives them (coincident
+ *                               centres: NaN); NaN x3 when min_pair == -1
+ *   joint_gradient [J] (double) the summed form of vgt_hip_clearance_joint_gradient, to the bit, with every weight 0 but
+ *                               sphere_weight[a] = sphere_weight[b] = 1.0 and sphere_gradient[a] = n, sphere_gradient[b]
+ *                               = -n: acc_j = +0.0, then sphere a's walk with g = n, then sphere b's with g = -n.  A NaN
+ *                               row when min_pair == -1.  It is d min_clearance / d q wherever the worst pair does not
+ *                               change.
+ *   status (uint8)              VGT_HIP_SELF_COLLISION when num_below > 0, or flags & VGT_HIP_SELF_NO_VALUE_IS_COLLISION
+ *                               and num_without_value > 0; otherwise VGT_HIP_SELF_CLEAR when min_pair != -1; otherwise
+ *                               VGT_HIP_SELF_NO_VALUE
+ *   fk_status (uint8)           the forward kinematics' status (the joint-value forms only)
+ * and per pair, optional: pair_clearance [B][P], NaN without a value.
+ * The worst pair is a total order and the counts are integer sums: no output depends on the launch geometry.
+ *
+ * vgt_hip_check_self_collision takes joint values (the tree, joint_values [B][J], world_from_base, joint_limits, as
+ * vgt_hip_forward_kinematics takes them); vgt_hip_check_self_collision_poses takes link_poses [B][L][16] as
+ * vgt_hip_check_spheres takes them, with num_links given, and a tree only for joint_gradient (NULL with a NULL
+ * joint_gradient; otherwise a tree of num_links links whose J gives the row length).
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: a NULL required pointer (ctx, status; the tree in the joint-value
+ * forms; the model's arrays when S > 0; pairs when P > 0 and S > 0; joint_values when B > 0 and J > 0; link_poses when
+ * B > 0); joint_gradient without a tree; a NaN minimum_clearance; an unknown flag bit; negative counts; B, S, P, B * J or
+ * B * L of 2^31 or more, or B * P of 2^31 or more when pair_clearance is given; a tree of another context, or of another
+ * number of links than num_links; a tree or model larger than the kernel takes (vgt_hip_self_collision_tile_samples
+ * gives 0; the message gives both numbers).  The host forms also look at their arrays and name the first offender:
+ * "sphere 17: link 9 is not in [0, num_links)", "sphere 17: the radius must not be negative or NaN", "pair 3: sphere 300
+ * is outside [0, 200)", "pair 12: (5, 5) is not ascending".  The device forms cannot look.
+ * B == 0 succeeds without a device.  P == 0 or S == 0 give NaN, -1, counts 0 and NO_VALUE (with S == 0 the pair list is
+ * not looked at in either form, and pair_clearance is not written).  The host forms stage their arrays and block; the
+ * device forms (model, pairs, joint values or link poses and outputs on the device; world_from_base and joint_limits
+ * are host arrays) are enqueued on the context's stream, not blocking.  Calls that use one tree are serialised by the
+ * context. */
+#define VGT_HIP_SELF_NO_VALUE_IS_COLLISION 1u
+#define VGT_HIP_SELF_CLEAR 0
+#define VGT_HIP_SELF_COLLISION 1
+#define VGT_HIP_SELF_NO_VALUE 2
+int vgt_hip_check_self_collision(vgt_hip_ctx* ctx, const double* sphere_xyzr_host, const int32_t* sphere_link_host,
+                                 int64_t num_spheres, const int32_t* pairs_host, int64_t num_pairs,
+                                 const vgt_hip_kinematics* tree, const double* joint_values_host,
+                                 int64_t num_configurations, const double* world_from_base, const double* joint_limits,
+                                 double minimum_clearance, uint32_t flags, uint8_t* status_host, int32_t* num_below_host,
+                                 int32_t* num_without_value_host, double* min_clearance_host, int32_t* min_pair_host,
+                                 double* min_direction_host, double* joint_gradient_host, uint8_t* fk_status_host,
+                                 double* pair_clearance_host);
+int vgt_hip_check_self_collision_dev(vgt_hip_ctx* ctx, const double* sphere_xyzr_dev, const int32_t* sphere_link_dev,
+                                     int64_t num_spheres, const int32_t* pairs_dev, int64_t num_pairs,
+                                     const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                                     int64_t num_configurations, const double* world_from_base,
+                                     const double* joint_limits, double minimum_clearance, uint32_t flags,
+                                     uint8_t* status_dev, int32_t* num_below_dev, int32_t* num_without_value_dev,
+                                     double* min_clearance_dev, int32_t* min_pair_dev, double* min_direction_dev,
+                                     double* joint_gradient_dev, uint8_t* fk_status_dev, double* pair_clearance_dev);
+int vgt_hip_check_self_collision_poses(vgt_hip_ctx* ctx, const double* sphere_xyzr_host, const int32_t* sphere_link_host,
+                                       int64_t num_spheres, const int32_t* pairs_host, int64_t num_pairs,
+                                       const double* link_poses_host, int64_t num_configurations, int64_t num_links,
+                                       const vgt_hip_kinematics* tree, double minimum_clearance, uint32_t flags,
+                                       uint8_t* status_host, int32_t* num_below_host, int32_t* num_without_value_host,
+                                       double* min_clearance_host, int32_t* min_pair_host, double* min_direction_host,
+                                       double* joint_gradient_host, double* pair_clearance_host);
+int vgt_hip_check_self_collision_poses_dev(vgt_hip_ctx* ctx, const double* sphere_xyzr_dev,
+                                           const int32_t* sphere_link_dev, int64_t num_spheres, const int32_t* pairs_dev,
+                                           int64_t num_pairs, const double* link_poses_dev, int64_t num_configurations,
+                                           int64_t num_links, const vgt_hip_kinematics* tree, double minimum_clearance,
+                                           uint32_t flags, uint8_t* status_dev, int32_t* num_below_dev,
+                                           int32_t* num_without_value_dev, double* min_clearance_dev,
+                                           int32_t* min_pair_dev, double* min_direction_dev, double* joint_gradient_dev,
+                                           double* pair_clearance_dev);
+/* The pair list of a model, on the host (no context, no device): in lexicographic order every (a, b) with a < b whose
+ * spheres sit on different links that are not an ignored pair and -- with flags & VGT_HIP_SELF_PAIRS_SKIP_ADJACENT and
+ * `parent` given -- of which neither is the other's direct parent.  sphere_link [S]; parent [L] (each in [-1, L)) or
+ * NULL; ignored_link_pairs [K][2], unordered, or NULL with K == 0.  Writes at most `capacity` rows to pairs_out (NULL
+ * with capacity == 0 only counts); *count always receives the full number.  VGT_HIP_ERR_INVALID_ARGUMENT, naming the
+ * first offender: "sphere 3: link 9 is not in [0, num_links)", "link 3: parent 9 is not in [-1, num_links)", "ignored
+ * pair 2: link 9 is not in [0, num_links)"; also a NULL count or sphere_link (S > 0), negative numbers, an unknown flag
+ * bit. */
+#define VGT_HIP_SELF_PAIRS_SKIP_ADJACENT 1u
+int vgt_hip_self_collision_pairs(const int32_t* sphere_link, int64_t num_spheres, const int32_t* parent,
+                                 int64_t num_links, const int32_t* ignored_link_pairs, int64_t num_ignored,
+                                 uint32_t flags, int32_t* pairs_out, int64_t capacity, int64_t* count);
+/* The configurations per tile the kernel uses for a tree of so many links carrying so many spheres: a power of two, at
+ * most 64, whose poses and centres take (96 L + 24 S) T <= 16 KiB of LDS where more than one configuration fits that
+ * (DESIGN.md 4p); 0: no links, or one configuration does not fit a launch's 64 KiB (96 L + 32 S + 256 bytes: 680 links
+ * without spheres, 2037 spheres on one link).  Exposed so that tests put batch sizes and models on both sides of it. */
+int32_t vgt_hip_self_collision_tile_samples(int64_t num_links, int64_t num_spheres);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

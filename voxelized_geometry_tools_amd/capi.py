@@ -118,6 +118,16 @@ SIGNATURES = {
     "vgt_hip_clearance_cost_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p, _p,
                                           _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_cost_tile_samples": (_i32, [_i64]),
+    "vgt_hip_check_self_collision": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _f64, ctypes.c_uint32,
+                                            _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_self_collision_dev": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _f64, ctypes.c_uint32,
+                                                _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_self_collision_poses": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _f64, ctypes.c_uint32,
+                                                  _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_self_collision_poses_dev": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _f64,
+                                                      ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_self_collision_pairs": (_int, [_p, _i64, _p, _i64, _p, _i64, ctypes.c_uint32, _p, _i64, _p]),
+    "vgt_hip_self_collision_tile_samples": (_i32, [_i64, _i64]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -204,6 +214,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_kinematics_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_motion_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_cost_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_self_collision_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
@@ -248,6 +259,12 @@ MOTION_CLEAR = 0
 MOTION_COLLISION = 1
 MOTION_NO_VALUE = 2
 MOTION_INVALID = 3
+# flags and statuses of check_self_collision and self_collision_pairs (VGT_HIP_SELF_*)
+SELF_NO_VALUE_IS_COLLISION = 1
+SELF_CLEAR = 0
+SELF_COLLISION = 1
+SELF_NO_VALUE = 2
+SELF_PAIRS_SKIP_ADJACENT = 1
 ALIGN_CONVERGED = 0
 ALIGN_ITERATION_LIMIT = 1
 ALIGN_DEGENERATE = 2
@@ -318,6 +335,18 @@ MotionChecks = collections.namedtuple(
 # what Context.clearance_cost returns: one entry per configuration; joint_gradient [B, J]
 ClearanceCosts = collections.namedtuple(
     "ClearanceCosts", "cost joint_gradient num_active num_outside num_without_gradient fk_status")
+
+
+# what Context.check_self_collision returns: one entry per configuration; min_direction [B, 3], joint_gradient [B, J],
+# pair_clearance [B, P] (None unless asked for); fk_status is None in the poses form
+SelfCollisionChecks = collections.namedtuple(
+    "SelfCollisionChecks", "status num_below num_without_value min_clearance min_pair min_direction joint_gradient "
+    "fk_status pair_clearance")
+
+
+def _sphere_pairs(pairs):
+    """[P, 2] int32"""
+    return np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
 
 
 def _joint_values(tree, joint_values):
@@ -888,6 +917,85 @@ class Context:
             _ptr(_joint_limits(tree, joint_limits)), float(margin), int(flags), _ptr(cost_ptr), _ptr(joint_gradient_ptr),
             _ptr(num_active_ptr), _ptr(num_outside_ptr), _ptr(num_without_gradient_ptr), _ptr(fk_status_ptr)))
 
+    def check_self_collision(self, spheres_xyzr, sphere_link, pairs, tree, joint_values, minimum_clearance=0.0,
+                             no_value_is_collision=False, per_pair=False, with_gradient=True, world_from_base=None,
+                             joint_limits=None):
+        """vgt_hip_check_self_collision: the sphere pairs `pairs` [P, 2] (a < b; self_collision_pairs makes a list) of a
+        model in the B configurations joint_values [B, J]; poses and centres never leave the device.  Returns
+        SelfCollisionChecks(status uint8 (SELF_*), num_below int32, num_without_value int32, min_clearance float64,
+        min_pair int32 (-1: none), min_direction [B, 3] float64, joint_gradient [B, J] float64 (None without
+        with_gradient), fk_status uint8 (FK_* bits), pair_clearance [B, P] float64 (None without per_pair))."""
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        ab = _sphere_pairs(pairs)
+        q = _joint_values(tree, joint_values)
+        b = q.shape[0]
+        out = SelfCollisionChecks(np.empty(b, np.uint8), np.empty(b, np.int32), np.empty(b, np.int32),
+                                  np.empty(b, np.float64), np.empty(b, np.int32), np.empty((b, 3), np.float64),
+                                  np.empty((b, q.shape[1]), np.float64) if with_gradient else None,
+                                  np.empty(b, np.uint8), np.empty((b, len(ab)), np.float64) if per_pair else None)
+        flags = SELF_NO_VALUE_IS_COLLISION if no_value_is_collision else 0
+        check(self._lib.vgt_hip_check_self_collision(
+            self.handle, _ptr(xyzr), _ptr(link), len(xyzr), _ptr(ab), len(ab), tree._handle_or_raise(), _ptr(q), b,
+            _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
+            flags, *[_ptr(o) for o in out]))
+        return out
+
+    def check_self_collision_dev(self, spheres_xyzr_ptr, sphere_link_ptr, num_spheres, pairs_ptr, num_pairs, tree,
+                                 joint_values_ptr, num_configurations, status_ptr, minimum_clearance=0.0,
+                                 num_below_ptr=None, num_without_value_ptr=None, min_clearance_ptr=None,
+                                 min_pair_ptr=None, min_direction_ptr=None, joint_gradient_ptr=None, fk_status_ptr=None,
+                                 pair_clearance_ptr=None, world_from_base=None, joint_limits=None, flags=0):
+        """vgt_hip_check_self_collision_dev: model, pairs, joint values and outputs on the device (the base transform and
+        the limits are host arrays); enqueued on the context's stream."""
+        check(self._lib.vgt_hip_check_self_collision_dev(
+            self.handle, _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr), int(num_spheres), _ptr(pairs_ptr),
+            int(num_pairs), tree._handle_or_raise(), _ptr(joint_values_ptr), int(num_configurations),
+            _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
+            int(flags), _ptr(status_ptr), _ptr(num_below_ptr), _ptr(num_without_value_ptr), _ptr(min_clearance_ptr),
+            _ptr(min_pair_ptr), _ptr(min_direction_ptr), _ptr(joint_gradient_ptr), _ptr(fk_status_ptr),
+            _ptr(pair_clearance_ptr)))
+
+    def check_self_collision_poses(self, spheres_xyzr, sphere_link, pairs, link_poses, tree=None, minimum_clearance=0.0,
+                                   no_value_is_collision=False, per_pair=False):
+        """vgt_hip_check_self_collision_poses: the same from link_poses [B, L, 16] (as check_spheres takes them); the
+        joint gradient only with a tree (of L links).  fk_status is None."""
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        ab = _sphere_pairs(pairs)
+        poses = np.ascontiguousarray(link_poses, dtype=np.float64)
+        if poses.ndim != 3 or poses.shape[2] != 16:
+            raise ValueError("link_poses must be [B, L, 16]")
+        b, links = poses.shape[0], poses.shape[1]
+        joints = tree.num_joints if tree is not None else 0
+        out = SelfCollisionChecks(np.empty(b, np.uint8), np.empty(b, np.int32), np.empty(b, np.int32),
+                                  np.empty(b, np.float64), np.empty(b, np.int32), np.empty((b, 3), np.float64),
+                                  np.empty((b, joints), np.float64) if tree is not None else None, None,
+                                  np.empty((b, len(ab)), np.float64) if per_pair else None)
+        flags = SELF_NO_VALUE_IS_COLLISION if no_value_is_collision else 0
+        check(self._lib.vgt_hip_check_self_collision_poses(
+            self.handle, _ptr(xyzr), _ptr(link), len(xyzr), _ptr(ab), len(ab), _ptr(poses), b, links,
+            tree._handle_or_raise() if tree is not None else None, float(minimum_clearance), flags,
+            *[_ptr(o) for i, o in enumerate(out) if i != 7]))
+        return out
+
+    def check_self_collision_poses_dev(self, spheres_xyzr_ptr, sphere_link_ptr, num_spheres, pairs_ptr, num_pairs,
+                                       link_poses_ptr, num_configurations, num_links, status_ptr, tree=None,
+                                       minimum_clearance=0.0, num_below_ptr=None, num_without_value_ptr=None,
+                                       min_clearance_ptr=None, min_pair_ptr=None, min_direction_ptr=None,
+                                       joint_gradient_ptr=None, pair_clearance_ptr=None, flags=0):
+        """vgt_hip_check_self_collision_poses_dev: everything on the device; enqueued on the context's stream."""
+        check(self._lib.vgt_hip_check_self_collision_poses_dev(
+            self.handle, _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr), int(num_spheres), _ptr(pairs_ptr),
+            int(num_pairs), _ptr(link_poses_ptr), int(num_configurations), int(num_links),
+            tree._handle_or_raise() if tree is not None else None, float(minimum_clearance), int(flags),
+            _ptr(status_ptr), _ptr(num_below_ptr), _ptr(num_without_value_ptr), _ptr(min_clearance_ptr),
+            _ptr(min_pair_ptr), _ptr(min_direction_ptr), _ptr(joint_gradient_ptr), _ptr(pair_clearance_ptr)))
+
     def rasterize_spheres(self, shape, resolution, spheres_xyzr, sphere_link, link_poses, padding=0.0, base=0, into=None,
                           grid_from_world=None):
         """vgt_hip_rasterize_spheres: the cells of a grid of `shape` that the model's spheres (as for check_spheres;
@@ -1393,6 +1501,11 @@ class Context:
         (0 = back to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_cost_workgroups(int(workgroups)))
 
+    def set_self_collision_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per launch of check_self_collision
+        (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_self_collision_workgroups(int(workgroups)))
+
     def set_sphere_volume_counters(self, counters_ptr):
         """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
         adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
@@ -1622,6 +1735,39 @@ def cost_tile_samples(num_links):
     """vgt_hip_cost_tile_samples: the configurations per tile clearance_cost uses for a tree of so many links; 0: too
     many."""
     return int(load().vgt_hip_cost_tile_samples(int(num_links)))
+
+
+def self_collision_tile_samples(num_links, num_spheres):
+    """vgt_hip_self_collision_tile_samples: the configurations per tile check_self_collision uses for a tree of so many
+    links carrying so many spheres; 0: the kernel does not take the shape."""
+    return int(load().vgt_hip_self_collision_tile_samples(int(num_links), int(num_spheres)))
+
+
+def self_collision_pairs(sphere_link, num_links, parent=None, ignored_link_pairs=None, skip_adjacent=False,
+                         capacity=None):
+    """vgt_hip_self_collision_pairs (host only, no context): -> (pairs [min(count, capacity), 2] int32, count): in
+    lexicographic order every (a, b), a < b, of spheres on different links that are not an ignored link pair
+    (`ignored_link_pairs` [K, 2], unordered) and, with skip_adjacent and `parent` [L], not parent and child.  capacity
+    None: room for all of them."""
+    link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+    up = None if parent is None else np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+    if up is not None and len(up) != int(num_links):
+        raise ValueError("parent must hold one entry per link")
+    ignored = None if ignored_link_pairs is None else _sphere_pairs(ignored_link_pairs)
+    flags = SELF_PAIRS_SKIP_ADJACENT if skip_adjacent else 0
+    lib = load()
+    count = ctypes.c_int64(-1)
+
+    def call(out, room):
+        check(lib.vgt_hip_self_collision_pairs(_ptr(link), len(link), _ptr(up), int(num_links), _ptr(ignored),
+                                               0 if ignored is None else len(ignored), flags, _ptr(out), room,
+                                               ctypes.byref(count)))
+    if capacity is None:
+        call(None, 0)
+        capacity = count.value
+    out = np.empty((int(capacity), 2), np.int32)
+    call(out if capacity > 0 else None, int(capacity))
+    return out[:min(count.value, int(capacity))], int(count.value)
 
 
 class KinematicTree:

@@ -177,6 +177,8 @@ std::atomic<int> g_kinematics_workgroups{0};
 std::atomic<int> g_motion_workgroups{0};
 // The same from vgt_hip_testing_set_cost_workgroups, for the clearance cost.
 std::atomic<int> g_cost_workgroups{0};
+// The same from vgt_hip_testing_set_self_collision_workgroups, for the self-collision check.
+std::atomic<int> g_self_collision_workgroups{0};
 // The same from vgt_hip_testing_set_sphere_volume_workgroups, for the sphere rasterizer and the point cover.
 std::atomic<int> g_sphere_volume_workgroups{0};
 // What vgt_hip_testing_set_sphere_volume_counters gave: three uint64 on the device that the sphere rasterizer adds its
@@ -1669,6 +1671,12 @@ int vgt_hip_testing_set_motion_workgroups(int workgroups)
 int vgt_hip_testing_set_cost_workgroups(int workgroups)
 {
   g_cost_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_self_collision_workgroups(int workgroups)
+{
+  g_self_collision_workgroups.store(workgroups > 0 ? workgroups : 0);
   return VGT_HIP_OK;
 }
 
@@ -5480,6 +5488,316 @@ int vgt_hip_clearance_cost(vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, 
       return HipResult(what, a.Enqueue(sdf.dev(), xyzr.dev(), link.dev(), values.dev(), out, stream));
     });
   });
+}
+
+/* ------------------------- self-collision of a sphere model, batched over configurations ------------------------- */
+
+namespace
+{
+// What the four self-collision entry points share: the arguments and the checks they make before any device work.
+struct SelfCollisionArguments
+{
+  const double* sphere_xyzr;
+  const int32_t* sphere_link;
+  int64_t num_spheres;
+  const int32_t* pairs;
+  int64_t num_pairs;
+  const vgt_hip_kinematics* tree;  // the poses form: only for the gradient
+  const double* joint_values;      // the joint-value form
+  const double* link_poses;        // the poses form
+  bool from_joints;
+  int64_t num_configurations, num_links;  // (the joint-value form: num_links is the tree's, filled in by Check)
+  const double *world_from_base, *joint_limits;
+  double minimum_clearance;
+  uint32_t flags;
+  vgt::SelfCollisionOutputs out;
+
+  int64_t NumJoints() const { return tree ? tree->num_joints : 0; }
+  // *done: nothing is left to do (B == 0).
+  int Check(const vgt_hip_ctx* ctx, bool* done)
+  {
+    *done = false;
+    if (!ctx || !out.status || (from_joints && !tree) || (num_spheres > 0 && (!sphere_xyzr || !sphere_link)) ||
+        (num_spheres > 0 && num_pairs > 0 && !pairs))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_spheres < 0 || num_pairs < 0 || num_configurations < 0 || (!from_joints && num_links < 0))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "the numbers of spheres, pairs, configurations and links must not be negative");
+    if (std::isnan(minimum_clearance)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "minimum_clearance must not be NaN");
+    if ((flags & ~VGT_HIP_SELF_NO_VALUE_IS_COLLISION) != 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown self-collision flag");
+    if (out.joint_gradient && !tree)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the joint gradient needs the kinematic tree");
+    const int64_t most = 0x7fffffffLL;
+    if (num_spheres > most || num_pairs > most || num_configurations > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "self-collision checks support fewer than 2^31 spheres, pairs and configurations");
+    if (out.pair_clearance && num_configurations * num_pairs > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "self-collision checks support fewer than 2^31 (configuration, pair) clearances");
+    *done = num_configurations == 0;  // (before the tree is looked at)
+    return VGT_HIP_OK;
+  }
+  // What needs the tree or the number of links (after B == 0, which succeeds before either is looked at).
+  int CheckTree(const vgt_hip_ctx* ctx)
+  {
+    if (tree && tree->ctx != ctx)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree belongs to another context");
+    if (from_joints)
+      num_links = tree->num_links;
+    else if (tree && tree->num_links != num_links)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree has " + std::to_string(tree->num_links) +
+                                                    " links, the poses have " + std::to_string(num_links));
+    if (vgt::SelfCollisionTileSamples(num_links, num_spheres) == 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "self-collision checks take at least one link and 96 bytes per link + 32 per sphere + 256 within " +
+                      std::to_string(vgt::kSelfLdsLimit) + ", this model has " + std::to_string(num_links) +
+                      " links and " + std::to_string(num_spheres) + " spheres");
+    if (from_joints ? (tree->num_joints > 0 && !joint_values) : !link_poses)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_configurations * NumJoints() >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "self-collision checks support fewer than 2^31 (configuration, joint) pairs");
+    if (num_configurations * num_links >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "self-collision checks support fewer than 2^31 (configuration, link) pairs");
+    return VGT_HIP_OK;
+  }
+  // The host forms' own checks: they can look at the model and the pairs (the links once their number is known).
+  int CheckHostArrays() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+      if (!(sphere_xyzr[4 * s + 3] >= 0.0))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "sphere " + std::to_string(s) + ": the radius must not be negative or NaN");
+    for (int64_t p = 0; num_spheres > 0 && p < num_pairs; p++)
+    {
+      const int64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+      for (const int64_t sphere : {a, b})
+        if (sphere < 0 || sphere >= num_spheres)
+          return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "pair " + std::to_string(p) + ": sphere " + std::to_string(sphere) +
+                                                        " is outside [0, " + std::to_string(num_spheres) + ")");
+      if (a >= b)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "pair " + std::to_string(p) + ": (" + std::to_string(a) + ", " +
+                                                      std::to_string(b) + ") is not ascending");
+    }
+    return VGT_HIP_OK;
+  }
+  int CheckHostLinks() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+      if (sphere_link[s] < 0 || sphere_link[s] >= num_links)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(s) + ": link " +
+                                                      std::to_string(sphere_link[s]) + " is not in [0, num_links)");
+    return VGT_HIP_OK;
+  }
+  // Enqueues the call on `stream`; the context's mutex is held (the tree's limits buffer is one per tree).
+  hipError_t Enqueue(const double* xyzr_dev, const int32_t* link_dev, const int32_t* pairs_dev, const double* source_dev,
+                     const vgt::SelfCollisionOutputs& out_dev, hipStream_t stream) const
+  {
+    const bool limited = from_joints && joint_limits && tree->num_joints > 0;
+    if (limited)
+    {
+      // (pageable host memory: the runtime has taken its copy when the call returns)
+      const hipError_t err = hipMemcpyAsync(tree->limits.as<double>(), joint_limits,
+                                            static_cast<size_t>(tree->num_joints) * 2 * sizeof(double),
+                                            hipMemcpyHostToDevice, stream);
+      if (err != hipSuccess) return err;
+    }
+    return vgt::LaunchSelfCollision(xyzr_dev, link_dev, num_spheres, pairs_dev, num_pairs,
+                                    tree ? tree->links.as<vgt::KinematicLink>() : nullptr, num_links, NumJoints(),
+                                    from_joints ? source_dev : nullptr, from_joints ? nullptr : source_dev,
+                                    num_configurations, world_from_base, limited ? tree->limits.as<double>() : nullptr,
+                                    minimum_clearance, (flags & VGT_HIP_SELF_NO_VALUE_IS_COLLISION) ? 1 : 0, out_dev,
+                                    g_self_collision_workgroups.load(), stream);
+  }
+  int RunOnDevice(vgt_hip_ctx* ctx)
+  {
+    bool done = false;
+    int rc = Check(ctx, &done);
+    if (rc != VGT_HIP_OK || done) return rc;
+    rc = CheckTree(ctx);
+    if (rc != VGT_HIP_OK) return rc;
+    VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+    // (a tree without joints: an address the kernel never reads stands in, so that the launcher can tell the forms)
+    static const double none = 0.0;
+    const double* const source = from_joints ? (joint_values ? joint_values : &none) : link_poses;
+    std::lock_guard<std::mutex> lock(ctx->mutex);
+    VGT_TRY_HIP(Enqueue(sphere_xyzr, sphere_link, pairs, source, out, ctx->stream), "self-collision check");
+    return VGT_HIP_OK;
+  }
+  int RunFromHost(vgt_hip_ctx* ctx)
+  {
+    bool done = false;
+    int rc = Check(ctx, &done);
+    if (rc != VGT_HIP_OK || done) return rc;
+    rc = CheckHostArrays();
+    if (rc == VGT_HIP_OK) rc = CheckTree(ctx);
+    if (rc == VGT_HIP_OK) rc = CheckHostLinks();
+    if (rc != VGT_HIP_OK) return rc;
+    VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+    const char* what = "self-collision check";
+    const size_t b = static_cast<size_t>(num_configurations), s = static_cast<size_t>(num_spheres);
+    const size_t p = static_cast<size_t>(num_pairs), joints = static_cast<size_t>(NumJoints());
+    // (a tree without joints: one double stands in, so that the kernel has an address it never reads)
+    const double none = 0.0;
+    // (nine outputs and four inputs, and a staging holds eight arrays: two of them, the second inside the first one's
+    // body; the per-pair output goes with the inputs)
+    vgt::HostStaging inputs;
+    const auto xyzr = inputs.In(sphere_xyzr, s * 4);
+    const auto link = inputs.In(sphere_link, s);
+    const auto list = inputs.In(pairs, p * 2);
+    const auto source = !from_joints ? inputs.In(link_poses, b * static_cast<size_t>(num_links) * 16)
+                        : joints > 0 ? inputs.In(joint_values, b * joints)
+                                     : inputs.In(&none, 1);
+    const auto pair_clearance = inputs.Out(out.pair_clearance, num_spheres > 0 ? b * p : 0);
+    return inputs.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+      vgt::HostStaging outputs;
+      const auto status = outputs.Out(out.status, b);
+      const auto num_below = outputs.Out(out.num_below, b);
+      const auto num_without_value = outputs.Out(out.num_without_value, b);
+      const auto min_clearance = outputs.Out(out.min_clearance, b);
+      const auto min_pair = outputs.Out(out.min_pair, b);
+      const auto min_direction = outputs.Out(out.min_direction, b * 3);
+      const auto joint_gradient = outputs.Out(out.joint_gradient, b * joints);
+      const auto fk_status = outputs.Out(out.fk_status, b);
+      return outputs.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+        const vgt::SelfCollisionOutputs out_dev{status.dev(),        num_below.dev(),     num_without_value.dev(),
+                                                min_clearance.dev(), min_pair.dev(),      min_direction.dev(),
+                                                joint_gradient.dev(), fk_status.dev(),    pair_clearance.dev()};
+        return HipResult(what, Enqueue(xyzr.dev(), link.dev(), list.dev(), source.dev(), out_dev, stream));
+      });
+    });
+  }
+};
+}  // namespace
+
+int32_t vgt_hip_self_collision_tile_samples(int64_t num_links, int64_t num_spheres)
+{
+  return vgt::SelfCollisionTileSamples(num_links, num_spheres);
+}
+
+int vgt_hip_check_self_collision_dev(vgt_hip_ctx* ctx, const double* sphere_xyzr_dev, const int32_t* sphere_link_dev,
+                                     int64_t num_spheres, const int32_t* pairs_dev, int64_t num_pairs,
+                                     const vgt_hip_kinematics* tree, const double* joint_values_dev,
+                                     int64_t num_configurations, const double* world_from_base,
+                                     const double* joint_limits, double minimum_clearance, uint32_t flags,
+                                     uint8_t* status_dev, int32_t* num_below_dev, int32_t* num_without_value_dev,
+                                     double* min_clearance_dev, int32_t* min_pair_dev, double* min_direction_dev,
+                                     double* joint_gradient_dev, uint8_t* fk_status_dev, double* pair_clearance_dev)
+{
+  SelfCollisionArguments a{sphere_xyzr_dev, sphere_link_dev, num_spheres, pairs_dev, num_pairs, tree, joint_values_dev,
+                           nullptr, true, num_configurations, 0, world_from_base, joint_limits, minimum_clearance, flags,
+                           {status_dev, num_below_dev, num_without_value_dev, min_clearance_dev, min_pair_dev,
+                            min_direction_dev, joint_gradient_dev, fk_status_dev, pair_clearance_dev}};
+  return a.RunOnDevice(ctx);
+}
+
+int vgt_hip_check_self_collision(vgt_hip_ctx* ctx, const double* sphere_xyzr_host, const int32_t* sphere_link_host,
+                                 int64_t num_spheres, const int32_t* pairs_host, int64_t num_pairs,
+                                 const vgt_hip_kinematics* tree, const double* joint_values_host,
+                                 int64_t num_configurations, const double* world_from_base, const double* joint_limits,
+                                 double minimum_clearance, uint32_t flags, uint8_t* status_host, int32_t* num_below_host,
+                                 int32_t* num_without_value_host, double* min_clearance_host, int32_t* min_pair_host,
+                                 double* min_direction_host, double* joint_gradient_host, uint8_t* fk_status_host,
+                                 double* pair_clearance_host)
+{
+  SelfCollisionArguments a{sphere_xyzr_host, sphere_link_host, num_spheres, pairs_host, num_pairs, tree,
+                           joint_values_host, nullptr, true, num_configurations, 0, world_from_base, joint_limits,
+                           minimum_clearance, flags,
+                           {status_host, num_below_host, num_without_value_host, min_clearance_host, min_pair_host,
+                            min_direction_host, joint_gradient_host, fk_status_host, pair_clearance_host}};
+  return a.RunFromHost(ctx);
+}
+
+int vgt_hip_check_self_collision_poses_dev(vgt_hip_ctx* ctx, const double* sphere_xyzr_dev,
+                                           const int32_t* sphere_link_dev, int64_t num_spheres, const int32_t* pairs_dev,
+                                           int64_t num_pairs, const double* link_poses_dev, int64_t num_configurations,
+                                           int64_t num_links, const vgt_hip_kinematics* tree, double minimum_clearance,
+                                           uint32_t flags, uint8_t* status_dev, int32_t* num_below_dev,
+                                           int32_t* num_without_value_dev, double* min_clearance_dev,
+                                           int32_t* min_pair_dev, double* min_direction_dev, double* joint_gradient_dev,
+                                           double* pair_clearance_dev)
+{
+  SelfCollisionArguments a{sphere_xyzr_dev, sphere_link_dev, num_spheres, pairs_dev, num_pairs, tree, nullptr,
+                           link_poses_dev, false, num_configurations, num_links, nullptr, nullptr, minimum_clearance,
+                           flags,
+                           {status_dev, num_below_dev, num_without_value_dev, min_clearance_dev, min_pair_dev,
+                            min_direction_dev, joint_gradient_dev, nullptr, pair_clearance_dev}};
+  return a.RunOnDevice(ctx);
+}
+
+int vgt_hip_check_self_collision_poses(vgt_hip_ctx* ctx, const double* sphere_xyzr_host, const int32_t* sphere_link_host,
+                                       int64_t num_spheres, const int32_t* pairs_host, int64_t num_pairs,
+                                       const double* link_poses_host, int64_t num_configurations, int64_t num_links,
+                                       const vgt_hip_kinematics* tree, double minimum_clearance, uint32_t flags,
+                                       uint8_t* status_host, int32_t* num_below_host, int32_t* num_without_value_host,
+                                       double* min_clearance_host, int32_t* min_pair_host, double* min_direction_host,
+                                       double* joint_gradient_host, double* pair_clearance_host)
+{
+  SelfCollisionArguments a{sphere_xyzr_host, sphere_link_host, num_spheres, pairs_host, num_pairs, tree, nullptr,
+                           link_poses_host, false, num_configurations, num_links, nullptr, nullptr, minimum_clearance,
+                           flags,
+                           {status_host, num_below_host, num_without_value_host, min_clearance_host, min_pair_host,
+                            min_direction_host, joint_gradient_host, nullptr, pair_clearance_host}};
+  return a.RunFromHost(ctx);
+}
+
+int vgt_hip_self_collision_pairs(const int32_t* sphere_link, int64_t num_spheres, const int32_t* parent,
+                                 int64_t num_links, const int32_t* ignored_link_pairs, int64_t num_ignored,
+                                 uint32_t flags, int32_t* pairs_out, int64_t capacity, int64_t* count)
+{
+  if (!count || (num_spheres > 0 && !sphere_link) || (num_ignored > 0 && !ignored_link_pairs) ||
+      (capacity > 0 && !pairs_out))
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_spheres < 0 || num_links < 0 || num_ignored < 0 || capacity < 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                "the numbers of spheres, links and ignored pairs and the capacity must not be negative");
+  if ((flags & ~VGT_HIP_SELF_PAIRS_SKIP_ADJACENT) != 0)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown self-collision pair flag");
+  if (num_spheres > 0x7fffffffLL)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "self-collision pairs support fewer than 2^31 spheres");
+  for (int64_t s = 0; s < num_spheres; s++)
+    if (sphere_link[s] < 0 || sphere_link[s] >= num_links)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(s) + ": link " +
+                                                    std::to_string(sphere_link[s]) + " is not in [0, num_links)");
+  for (int64_t i = 0; parent && i < num_links; i++)
+    if (parent[i] < -1 || parent[i] >= num_links)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "link " + std::to_string(i) + ": parent " + std::to_string(parent[i]) +
+                                                    " is not in [-1, num_links)");
+  // the ignored pairs as sorted keys low * L + high
+  std::vector<int64_t> ignored;
+  ignored.reserve(static_cast<size_t>(num_ignored));
+  for (int64_t i = 0; i < num_ignored; i++)
+  {
+    const int64_t first = ignored_link_pairs[2 * i], second = ignored_link_pairs[2 * i + 1];
+    for (const int64_t link : {first, second})
+      if (link < 0 || link >= num_links)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "ignored pair " + std::to_string(i) + ": link " +
+                                                      std::to_string(link) + " is not in [0, num_links)");
+    ignored.push_back(std::min(first, second) * num_links + std::max(first, second));
+  }
+  std::sort(ignored.begin(), ignored.end());
+  const bool skip_adjacent = (flags & VGT_HIP_SELF_PAIRS_SKIP_ADJACENT) != 0 && parent != nullptr;
+  int64_t found = 0;
+  for (int64_t a = 0; a < num_spheres; a++)
+    for (int64_t b = a + 1; b < num_spheres; b++)
+    {
+      const int64_t la = sphere_link[a], lb = sphere_link[b];
+      if (la == lb) continue;
+      if (skip_adjacent && (parent[la] == lb || parent[lb] == la)) continue;
+      if (!ignored.empty() &&
+          std::binary_search(ignored.begin(), ignored.end(), std::min(la, lb) * num_links + std::max(la, lb)))
+        continue;
+      if (found < capacity)
+      {
+        pairs_out[2 * found] = static_cast<int32_t>(a);
+        pairs_out[2 * found + 1] = static_cast<int32_t>(b);
+      }
+      found++;
+    }
+  *count = found;
+  return VGT_HIP_OK;
 }
 
 }  // extern "C"

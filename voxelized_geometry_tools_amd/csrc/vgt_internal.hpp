@@ -652,6 +652,44 @@ hipError_t LaunchClearanceCost(const float* sdf_dev, int64_t nx, int64_t ny, int
                                const double* world_from_base_host, const double* limits_dev, double margin,
                                const CostOutputs& out, int max_workgroups, hipStream_t stream);
 
+// --- launcher (self_collision_kernels.hip): self-collision of a sphere model over a list of sphere pairs ---
+// The definition of every output: include/vgt_hip.h, vgt_hip_check_self_collision.  status is required, every other
+// output may be nullptr.
+struct SelfCollisionOutputs
+{
+  uint8_t* status;
+  int32_t* num_below;
+  int32_t* num_without_value;
+  double* min_clearance;
+  int32_t* min_pair;
+  double* min_direction;   // [B][3]
+  double* joint_gradient;  // [B][J]; needs the tree's links
+  uint8_t* fk_status;      // the joint-value form only
+  double* pair_clearance;  // [B][P]
+};
+// What a launch may take of dynamic LDS (what it gets without an attribute), and what a link and a sphere take of it per
+// configuration of a tile: the twelve used elements of a pose, the three of a centre.  Beside them a launch holds 8 B
+// per sphere (the radii) and 256 B (min_pair).
+constexpr size_t kSelfLdsLimit = 64 * 1024, kSelfPoseBytesPerLink = 96, kSelfCentreBytes = 24;
+// The configurations of a tile for a tree of so many links carrying so many spheres: the largest power of two T <= 64
+// whose poses and centres, (96 L + 24 S) T bytes, stay within the build's VGT_SELF_TILE_BYTES (16 KiB), 1 where two
+// configurations exceed that; 0: no links, or one configuration does not fit the LDS of a launch
+// (96 L + 32 S + 256 > 64 KiB).
+int SelfCollisionTileSamples(int64_t num_links, int64_t num_spheres);
+// Fewer than 2^31 spheres, pairs, configurations and (configuration, joint / link) pairs; a shape
+// SelfCollisionTileSamples takes.  Model, pairs, joint values or link poses and outputs on the device.  Exactly one of
+// joint_values_dev (with links_dev; world_from_base_host [16] or nullptr; limits_dev [J][2] or nullptr) and
+// link_poses_dev ([B][L][16]; links_dev may be nullptr when out.joint_gradient is) is given -- for a tree without joints
+// joint_values_dev is any address, never read, and link_poses_dev nullptr selects the form.  max_workgroups: 0 = the
+// launcher's own limit (vgt_hip_testing_set_self_collision_workgroups).
+hipError_t LaunchSelfCollision(const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                               const int32_t* pairs_dev, int64_t num_pairs, const KinematicLink* links_dev,
+                               int64_t num_links, int64_t num_joints, const double* joint_values_dev,
+                               const double* link_poses_dev, int64_t num_configurations,
+                               const double* world_from_base_host, const double* limits_dev, double minimum_clearance,
+                               int no_value_is_collision, const SelfCollisionOutputs& out, int max_workgroups,
+                               hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
