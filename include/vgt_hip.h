@@ -285,6 +285,19 @@ int vgt_hip_testing_set_motion_workgroups(int workgroups);
 /* The same for the launches of vgt_hip_clearance_cost[_dev] (one workgroup per tile of configurations), so that a few
  * hundred configurations already make its persistent waves stride. */
 int vgt_hip_testing_set_cost_workgroups(int workgroups);
+/* What a launch of vgt_hip_check_motions[_dev] for a tree of num_links links and a model of num_spheres spheres is made
+ * of, computed by the function the launcher itself takes it from: the samples of a tile (vgt_hip_motion_tile_samples)
+ * and whether the sphere table sits in LDS (1) or is read through the cache (0).  Lets the tests pick shapes on both
+ * sides of that choice whatever the kernel's constants are.  VGT_HIP_ERR_INVALID_ARGUMENT: a NULL output, a negative
+ * sphere count, or a tree the kernel does not take. */
+int vgt_hip_testing_motion_launch_geometry(int64_t num_links, int64_t num_spheres, int32_t* tile_samples,
+                                           int32_t* table_in_lds);
+/* The same for vgt_hip_clearance_cost[_dev], in the gradient form (gradient_form != 0: joint_gradient or
+ * num_without_gradient is asked for) or the cost-only form: the configurations of a tile (vgt_hip_cost_tile_samples),
+ * the passes of phase B buffered in front of phase C, and whether the sphere table and what the walk reads of the links
+ * sit in LDS (1) or are read through the cache (0). */
+int vgt_hip_testing_cost_launch_geometry(int64_t num_links, int64_t num_spheres, int gradient_form, int32_t* tile_samples,
+                                         int32_t* passes, int32_t* table_in_lds, int32_t* links_in_lds);
 /* The same for the launches of vgt_hip_check_self_collision[_poses][_dev] (one workgroup per tile of configurations). */
 int vgt_hip_testing_set_self_collision_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to

@@ -7,7 +7,8 @@ joint values uniform in +-1 with planted rows -- a NaN, an infinity, a value bey
 0.25; arm-21 also runs with 2^-30, 1000 and a margin equal to a clearance that occurs (the `d == eps` edge), and once with
 the radius of a sphere set to the bits of its own estimate in configuration 3, whose clearance is then exactly 0 there:
 the order of `d < 0` and `d <= eps` decides the bits.  Sphere counts sit on both sides of the segment width 64 (64, 65, 70)
-and of the kernel's sphere table (257 > 256).  Every second case passes joint limits.
+and of the kernel's sphere table (257 > 256).  Every second case passes joint limits.  The cases of FRAMED, appended,
+run under a grid turned about a general axis and shifted.
 
 coverage() states what the cases must hit, so that none passes by hitting nothing; tests/test_cost_ref.py asserts it."""
 import collections
@@ -20,6 +21,7 @@ import body_cases
 import cost_ref
 import kinematics_cases
 import motion_cases
+import projection_cases
 
 NUM_CONFIGURATIONS = 67
 RESOLUTION = body_cases.RESOLUTION
@@ -60,15 +62,29 @@ def _cases():
 
 
 CASES = _cases()
+# appended (the tests take cases by index, and index % 2 steers the limits): under the frame of
+# tests/projection_cases.general_frame_pair() -- the grid turned about a general axis and shifted, grid_from_world and
+# rotation passed, the tree on world_from_grid * world_from_base, so that it stays in the same part of the scene --
+# arm-65-odd (several slices with the resting sums; its index is odd: with limits), arm-21 and the branching tree.  Every
+# other case passes neither (None).
+FRAMED = frozenset(range(len(CASES), len(CASES) + 3))
+CASES += [
+    ("arm", 65, True, NUM_CONFIGURATIONS, MARGIN, False),
+    ("arm", 21, False, NUM_CONFIGURATIONS, MARGIN, False),
+    ("body", 9, True, NUM_CONFIGURATIONS, MARGIN, False),
+]
+assert min(FRAMED) % 2 == 1
 
 Case = collections.namedtuple(
-    "Case", "name tree sdf xyzr link joint_values margin world_from_base joint_limits spheres want")
+    "Case", "name tree sdf xyzr link joint_values margin world_from_base joint_limits spheres want grid_from_world rotation")
 
 
 def names():
     out = []
-    for tree, s, odd, b, margin, radius in CASES:
+    for index, (tree, s, odd, b, margin, radius) in enumerate(CASES):
         name = "%s-%d%s" % (tree, s, "-odd" if odd else "")
+        if index in FRAMED:
+            name += "-frame"
         if b != NUM_CONFIGURATIONS:
             name += "-B%d" % b
         if margin != MARGIN:
@@ -106,9 +122,13 @@ def case(index):
     q = joint_values(num, tree.num_joints)
     limits = kinematics_cases.limits(tree.num_joints) if index % 2 == 1 else None
     base = motion_cases.world_from_base()
+    grid_from_world = rotation = None
+    if index in FRAMED:
+        grid_from_world, rotation, world_from_grid = projection_cases.general_frame_pair()
+        base = projection_cases.base_under(world_from_grid, base)
 
     def spheres_at(eps):
-        return cost_ref.spheres(O, sdf, RESOLUTION, xyzr, link, tree, q, eps, None, None, base, limits)
+        return cost_ref.spheres(O, sdf, RESOLUTION, xyzr, link, tree, q, eps, grid_from_world, rotation, base, limits)
 
     if planted_radius:
         # the estimate itself: the clearance of a sphere of radius 0; the first sphere whose estimate in configuration 3
@@ -127,9 +147,10 @@ def case(index):
     want = cost_ref.reduce_spheres(tree, xyzr, link, per_sphere)
     if planted_radius:
         assert per_sphere.clearance[3, s] == 0.0 and not np.signbit(per_sphere.clearance[3, s])
-    for a in [xyzr, link, q, base] + list(per_sphere) + list(want) + ([limits] if limits is not None else []):
+    optional = [a for a in (limits, grid_from_world, rotation) if a is not None]
+    for a in [xyzr, link, q, base] + list(per_sphere) + list(want) + optional:
         a.setflags(write=False)
-    return Case(names()[index], tree, sdf, xyzr, link, q, margin, base, limits, per_sphere, want)
+    return Case(names()[index], tree, sdf, xyzr, link, q, margin, base, limits, per_sphere, want, grid_from_world, rotation)
 
 
 def coverage(index):

@@ -2,7 +2,8 @@
 // (the hinge and the ordered sums, over per-sphere values) against answers derived by hand on a two-link tree, and the
 // argument errors.  With a device: ClearanceCost against the hand-made answers and against that restatement over the
 // per-sphere values of CheckSphereModel from joint values, with ClearanceJointGradient's summed form on the poses of
-// ComputeLinkPoses for the gradient, bit for bit.
+// ComputeLinkPoses for the gradient, bit for bit; then all of it once more with the grid on a turned and shifted origin
+// and the tree's base on that origin, against the identity grid's run.
 //
 // The hand-made scene (that of test_motion_host.cc).  Field: 8 x 4 x 4 cells of resolution 1, sdf[x][y][z] = x + 1.5: the
 // estimate at a point p with 0.5 <= p_x <= 7.5 is p_x + 0.5 and its gradient (1, 0, 0).  Tree: link 0 prismatic along x at
@@ -173,10 +174,18 @@ static SphereModel TwoSpheres()
   return model;
 }
 
-static SignedDistanceField Ramp()
+// A grid origin turned by 0.7 about (0.3, -0.5, 0.8) -- an axis that is none of x, y, z: no entry of the rotation is near
+// 0 or +-1 -- and shifted.
+static Isometry3 TurnedOrigin()
+{
+  const double s = std::sin(0.35) / std::sqrt(0.3 * 0.3 + 0.5 * 0.5 + 0.8 * 0.8);
+  return Isometry3::FromQuaternion(std::cos(0.35), 0.3 * s, -0.5 * s, 0.8 * s, 0.4, -0.2, 0.05);
+}
+
+static SignedDistanceField Ramp(const Isometry3& origin = Isometry3::Identity())
 {
   SignedDistanceField sdf;
-  sdf.grid = DenseGrid(Isometry3::Identity(), "f", 1.0, 8, 4, 4, 0.0f);
+  sdf.grid = DenseGrid(origin, "f", 1.0, 8, 4, 4, 0.0f);
   for (int64_t x = 0; x < 8; x++)
     for (int64_t y = 0; y < 4; y++)
       for (int64_t z = 0; z < 4; z++) sdf.grid.SetIndex(x, y, z, static_cast<float>(x) + 1.5f);
@@ -279,66 +288,114 @@ static int RunDevice()
 {
   const KinematicTree tree = TwoLinks();
   const SphereModel model = TwoSpheres();
-  const SignedDistanceField sdf = Ramp();
+  const SignedDistanceField identity_sdf = Ramp();
+  const Isometry3 origin = TurnedOrigin();
   // 70 configurations of the hand-made scene at multiples of 0.5, on both sides of the grid's ends and of the margin
   std::vector<double> q;
   for (int b = 0; b < 70; b++) q.push_back(0.5 * ((b * 7) % 23) - 2.0);
   q[11] = std::numeric_limits<double>::quiet_NaN();
   q[12] = std::numeric_limits<double>::infinity();
-  for (int variant = 0; variant < 4; variant++)
+  // The second pass: the ramp on the turned and shifted origin and the tree's base on that origin, so that the tree is
+  // where it was in the grid.  The comparisons with the layer's other calls stay bit for bit; the answers by hand give
+  // way to the identity grid's run of the same call, which they hold.  There the margins are off the lattice of the
+  // clearances (multiples of 0.25): a clearance equal to the margin has w == +0.0 and is not active, and the rounding of
+  // the two more transforms would decide on which side of it the turned run lands.
+  for (int turned = 0; turned < 2; turned++)
   {
-    const double margin = (variant & 1) ? 2.0 : 4.0;  // (clearances start at 1: a smaller margin has no active sphere)
-    ClearanceCostOptions options;
-    if (variant >= 2) options.joint_limits = {0.0, 6.0};
-    const ClearanceCosts got = ClearanceCost(sdf, model, tree, q, margin, options);
-    CHECK(got.cost.size() == 70 && got.joint_gradient.size() == 70 && got.num_active.size() == 70);
-    CHECK(got.num_outside.size() == 70 && got.num_without_gradient.size() == 70 && got.fk_status.size() == 70);
-    options.with_gradient = false;
-    const ClearanceCosts scored = ClearanceCost(sdf, model, tree, q, margin, options);
-    CHECK(scored.joint_gradient.empty() && scored.num_without_gradient.empty() && scored.cost.size() == 70);
-
-    // the layer's calls that exist without this one
-    JointSphereModelOptions flat_options;
-    flat_options.per_sphere = true;
-    flat_options.joint_limits = options.joint_limits;
-    const JointSphereModelChecks flat = CheckSphereModel(sdf, model, tree, q, flat_options);
-    const LinkPoses poses = ComputeLinkPoses(tree, q, 70, nullptr, options.joint_limits);
-    std::vector<double> weights;
-    std::vector<restated::Configuration> reduced;
-    for (size_t b = 0; b < 70; b++)
+    const SignedDistanceField sdf = turned ? Ramp(origin) : identity_sdf;
+    int compared = 0, on_an_end_face = 0;
+    for (int variant = 0; variant < 4; variant++)
     {
-      reduced.push_back(restated::Reduce(&flat.checks.sphere_clearance[2 * b], &flat.checks.sphere_gradient[6 * b], 2, margin));
-      weights.insert(weights.end(), reduced.back().weight.begin(), reduced.back().weight.end());
-    }
-    const std::vector<double> summed = ClearanceJointGradient(tree, poses.link_poses, model, weights, flat.checks.sphere_gradient);
-    int active = 0, outside = 0;
-    for (size_t b = 0; b < 70; b++)
-    {
-      const bool in_hand_range = std::isnan(q[b]) || std::isinf(q[b]) || (q[b] >= 0.5 && q[b] <= 6.5) || q[b] > 7.5 || q[b] < -1.5;
-      const restated::Hand hand = restated::HandConfiguration(q[b], margin, options.joint_limits.empty() ? nullptr : options.joint_limits.data());
-      const restated::Configuration& want = reduced[b];
-      const bool same = SameDouble(got.cost[b], want.cost) && SameDouble(got.joint_gradient[b], summed[b]) &&
-                        got.num_active[b] == want.num_active && got.num_outside[b] == want.num_outside &&
-                        got.num_without_gradient[b] == want.num_without_gradient && got.fk_status[b] == flat.fk_status[b];
-      // (the formulas at the head of this file hold where both spheres are well inside the grid, or both outside)
-      const bool same_as_hand = !in_hand_range ||
-                                (SameDouble(got.cost[b], hand.reduced.cost) && SameDouble(got.joint_gradient[b], hand.joint_gradient) &&
-                                 got.num_active[b] == hand.reduced.num_active && got.num_outside[b] == hand.reduced.num_outside &&
-                                 got.fk_status[b] == hand.fk_status);
-      if (!same || !same_as_hand)
+      // (clearances start at 1: a smaller margin has no active sphere)
+      const double margin = ((variant & 1) ? 2.0 : 4.0) + (turned ? 0.125 : 0.0);
+      ClearanceCostOptions options;
+      if (variant >= 2) options.joint_limits = {0.0, 6.0};
+      const ClearanceCostOptions plain_options = options;
+      if (turned)
       {
-        std::printf("  configuration %zu (q %g) variant %d: cost %g/%g/%g gradient %g/%g/%g active %d/%d outside %d/%d fk %d/%d\n",
-                    b, q[b], variant, got.cost[b], want.cost, hand.reduced.cost, got.joint_gradient[b], summed[b],
-                    hand.joint_gradient, got.num_active[b], want.num_active, got.num_outside[b], want.num_outside,
-                    got.fk_status[b], flat.fk_status[b]);
-        CHECK(false);
+        options.has_world_from_base = true;
+        options.world_from_base = origin;
       }
-      CHECK(SameDouble(scored.cost[b], got.cost[b]) && scored.num_active[b] == got.num_active[b] &&
-            scored.num_outside[b] == got.num_outside[b] && scored.fk_status[b] == got.fk_status[b]);
-      active += got.num_active[b];
-      outside += got.num_outside[b];
+      const ClearanceCosts got = ClearanceCost(sdf, model, tree, q, margin, options);
+      CHECK(got.cost.size() == 70 && got.joint_gradient.size() == 70 && got.num_active.size() == 70);
+      CHECK(got.num_outside.size() == 70 && got.num_without_gradient.size() == 70 && got.fk_status.size() == 70);
+      options.with_gradient = false;
+      const ClearanceCosts scored = ClearanceCost(sdf, model, tree, q, margin, options);
+      CHECK(scored.joint_gradient.empty() && scored.num_without_gradient.empty() && scored.cost.size() == 70);
+
+      // the layer's calls that exist without this one
+      JointSphereModelOptions flat_options;
+      flat_options.per_sphere = true;
+      flat_options.joint_limits = options.joint_limits;
+      flat_options.has_world_from_base = options.has_world_from_base;
+      flat_options.world_from_base = options.world_from_base;
+      const JointSphereModelChecks flat = CheckSphereModel(sdf, model, tree, q, flat_options);
+      const LinkPoses poses = ComputeLinkPoses(tree, q, 70, turned ? &origin : nullptr, options.joint_limits);
+      std::vector<double> weights;
+      std::vector<restated::Configuration> reduced;
+      for (size_t b = 0; b < 70; b++)
+      {
+        reduced.push_back(restated::Reduce(&flat.checks.sphere_clearance[2 * b], &flat.checks.sphere_gradient[6 * b], 2, margin));
+        weights.insert(weights.end(), reduced.back().weight.begin(), reduced.back().weight.end());
+      }
+      const std::vector<double> summed = ClearanceJointGradient(tree, poses.link_poses, model, weights, flat.checks.sphere_gradient);
+      // the same call on the identity grid
+      const ClearanceCosts plain = turned ? ClearanceCost(identity_sdf, model, tree, q, margin, plain_options) : got;
+      int active = 0, outside = 0;
+      for (size_t b = 0; b < 70; b++)
+      {
+        const bool in_hand_range = std::isnan(q[b]) || std::isinf(q[b]) || (q[b] >= 0.5 && q[b] <= 6.5) || q[b] > 7.5 || q[b] < -1.5;
+        const restated::Hand hand = restated::HandConfiguration(q[b], margin, options.joint_limits.empty() ? nullptr : options.joint_limits.data());
+        const restated::Configuration& want = reduced[b];
+        const bool same = SameDouble(got.cost[b], want.cost) && SameDouble(got.joint_gradient[b], summed[b]) &&
+                          got.num_active[b] == want.num_active && got.num_outside[b] == want.num_outside &&
+                          got.num_without_gradient[b] == want.num_without_gradient && got.fk_status[b] == flat.fk_status[b];
+        // (the formulas at the head of this file hold where both spheres are well inside the grid, or both outside)
+        const bool same_as_hand = turned || !in_hand_range ||
+                                  (SameDouble(got.cost[b], hand.reduced.cost) && SameDouble(got.joint_gradient[b], hand.joint_gradient) &&
+                                   got.num_active[b] == hand.reduced.num_active && got.num_outside[b] == hand.reduced.num_outside &&
+                                   got.fk_status[b] == hand.fk_status);
+        if (!same || !same_as_hand)
+        {
+          std::printf("  configuration %zu (q %g) variant %d turned %d: cost %g/%g/%g gradient %g/%g/%g active %d/%d outside %d/%d fk %d/%d\n",
+                      b, q[b], variant, turned, got.cost[b], want.cost, hand.reduced.cost, got.joint_gradient[b], summed[b],
+                      hand.joint_gradient, got.num_active[b], want.num_active, got.num_outside[b], want.num_outside,
+                      got.fk_status[b], flat.fk_status[b]);
+          CHECK(false);
+        }
+        CHECK(SameDouble(scored.cost[b], got.cost[b]) && scored.num_active[b] == got.num_active[b] &&
+              scored.num_outside[b] == got.num_outside[b] && scored.fk_status[b] == got.fk_status[b]);
+        active += got.num_active[b];
+        outside += got.num_outside[b];
+        if (!turned) continue;
+        // A sphere centre on an end face of the grid in x (the spheres are at q + 1 and q) is inside or outside by the
+        // rounding of the transforms; every other configuration is the identity grid's, up to that rounding.
+        if (q[b] == -1.0 || q[b] == 0.0 || q[b] == 7.0 || q[b] == 8.0)
+        {
+          on_an_end_face++;
+          continue;
+        }
+        compared++;
+        const auto close = [](double a, double b) {
+          return (std::isnan(a) && std::isnan(b)) || a == b || std::fabs(a - b) <= 1e-12;
+        };
+        const bool as_plain = close(got.cost[b], plain.cost[b]) && close(got.joint_gradient[b], plain.joint_gradient[b]) &&
+                              got.num_active[b] == plain.num_active[b] && got.num_outside[b] == plain.num_outside[b] &&
+                              got.num_without_gradient[b] == plain.num_without_gradient[b] &&
+                              got.fk_status[b] == plain.fk_status[b];
+        if (!as_plain)
+        {
+          std::printf("  configuration %zu (q %g) variant %d, turned/identity: cost %.17g/%.17g gradient %.17g/%.17g active %d/%d outside %d/%d fk %d/%d\n",
+                      b, q[b], variant, got.cost[b], plain.cost[b], got.joint_gradient[b], plain.joint_gradient[b],
+                      got.num_active[b], plain.num_active[b], got.num_outside[b], plain.num_outside[b], got.fk_status[b],
+                      plain.fk_status[b]);
+          CHECK(false);
+        }
+      }
+      CHECK(active > 0 && outside > 0);
     }
-    CHECK(active > 0 && outside > 0);
+    // per variant the 12 configurations with q in {-1, 0, 7, 8}
+    if (turned) CHECK(on_an_end_face == 4 * 12 && compared == 4 * (70 - 12));
   }
   return g_failures;
 }

@@ -558,6 +558,41 @@ static int RunDevice()
     int statuses[3] = {0, 0, 0};
     for (uint8_t v : checks.status) statuses[v]++;
     CHECK(statuses[0] + statuses[1] > 50 && statuses[1] > 0);
+
+    // The same field on an origin turned by 0.7 about (0.3, -0.5, 0.8) -- an axis that is none of x, y, z -- and shifted,
+    // the base moved with it: the chained call against the two steps under that grid (test_body_host.cc holds
+    // CheckSphereModel on given poses under a turned grid to its restatement).
+    const double s = std::sin(0.35) / std::sqrt(0.3 * 0.3 + 0.5 * 0.5 + 0.8 * 0.8);
+    const Isometry3 turn = Isometry3::FromQuaternion(std::cos(0.35), 0.3 * s, -0.5 * s, 0.8 * s, 0.4, -0.2, 0.05);
+    SignedDistanceField turned_sdf;
+    turned_sdf.grid = DenseGrid(turn, "f", 0.125, 11, 9, 13, 0.0f);
+    for (int64_t x = 0; x < 11; x++)
+      for (int64_t y = 0; y < 9; y++)
+        for (int64_t z = 0; z < 13; z++) turned_sdf.grid.SetIndex(x, y, z, sdf.grid.GetIndexImmutable(x, y, z));
+    const Isometry3 turned_base = turn * base;
+    const LinkPoses turned_poses = ComputeLinkPoses(tree, q, num, &turned_base, limits);
+    const SphereModelChecks turned_checks = CheckSphereModel(turned_sdf, model, turned_poses.link_poses, 11, step_options);
+    const std::vector<double> turned_worst = ClearanceJointGradient(tree, turned_poses.link_poses, model, turned_checks);
+    options.per_sphere = options.joint_gradient = true;
+    options.world_from_base = turned_base;
+    const JointSphereModelChecks turned_chained = CheckSphereModel(turned_sdf, model, tree, q, options);
+    CHECK(SameBytes(turned_chained.checks.status, turned_checks.status));
+    CHECK(SameBytes(turned_chained.checks.min_sphere, turned_checks.min_sphere));
+    CHECK(SameBytes(turned_chained.checks.num_below, turned_checks.num_below));
+    CHECK(SameBytes(turned_chained.checks.num_outside, turned_checks.num_outside));
+    CHECK(SameDoubles(turned_chained.checks.min_clearance, turned_checks.min_clearance));
+    CHECK(SameDoubles(turned_chained.checks.min_gradient, turned_checks.min_gradient));
+    CHECK(SameDoubles(turned_chained.checks.sphere_clearance, turned_checks.sphere_clearance));
+    CHECK(SameDoubles(turned_chained.checks.sphere_gradient, turned_checks.sphere_gradient));
+    CHECK(SameBytes(turned_chained.fk_status, turned_poses.status) && SameDoubles(turned_chained.joint_gradient, turned_worst));
+    // (the scene is the same one: most configurations keep their status, and the gradients are other vectors)
+    int same_status = 0, other_gradient = 0;
+    for (size_t b = 0; b < checks.status.size(); b++)
+    {
+      same_status += turned_checks.status[b] == checks.status[b] ? 1 : 0;
+      other_gradient += std::fabs(turned_checks.min_gradient[3 * b] - checks.min_gradient[3 * b]) > 1e-3 ? 1 : 0;
+    }
+    CHECK(same_status > 135 && other_gradient > 50);
   }
   return g_failures;
 }

@@ -1,7 +1,8 @@
 // CheckMotions of the C++ host layer (include/vgt_hip/motion_queries.hpp).  --no-device: the restatement in this file
 // (interpolation and the reduction per motion, over per-sample values) against answers derived by hand on a two-link
 // tree, and the argument errors.  With a device: CheckMotions against that restatement over the per-sample values of
-// CheckSphereModel from joint values, bit for bit, with and without the stop flag.
+// CheckSphereModel from joint values, bit for bit, with and without the stop flag; then all of it once more with the
+// grid on a turned and shifted origin and the tree's base on that origin, against the identity grid's run.
 //
 // The hand-made scene (tests/test_motion_ref.py has the same one).  Field: 8 x 4 x 4 cells of resolution 1,
 // sdf[x][y][z] = x + 1.5: the estimate at a point p with 0.5 <= p_x <= 7.5 is p_x + 0.5.  Tree: link 0 prismatic along x
@@ -190,10 +191,18 @@ static SphereModel TwoSpheres()
   return model;
 }
 
-static SignedDistanceField Ramp()
+// A grid origin turned by 0.7 about (0.3, -0.5, 0.8) -- an axis that is none of x, y, z: no entry of the rotation is near
+// 0 or +-1 -- and shifted.
+static Isometry3 TurnedOrigin()
+{
+  const double s = std::sin(0.35) / std::sqrt(0.3 * 0.3 + 0.5 * 0.5 + 0.8 * 0.8);
+  return Isometry3::FromQuaternion(std::cos(0.35), 0.3 * s, -0.5 * s, 0.8 * s, 0.4, -0.2, 0.05);
+}
+
+static SignedDistanceField Ramp(const Isometry3& origin = Isometry3::Identity())
 {
   SignedDistanceField sdf;
-  sdf.grid = DenseGrid(Isometry3::Identity(), "f", 1.0, 8, 4, 4, 0.0f);
+  sdf.grid = DenseGrid(origin, "f", 1.0, 8, 4, 4, 0.0f);
   for (int64_t x = 0; x < 8; x++)
     for (int64_t y = 0; y < 4; y++)
       for (int64_t z = 0; z < 4; z++) sdf.grid.SetIndex(x, y, z, static_cast<float>(x) + 1.5f);
@@ -343,44 +352,101 @@ static int RunDevice()
   }
   from[11] = std::numeric_limits<double>::quiet_NaN();
   to[12] = std::numeric_limits<double>::infinity();
-  for (int variant = 0; variant < 4; variant++)
+  // The second pass: the ramp on the turned and shifted origin and the tree's base on that origin, so that the tree is
+  // where it was in the grid.  The comparison with the layer's per-sample call stays bit for bit; the answers by hand
+  // give way to the identity grid's run of the same call, which they hold.  There the threshold is off the lattice of
+  // the clearances (multiples of 0.25): the rounding of the two more transforms would decide on which side of `<=` a
+  // sample with a clearance equal to the threshold lands.
+  const Isometry3 origin = TurnedOrigin();
+  for (int turned = 0; turned < 2; turned++)
   {
-    MotionOptions options;
-    options.minimum_clearance = 2.0;
-    options.stop_at_collision = (variant & 1) != 0;
-    options.outside_is_collision = (variant & 2) != 0;
-    if (variant >= 2) options.joint_limits = {0.0, 6.0};
-    const std::vector<MotionCheck> got = CheckMotions(sdf, model, tree, from, to, steps, options);
-    CHECK(got.size() == 70);
-    int statuses[3] = {0, 0, 0};
-    for (size_t e = 0; e < got.size(); e++)
+    const SignedDistanceField grid = turned ? Ramp(origin) : sdf;
+    int compared = 0, on_an_end_face = 0;
+    for (int variant = 0; variant < 4; variant++)
     {
-      // by hand
-      const MotionCheck hand = restated::HandMotion(from[e], to[e], steps[e], options);
-      if (!Same(got[e], hand))
+      MotionOptions options;
+      options.minimum_clearance = turned ? 2.125 : 2.0;
+      options.stop_at_collision = (variant & 1) != 0;
+      options.outside_is_collision = (variant & 2) != 0;
+      if (variant >= 2) options.joint_limits = {0.0, 6.0};
+      const MotionOptions plain_options = options;
+      if (turned)
       {
-        std::printf("  motion %zu variant %d: status %d/%d first %d/%d sample %d/%d clearance %g/%g fk %d/%d\n", e, variant,
-                    got[e].status, hand.status, got[e].first_collision, hand.first_collision, got[e].min_sample,
-                    hand.min_sample, got[e].min_clearance, hand.min_clearance, got[e].fk_status, hand.fk_status);
-        CHECK(false);
+        options.has_world_from_base = true;
+        options.world_from_base = origin;
       }
-      // the per-sample call of the layer, reduced here
-      const std::vector<double> q = restated::Interpolate(&from[e], &to[e], 1, steps[e]);
-      JointSphereModelOptions sample_options;
-      sample_options.minimum_clearance = options.minimum_clearance;
-      sample_options.outside_is_collision = options.outside_is_collision;
-      sample_options.joint_limits = options.joint_limits;
-      const JointSphereModelChecks flat = CheckSphereModel(sdf, model, tree, q, sample_options);
-      std::vector<restated::Sample> samples;
-      for (size_t k = 0; k < q.size(); k++)
-        samples.push_back({flat.checks.status[k], flat.checks.min_clearance[k], flat.checks.min_sphere[k],
-                           {flat.checks.min_gradient[3 * k], flat.checks.min_gradient[3 * k + 1],
-                            flat.checks.min_gradient[3 * k + 2]},
-                           flat.fk_status[k]});
-      CHECK(Same(got[e], restated::Reduce(samples, options.stop_at_collision)));
-      if (got[e].status < 3) statuses[got[e].status]++;
+      const std::vector<MotionCheck> got = CheckMotions(grid, model, tree, from, to, steps, options);
+      CHECK(got.size() == 70);
+      // the same call on the identity grid
+      const std::vector<MotionCheck> plain = turned ? CheckMotions(sdf, model, tree, from, to, steps, plain_options) : got;
+      CHECK(plain.size() == 70);
+      int statuses[3] = {0, 0, 0};
+      for (size_t e = 0; e < got.size(); e++)
+      {
+        // by hand
+        const MotionCheck hand = restated::HandMotion(from[e], to[e], steps[e], options);
+        if (!turned && !Same(got[e], hand))
+        {
+          std::printf("  motion %zu variant %d: status %d/%d first %d/%d sample %d/%d clearance %g/%g fk %d/%d\n", e, variant,
+                      got[e].status, hand.status, got[e].first_collision, hand.first_collision, got[e].min_sample,
+                      hand.min_sample, got[e].min_clearance, hand.min_clearance, got[e].fk_status, hand.fk_status);
+          CHECK(false);
+        }
+        // the per-sample call of the layer, reduced here
+        const std::vector<double> q = restated::Interpolate(&from[e], &to[e], 1, steps[e]);
+        JointSphereModelOptions sample_options;
+        sample_options.minimum_clearance = options.minimum_clearance;
+        sample_options.outside_is_collision = options.outside_is_collision;
+        sample_options.joint_limits = options.joint_limits;
+        sample_options.has_world_from_base = options.has_world_from_base;
+        sample_options.world_from_base = options.world_from_base;
+        const JointSphereModelChecks flat = CheckSphereModel(grid, model, tree, q, sample_options);
+        std::vector<restated::Sample> samples;
+        for (size_t k = 0; k < q.size(); k++)
+          samples.push_back({flat.checks.status[k], flat.checks.min_clearance[k], flat.checks.min_sphere[k],
+                             {flat.checks.min_gradient[3 * k], flat.checks.min_gradient[3 * k + 1],
+                              flat.checks.min_gradient[3 * k + 2]},
+                             flat.fk_status[k]});
+        CHECK(Same(got[e], restated::Reduce(samples, options.stop_at_collision)));
+        if (got[e].status < 3) statuses[got[e].status]++;
+        if (!turned) continue;
+        // A sphere centre on an end face of the grid in x (the spheres are at q + 1 and q) is inside or outside by the
+        // rounding of the transforms; every motion without such a sample is the identity grid's, up to that rounding,
+        // and its gradient the identity grid's turned by the origin's rotation.
+        bool end_face = false;
+        for (const double value : q) end_face = end_face || value == -1.0 || value == 0.0 || value == 7.0 || value == 8.0;
+        if (end_face)
+        {
+          on_an_end_face++;
+          continue;
+        }
+        compared++;
+        const auto close = [](double a, double b) {
+          return (std::isnan(a) && std::isnan(b)) || a == b || std::fabs(a - b) <= 1e-12;
+        };
+        bool as_plain = got[e].status == plain[e].status && got[e].first_collision == plain[e].first_collision &&
+                        got[e].min_sample == plain[e].min_sample && got[e].min_sphere == plain[e].min_sphere &&
+                        got[e].fk_status == plain[e].fk_status && close(got[e].min_clearance, plain[e].min_clearance);
+        for (int r = 0; r < 3; r++)
+        {
+          const double* g = plain[e].min_gradient.data();
+          as_plain = as_plain && close(got[e].min_gradient[r], (origin(r, 0) * g[0] + origin(r, 1) * g[1]) + origin(r, 2) * g[2]);
+        }
+        if (!as_plain)
+        {
+          std::printf("  motion %zu variant %d, turned/identity: status %d/%d first %d/%d sample %d/%d sphere %d/%d clearance %.17g/%.17g fk %d/%d gradient (%g %g %g)/(%g %g %g)\n",
+                      e, variant, got[e].status, plain[e].status, got[e].first_collision, plain[e].first_collision,
+                      got[e].min_sample, plain[e].min_sample, got[e].min_sphere, plain[e].min_sphere, got[e].min_clearance,
+                      plain[e].min_clearance, got[e].fk_status, plain[e].fk_status, got[e].min_gradient[0],
+                      got[e].min_gradient[1], got[e].min_gradient[2], plain[e].min_gradient[0], plain[e].min_gradient[1],
+                      plain[e].min_gradient[2]);
+          CHECK(false);
+        }
+      }
+      CHECK(statuses[0] > 0 && statuses[1] > 0 && (variant >= 2 || statuses[2] > 0));
     }
-    CHECK(statuses[0] > 0 && statuses[1] > 0 && (variant >= 2 || statuses[2] > 0));
+    // per variant the 31 motions that have a sample with q in {-1, 0, 7, 8}
+    if (turned) CHECK(on_an_end_face == 4 * 31 && compared == 4 * (70 - 31));
   }
   // one count for all motions
   {

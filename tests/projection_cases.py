@@ -72,6 +72,31 @@ def frame_pair():
     return grid_from_world.T.reshape(16).copy(), rotation.reshape(9).copy(), world_from_grid
 
 
+def general_frame_pair():
+    """The same three as frame_pair() for an origin transform whose rotation is about an axis that is none of x, y, z:
+    (0.3, -0.5, 0.8) normalised, by 0.7 (Rodrigues' formula), so that every entry of `rotation` is far from 0 and +-1 and
+    a transposed, dropped or swapped rotation changes every component; the same translation."""
+    axis = np.array([0.3, -0.5, 0.8])
+    axis /= np.linalg.norm(axis)
+    k = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]])
+    rotation = np.eye(3) + np.sin(0.7) * k + (1.0 - np.cos(0.7)) * (k @ k)
+    assert (np.abs(rotation) >= 0.05).all() and (np.abs(rotation) <= 0.95).all(), rotation
+    world_from_grid = np.eye(4)
+    world_from_grid[:3, :3] = rotation
+    world_from_grid[:3, 3] = [0.4, -0.2, 0.05]
+    grid_from_world = np.eye(4)
+    grid_from_world[:3, :3] = rotation.T
+    grid_from_world[:3, 3] = -(rotation.T @ world_from_grid[:3, 3])
+    return grid_from_world.T.reshape(16).copy(), rotation.reshape(9).copy(), world_from_grid
+
+
+def base_under(world_from_grid, world_from_base):
+    """world_from_grid * world_from_base, both ways of writing a transform: a 4x4 matrix times 16 doubles column-major ->
+    16 doubles column-major.  A tree on this base moves through the same part of the grid as before the frame."""
+    base = np.asarray(world_from_base, dtype=np.float64).reshape(4, 4).T
+    return (world_from_grid @ base).T.reshape(16).copy()
+
+
 def to_world(points, world_from_grid):
     with np.errstate(invalid="ignore"):                     # (the cloud's NaN and infinite points)
         return points @ world_from_grid[:3, :3].T + world_from_grid[:3, 3]

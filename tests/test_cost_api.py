@@ -156,3 +156,32 @@ def test_tile_samples(lib):
     assert steps == [2, 3, 5, 9, 17, 33]
     for links in steps:
         assert t(links - 1) == 2 * t(links) and 96 * (links - 1) * t(links - 1) <= 6 * 1024 < 96 * links * t(links - 1)
+
+
+def test_launch_geometry_hook(lib):
+    """vgt_hip_testing_cost_launch_geometry: in the testing library only; its tile is vgt_hip_cost_tile_samples, the passes
+    are a power of two within the tile, the cost-only form has no links in LDS, few links and spheres sit in LDS and many
+    do not, and what the launcher refuses the hook refuses."""
+    name = "vgt_hip_testing_cost_launch_geometry"
+    text = open(os.path.join(ROOT, "include", "vgt_hip.h")).read()
+    testing_section = text[text.index("#ifdef VGT_HIP_TESTING"):text.index("#endif /* VGT_HIP_TESTING */")]
+    assert name in testing_section and name in capi.TESTING_SIGNATURES and name not in capi.SIGNATURES
+    assert hasattr(ctypes.CDLL(capi.TESTING_LIB_PATH), name) and not hasattr(ctypes.CDLL(capi.LIB_PATH), name)
+    g = capi.cost_launch_geometry
+    for links in (1, 8, 33, 463, 512):
+        for spheres in (0, 1, 5, 64, 65, 257):
+            for gradient in (True, False):
+                got = g(links, spheres, gradient)
+                assert got.tile_samples == capi.cost_tile_samples(links)
+                assert got.passes >= 1 and got.passes & (got.passes - 1) == 0 and got.passes <= max(got.tile_samples, 1)
+                assert gradient or not got.links_in_lds
+                assert spheres <= 256 or not got.table_in_lds
+    assert g(8, 21, True) == (capi.cost_tile_samples(8), g(8, 21, True).passes, 1, 1)
+    assert g(512, 5, True).links_in_lds == 0
+    for links, spheres in ((513, 5), (0, 5), (8, -1)):
+        with pytest.raises(ValueError):
+            g(links, spheres)
+    out = [ctypes.c_int32(7) for _ in range(3)]
+    testing = capi.load(testing=True)
+    rc = testing.vgt_hip_testing_cost_launch_geometry(8, 5, 1, None, *[ctypes.byref(o) for o in out])
+    assert rc == 1 and [o.value for o in out] == [7, 7, 7]

@@ -1,6 +1,7 @@
 """(not gpu) tests/cost_ref.py, the restatement vgt_hip_clearance_cost is compared against: the hinge at its edges, its
 continuity and w = dc/dd; the composition -- spheres without a weight are skipped, the NaN-gradient rule and its count,
-a model without spheres; and the coverage of tests/cost_cases.py, so that no case passes by hitting nothing."""
+a model without spheres; the restatement under a turned grid against itself without one; and the coverage of
+tests/cost_cases.py, so that no case passes by hitting nothing."""
 import numpy as np
 import pytest
 
@@ -109,6 +110,67 @@ def test_a_model_without_spheres():
     assert want.fk_status.any()
 
 
+def agree(got, want, bound, undefined_rows=None):
+    """NaNs and infinities in the same places (the infinities with their signs), everything else within `bound`; -> the
+    largest difference.  In the rows of `undefined_rows` (a mask) a value that is not finite is only held to be not
+    finite on both sides."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape
+    finite = np.isfinite(want)
+    assert np.array_equal(np.isfinite(got), finite)
+    strict = ~finite
+    if undefined_rows is not None:
+        strict = strict & ~np.asarray(undefined_rows, dtype=bool).reshape((-1,) + (1,) * (got.ndim - 1))
+    assert np.array_equal(np.isnan(got[strict]), np.isnan(want[strict]))
+    infinite = strict & ~np.isnan(want)
+    assert np.array_equal(got[infinite], want[infinite])
+    worst = float(np.abs(got[finite] - want[finite]).max()) if finite.any() else 0.0
+    assert worst <= bound, worst
+    return worst
+
+
+@pytest.mark.parametrize("name", ["arm-21", "arm-64-odd", "arm-257-odd", "body-9-odd"])
+def test_the_restatement_under_a_turned_grid(name):
+    """The restatement under tests/projection_cases.general_frame_pair(), held to itself without a frame: the grid turned
+    and shifted and the tree with it (world_from_grid * world_from_base) is the same scene, so every sphere has the same
+    cell and the same clearance up to the rounding of two more transforms, its gradient is the plain one turned into the
+    world (g * rotation^T for a row vector g), and the joint gradient -- a derivative with respect to the joints --
+    does not depend on the frame.  No configuration and no sphere is left out.  A frame applied the wrong way round, or
+    a gradient left in the grid's frame, moves these values by 1e-3 or more.
+
+    One thing does depend on the frame, and only on the fields with infinite cells: an active sphere whose gradient has
+    an infinite component.  It is no NaN gradient, so it keeps its weight; its terms are then +-infinity, and whether
+    their sum is an infinity or a NaN depends on their signs.  Turned, the gradient is infinite in all three components
+    (no entry of the rotation is 0), so the signs differ from the plain ones: in body-9-odd 17 joint-gradient entries in
+    7 configurations are an infinity on one side and a NaN on the other.  Neither is a value.  In exactly the
+    configurations that have such a sphere the joint gradient is therefore held to be finite in the same places and
+    within the bound there; everywhere else NaNs and infinities are in the same places too."""
+    from oracle import oracle as O
+    import projection_cases
+    case = C.case(C.names().index(name))
+    assert case.grid_from_world is None and case.rotation is None
+    grid_from_world, rotation, world_from_grid = projection_cases.general_frame_pair()
+    base = projection_cases.base_under(world_from_grid, case.world_from_base)
+    turned = R.spheres(O, case.sdf, C.RESOLUTION, case.xyzr, case.link, case.tree, case.joint_values, case.margin,
+                       grid_from_world, rotation, base, case.joint_limits)
+    got = R.reduce_spheres(case.tree, case.xyzr, case.link, turned)
+    want = case.want
+    for field in ("num_active", "num_outside", "num_without_gradient", "fk_status"):
+        assert np.array_equal(getattr(got, field), getattr(want, field)), field
+    g = case.spheres.gradient
+    undefined = ((case.spheres.w != 0.0) & np.isinf(g).any(axis=2) & ~np.isnan(g).any(axis=2)).any(axis=1)
+    assert not undefined.any() or name.endswith("-odd")
+    print(name, "configurations with an active sphere of infinite gradient:", np.flatnonzero(undefined).tolist())
+    worst = [agree(got.cost, want.cost, 1e-9), agree(got.joint_gradient, want.joint_gradient, 1e-9, undefined)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = rotation.reshape(3, 3)
+        rotated = np.stack([(g[..., 0] * r[i, 0] + g[..., 1] * r[i, 1]) + g[..., 2] * r[i, 2] for i in range(3)], axis=-1)
+    worst.append(agree(turned.gradient, rotated, 1e-12))
+    worst.append(agree(turned.clearance, case.spheres.clearance, 1e-12))
+    print(name, "largest differences: cost %g, joint gradient %g, turned gradients %g, clearances %g" % tuple(worst))
+    assert want.num_active.any() and np.isfinite(want.joint_gradient).any() and want.joint_gradient[np.isfinite(want.joint_gradient)].any()
+
+
 def test_cases_cover_what_they_claim():
     names = C.names()
     assert len(set(names)) == len(names)
@@ -120,6 +182,14 @@ def test_cases_cover_what_they_claim():
         total_outside += outside
         total_without_gradient += without_gradient
         moving = kinematics_cases.tree(tree).num_joints > 0
+        if index in C.FRAMED:
+            # the frame cases: all three hinge branches, under a grid_from_world and a rotation that are there
+            assert below > 0 and inside > 0 and beyond > 0, names[index]
+            framed = C.case(index)
+            assert framed.grid_from_world is not None and framed.rotation is not None
+            if (tree, s, odd) == ("arm", 65, True):
+                assert framed.want.num_without_gradient.sum() > 0 and framed.want.num_outside.sum() > 0
+                assert framed.joint_limits is not None and (framed.want.fk_status & 2).any()
         if margin == C.MARGIN and s >= 5 and moving and b == C.NUM_CONFIGURATIONS:
             assert below > 0 and inside > 0 and beyond > 0, names[index]
         if margin == C.EDGE:

@@ -3,7 +3,11 @@ position) on the shared cases of tests/cost_cases.py -- through the host form of
 form on torch buffers through the testing library limited to two workgroups, so that 67 configurations make the
 persistent waves stride.  Then the cost-only form, the optional outputs, the GPU entry points that exist without this
 call (check_spheres_from_joints, a numpy hinge, the summed clearance_joint_gradient), in the device form links outside
-the tree and a model without spheres, trees at the kernel's limits, and the argument errors that need a tree."""
+the tree and a model without spheres, trees at the kernel's limits, and the argument errors that need a tree.
+
+The cases of cost_cases.FRAMED pass a grid_from_world and a rotation (a turn about a general axis), in both forms; one
+test passes the first without the second.  The links the gradient's walk reads are run on both sides of the kernel's
+LDS, the shapes chosen by the launcher's own geometry (capi.cost_launch_geometry)."""
 import numpy as np
 import pytest
 
@@ -60,6 +64,7 @@ def assert_same(got, want, what, fields=FIELDS):
 
 def host_form(context, tree, case, **kw):
     return context.clearance_cost(case.sdf, C.RESOLUTION, case.xyzr, case.link, tree, case.joint_values, case.margin,
+                                  grid_from_world=case.grid_from_world, rotation=case.rotation,
                                   world_from_base=case.world_from_base, joint_limits=case.joint_limits, **kw)
 
 
@@ -86,7 +91,8 @@ def device_form(context, tree, case, without=(), num_spheres=None):
     pointers = {name + "_ptr": None if name in without else out[name].data_ptr() for name in out if name != "cost"}
     context.clearance_cost_dev(dev[0].data_ptr(), case.sdf.shape, C.RESOLUTION, dev[1].data_ptr(), dev[2].data_ptr(),
                                len(case.link) if num_spheres is None else num_spheres, tree, dev[3].data_ptr(), num,
-                               case.margin, out["cost"].data_ptr(), world_from_base=case.world_from_base,
+                               case.margin, out["cost"].data_ptr(), grid_from_world=case.grid_from_world,
+                               rotation=case.rotation, world_from_base=case.world_from_base,
                                joint_limits=case.joint_limits, **pointers)
     context.synchronize()
     got = []
@@ -121,7 +127,8 @@ def test_device_form_with_striding_waves(few_workgroups, index):
     assert_same(got, case.want, case.name)
 
 
-COST_ONLY = [name for name in C.names() if name in ("arm-21", "arm-70", "arm-257-odd", "body-9-odd", "arm-0", "fixed1-2")]
+COST_ONLY = [name for name in C.names() if name in ("arm-21", "arm-70", "arm-257-odd", "body-9-odd", "arm-0", "fixed1-2",
+                                                    "arm-65-odd-frame")]
 
 
 @pytest.mark.parametrize("name", COST_ONLY)
@@ -166,14 +173,15 @@ def test_outputs_passed_as_null_stay_untouched(few_workgroups):
             assert same_bits(getattr(some, name), getattr(case.want, name)), name
 
 
-@pytest.mark.parametrize("name", ["arm-70", "arm-64-odd"])
+@pytest.mark.parametrize("name", ["arm-70", "arm-64-odd", "arm-65-odd-frame"])
 def test_equals_the_calls_that_exist_without_it(ctx, name):
     """Context.check_spheres_from_joints for every sphere's clearance and gradient, the hinge in numpy, the summed form of
     Context.clearance_joint_gradient on the poses of Context.forward_kinematics: bit for bit."""
     case = C.case(C.names().index(name))
     with make_tree(ctx, case.tree) as tree:
         flat = ctx.check_spheres_from_joints(case.sdf, C.RESOLUTION, case.xyzr, case.link, tree, case.joint_values,
-                                             per_sphere=True, world_from_base=case.world_from_base,
+                                             per_sphere=True, grid_from_world=case.grid_from_world,
+                                             rotation=case.rotation, world_from_base=case.world_from_base,
                                              joint_limits=case.joint_limits)
         poses, fk_status = ctx.forward_kinematics(tree, case.joint_values, world_from_base=case.world_from_base,
                                                   joint_limits=case.joint_limits)
@@ -197,7 +205,7 @@ def test_equals_the_calls_that_exist_without_it(ctx, name):
                                (~value).sum(axis=1).astype(np.int32), without_gradient.sum(axis=1).astype(np.int32),
                                np.asarray(fk_status, dtype=np.uint8))
     assert_same(got, want, case.name)
-    assert without_gradient.any() == (name == "arm-64-odd")        # (the NaN-gradient rule is part of one of the two)
+    assert without_gradient.any() == (name != "arm-70")            # (the NaN-gradient rule is part of the odd ones)
 
 
 def test_device_form_with_links_outside_the_tree_and_without_spheres(few_workgroups):
@@ -246,6 +254,83 @@ def test_trees_at_the_kernels_limits(ctx):
             got = ctx.clearance_cost(sdf, C.RESOLUTION, xyzr, link, tree, q, C.MARGIN, world_from_base=base)
         print("chain of", links, "cost", got.cost.tolist(), "active", got.num_active.tolist())
         assert_same(got, want, "chain-%d" % links)
+
+
+def long_chain(links, spheres):
+    """A chain of so many links carrying so many spheres, and B = 3 rows of small joint values (the chain stays in the
+    grid) from the first seed for which the restatement has active spheres and a joint gradient that is not zero in at
+    least two of the three configurations: a shape whose spheres are all beyond the margin would test nothing.
+    -> (tree, xyzr, link, q, want)"""
+    from oracle import oracle as O
+    sdf = body_cases.field(False)
+    base = C.motion_cases.world_from_base()
+    t = kinematics_cases.tree("chain-%d" % links)
+    xyzr, link = kinematics_cases.sphere_model(t, spheres, 31)
+    for seed in range(links, links + 32):
+        q = (np.random.default_rng(seed).random((3, t.num_joints)) * 2.0 - 1.0) * 0.05
+        want = R.clearance_cost(O, sdf, C.RESOLUTION, xyzr, link, t, q, C.MARGIN, world_from_base=base)
+        if ((want.num_active > 0) & (want.joint_gradient != 0.0).any(axis=1)).sum() >= 2:
+            return t, xyzr, link, q, want
+    raise AssertionError("no seed with active spheres for a chain of %d links" % links)
+
+
+def assert_long_chain(ctx, links, spheres):
+    """Both forms of the kernel on long_chain(links, spheres) against the restatement."""
+    sdf = body_cases.field(False)
+    base = C.motion_cases.world_from_base()
+    t, xyzr, link, q, want = long_chain(links, spheres)
+    with make_tree(ctx, t) as tree:
+        got = ctx.clearance_cost(sdf, C.RESOLUTION, xyzr, link, tree, q, C.MARGIN, world_from_base=base)
+        scored = ctx.clearance_cost(sdf, C.RESOLUTION, xyzr, link, tree, q, C.MARGIN, world_from_base=base,
+                                    with_gradient=False)
+    print("chain of", links, "with", spheres, "spheres:", capi.cost_launch_geometry(links, spheres, True),
+          capi.cost_launch_geometry(links, spheres, False), "active", got.num_active.tolist(), "cost", got.cost.tolist())
+    assert_same(got, want, "chain-%d" % links)
+    assert scored.joint_gradient is None and scored.num_without_gradient is None
+    assert_same(scored, want, "chain-%d, cost only" % links, ("cost", "num_active", "num_outside", "fk_status"))
+
+
+def test_the_links_on_both_sides_of_the_lds(ctx):
+    """What the walk reads of the links, behind the poses of a long chain: the greatest L the launcher still puts into LDS
+    in the gradient form at S = 5, by its own geometry, one link more -- which the walk reads through the cache -- and
+    the longest chain the kernel takes."""
+    spheres = 5
+    in_lds = [n for n in range(1, 513) if capi.cost_launch_geometry(n, spheres, True).links_in_lds]
+    most = max(in_lds)
+    assert in_lds == list(range(1, most + 1)) and most < 512
+    assert not capi.cost_launch_geometry(most, spheres, False).links_in_lds          # (the cost-only form has no walk)
+    for links in (most, most + 1, 512):
+        assert_long_chain(ctx, links, spheres)
+
+
+def test_fewer_buffered_passes_than_the_tile_has_room_for(ctx):
+    """Shapes whose launch buffers fewer passes than the build's limit although the tile has configurations for more,
+    because the buffer would not fit next to the poses: S >= 64, so that a pass is one configuration, and every L.  They
+    are found with the launcher's own geometry; the longest such chain runs against the restatement.  With the shipped
+    constants (tiles of more than one configuration have at most 6 KiB of poses, and four passes take 17 KiB) there is
+    none, and the loop of the launcher that halves the passes never turns: this test then only says so."""
+    spheres = 70
+    limit = max(capi.cost_launch_geometry(n, spheres, True).passes for n in range(1, 513))
+    found = [n for n in range(1, 513) for g in [capi.cost_launch_geometry(n, spheres, True)]
+             if g.passes < limit and g.passes < g.tile_samples]
+    print("buffered passes at the most:", limit, "; chains whose launch has fewer than its tile has room for:", found)
+    if found:
+        assert_long_chain(ctx, max(found), spheres)
+
+
+def test_the_two_frame_arguments_are_not_interchangeable(ctx):
+    """grid_from_world of the frame and no rotation, against the restatement called the same way, bit for bit: the
+    gradients stay in the grid's frame, so the joint gradient is another one than the frame case's."""
+    from oracle import oracle as O
+    case = C.case(C.names().index("arm-21-frame"))
+    want = R.clearance_cost(O, case.sdf, C.RESOLUTION, case.xyzr, case.link, case.tree, case.joint_values, case.margin,
+                            case.grid_from_world, None, case.world_from_base, case.joint_limits)
+    with make_tree(ctx, case.tree) as tree:
+        got = host_form(ctx, tree, case._replace(rotation=None))
+    assert_same(got, want, case.name + " without the rotation")
+    assert_same(got, case.want, case.name, ("cost", "num_active", "num_outside", "num_without_gradient", "fk_status"))
+    finite = np.isfinite(want.joint_gradient) & np.isfinite(case.want.joint_gradient)
+    assert np.abs(want.joint_gradient[finite] - case.want.joint_gradient[finite]).max() > 1e-3
 
 
 def test_argument_errors_that_need_a_tree(ctx):

@@ -2,7 +2,8 @@
 CPU restatement: poses, status and both gradient forms bit-equal (NaNs by position) on the shared cases of
 tests/kinematics_cases.py -- through the host forms of the product library, the device forms on torch buffers, and the
 testing library limited to two workgroups, so that 257 configurations make the persistent waves stride.  Then the
-optional outputs, the consumers on the forward kinematics' own device output, and the chained call."""
+optional outputs, the consumers on the forward kinematics' own device output, and the chained call -- without a grid
+frame, under a grid turned about a general axis, and with the grid's transform but not its rotation."""
 import numpy as np
 import pytest
 
@@ -10,6 +11,7 @@ import body_cases
 import body_ref
 import kinematics_cases as C
 import kinematics_ref as R
+import projection_cases
 import volume_ref
 from voxelized_geometry_tools_amd import capi
 
@@ -206,21 +208,27 @@ def test_consumers_take_the_device_output_as_it_stands(ctx):
     assert same_bits(cells.cpu().numpy(), want_cells)
 
 
-@pytest.mark.parametrize("per_sphere", [False, True])
-def test_chained_call_equals_the_two_steps(ctx, per_sphere):
+def chained_call(ctx, per_sphere, frame):
+    """check_spheres_from_joints against forward_kinematics, check_spheres and clearance_joint_gradient in turn; frame:
+    (grid_from_world, rotation, world_from_grid) of the grid's origin, the arm's base moved with it, or None."""
     t, q, base, xyzr, link = _scene()
     sdf = body_cases.field(True)
     limits = C.limits(t.num_joints)
+    grid_from_world = rotation = None
+    if frame is not None:
+        grid_from_world, rotation, world_from_grid = frame
+        base = projection_cases.base_under(world_from_grid, base)
+    grid = dict(grid_from_world=grid_from_world, rotation=rotation)
     with make_tree(ctx, t) as tree:
         got = ctx.check_spheres_from_joints(sdf, body_cases.RESOLUTION, xyzr, link, tree, q, minimum_clearance=0.05,
                                             outside_is_collision=True, per_sphere=per_sphere, world_from_base=base,
-                                            joint_limits=limits, joint_gradient=True)
+                                            joint_limits=limits, joint_gradient=True, **grid)
         poses, fk_status = ctx.forward_kinematics(tree, q, base, limits)
-        checks = ctx.check_spheres(sdf, body_cases.RESOLUTION, xyzr, link, poses, 0.05, True, per_sphere=per_sphere)
+        checks = ctx.check_spheres(sdf, body_cases.RESOLUTION, xyzr, link, poses, 0.05, True, per_sphere=per_sphere, **grid)
         gradient = ctx.clearance_joint_gradient(tree, poses, xyzr, link, min_sphere=checks.min_sphere,
                                                 min_gradient=checks.min_gradient)
         plain = ctx.check_spheres_from_joints(sdf, body_cases.RESOLUTION, xyzr, link, tree, q, minimum_clearance=0.05,
-                                              outside_is_collision=True, world_from_base=base)
+                                              outside_is_collision=True, world_from_base=base, **grid)
         none = ctx.check_spheres_from_joints(sdf, body_cases.RESOLUTION, xyzr, link, tree, q[:0], joint_gradient=True)
     for name in capi.SphereChecks._fields:
         g, w = getattr(got, name), getattr(checks, name)
@@ -230,3 +238,62 @@ def test_chained_call_equals_the_two_steps(ctx, per_sphere):
     assert plain.joint_gradient is None and plain.sphere_clearance is None and same_bits(plain.status, checks.status)
     assert plain.fk_status.tolist() == (fk_status & 1).tolist()
     assert none.status.shape == (0,) and none.fk_status.shape == (0,) and none.joint_gradient.shape == (0, t.num_joints)
+    return got
+
+
+@pytest.mark.parametrize("per_sphere", [False, True])
+def test_chained_call_equals_the_two_steps(ctx, per_sphere):
+    chained_call(ctx, per_sphere, None)
+
+
+@pytest.mark.parametrize("per_sphere", [False, True])
+def test_chained_call_under_a_turned_grid(ctx, per_sphere):
+    """The same under tests/projection_cases.general_frame_pair(), and directly against the two restatements under the
+    frame: every output of the check bit-equal, the joint gradient the restatement's worst-sphere form."""
+    from oracle import oracle as O
+    frame = projection_cases.general_frame_pair()
+    got = chained_call(ctx, per_sphere, frame)
+    t, q, base, xyzr, link = _scene()
+    base = projection_cases.base_under(frame[2], base)
+    want_poses, want_status = R.forward_kinematics(t, q, base, C.limits(t.num_joints))
+    want = body_ref.check_spheres(O, body_cases.field(True), body_cases.RESOLUTION, xyzr, link, want_poses, 0.05, True,
+                                  frame[0], frame[1])
+    for name in capi.SphereChecks._fields:
+        if per_sphere or not name.startswith("sphere_"):
+            assert same_bits(getattr(got, name), getattr(want, name)), name
+    assert same_bits(got.fk_status, want_status)
+    assert same_bits(got.joint_gradient, R.clearance_joint_gradient(t, want_poses, xyzr, link, min_sphere=want.min_sphere,
+                                                                    min_gradient=want.min_gradient))
+    print("statuses", np.bincount(got.status, minlength=3).tolist(), "finite gradient rows",
+          int(np.isfinite(got.min_gradient).all(axis=1).sum()))
+    assert len(set(got.status.tolist())) > 1 and np.isfinite(got.min_gradient).all(axis=1).any()
+
+
+def test_the_two_frame_arguments_are_not_interchangeable(ctx):
+    """grid_from_world of the frame and no rotation: the same cells, so clearances, statuses, counts and indices are those
+    under the frame bit for bit, and the gradients stay in the grid's frame -- those under the frame turned back
+    (g * rotation for a row vector g), within 1e-12: another order of operations, so not bit for bit."""
+    t, q, base, xyzr, link = _scene()
+    grid_from_world, rotation, world_from_grid = projection_cases.general_frame_pair()
+    base = projection_cases.base_under(world_from_grid, base)
+    sdf = body_cases.field(True)
+    r = rotation.reshape(3, 3)
+    with make_tree(ctx, t) as tree:
+        both, one = [ctx.check_spheres_from_joints(sdf, body_cases.RESOLUTION, xyzr, link, tree, q, minimum_clearance=0.05,
+                                                   outside_is_collision=True, per_sphere=True, world_from_base=base,
+                                                   grid_from_world=grid_from_world, rotation=turn)
+                     for turn in (rotation, None)]
+    for name in ("status", "min_clearance", "min_sphere", "num_below", "num_outside", "sphere_clearance", "fk_status"):
+        assert same_bits(getattr(one, name), getattr(both, name)), name
+    for name in ("min_gradient", "sphere_gradient"):
+        g = getattr(both, name)
+        with np.errstate(invalid="ignore", over="ignore"):
+            back = np.stack([(g[..., 0] * r[0, i] + g[..., 1] * r[1, i]) + g[..., 2] * r[2, i] for i in range(3)], axis=-1)
+        # (a gradient with an infinite component is infinite in all three under the frame, and turning it back adds
+        # infinities of both signs: only what is finite on both sides has a value to compare)
+        finite = np.isfinite(back) & np.isfinite(getattr(one, name))
+        worst = float(np.abs(getattr(one, name)[finite] - back[finite]).max())
+        moved = float(np.abs(getattr(one, name)[finite] - g[finite]).max())
+        print(name, "finite entries", int(finite.sum()), "of", finite.size, "largest difference", worst,
+              "and from the turned gradients", moved)
+        assert finite.sum() * 2 > finite.size and worst <= 1e-12 and moved > 1e-3

@@ -4,7 +4,11 @@ host form of the product library, and the device form on torch buffers through t
 workgroups, so that 67 motions make the persistent waves stride.  Then the code that exists without this call
 (check_spheres_from_joints on the samples, reduced by the restatement's reduction), the optional outputs, an invalid
 step count in the device form, trees at the kernel's limits, the argument errors that need a tree, and in the device
-form links outside the tree and a model without spheres."""
+form links outside the tree and a model without spheres.
+
+The cases of motion_cases.FRAMED pass a grid_from_world and a rotation (a turn about a general axis), in both forms; one
+test passes the first without the second.  The sphere table is run on both sides of the kernel's LDS, the shapes chosen
+by the launcher's own geometry (capi.motion_launch_geometry)."""
 import numpy as np
 import pytest
 
@@ -62,6 +66,7 @@ def assert_same(got, want, what):
 def host_form(context, tree, case, stop):
     return context.check_motions(case.sdf, C.RESOLUTION, case.xyzr, case.link, tree, case.joint_from, case.joint_to,
                                  case.num_steps, case.minimum_clearance, case.outside_is_collision, stop,
+                                 grid_from_world=case.grid_from_world, rotation=case.rotation,
                                  world_from_base=case.world_from_base, joint_limits=case.joint_limits)
 
 
@@ -91,7 +96,8 @@ def device_form(context, tree, case, stop, without=(), num_steps=None, num_spher
                               dev[4].data_ptr(),
                               int(steps) if steps_dev is None else 0, motions, out["status"].data_ptr(),
                               minimum_clearance=case.minimum_clearance, outside_is_collision=case.outside_is_collision,
-                              stop_at_collision=stop, world_from_base=case.world_from_base,
+                              stop_at_collision=stop, grid_from_world=case.grid_from_world, rotation=case.rotation,
+                              world_from_base=case.world_from_base,
                               joint_limits=case.joint_limits,
                               num_steps_ptr=None if steps_dev is None else steps_dev.data_ptr(), **pointers)
     context.synchronize()
@@ -152,7 +158,10 @@ def test_outputs_passed_as_null_stay_untouched(few_workgroups):
             assert same_bits(getattr(some, name), getattr(case.want_stopped, name)), name
 
 
-@pytest.mark.parametrize("index", [0, 3], ids=[C.names()[0], C.names()[3]])
+FIRST_FRAMED = min(C.FRAMED)
+
+
+@pytest.mark.parametrize("index", [0, 3, FIRST_FRAMED], ids=[C.names()[0], C.names()[3], C.names()[FIRST_FRAMED]])
 def test_equals_the_calls_that_exist_without_it(ctx, index):
     """The samples interpolated in numpy, Context.check_spheres_from_joints on them, the restatement's reduction."""
     case = C.case(index)
@@ -161,6 +170,7 @@ def test_equals_the_calls_that_exist_without_it(ctx, index):
         flat = ctx.check_spheres_from_joints(case.sdf, C.RESOLUTION, case.xyzr, case.link, tree, q,
                                              minimum_clearance=case.minimum_clearance,
                                              outside_is_collision=case.outside_is_collision,
+                                             grid_from_world=case.grid_from_world, rotation=case.rotation,
                                              world_from_base=case.world_from_base, joint_limits=case.joint_limits)
         samples = R.Samples(flat.status, flat.min_clearance, flat.min_sphere, flat.min_gradient, flat.fk_status)
         for stop in (False, True):
@@ -206,6 +216,73 @@ def test_trees_at_the_kernels_limits(ctx):
                                     world_from_base=C.world_from_base())
         print("chain of", links, "statuses", got.status.tolist(), "min_sample", got.min_sample.tolist())
         assert_same(got, want, "chain-%d" % links)
+
+
+def test_the_sphere_table_on_both_sides_of_the_lds(ctx):
+    """The table of the model behind 60 KiB of poses: at 640 links the greatest S the launcher still puts into LDS, by its
+    own geometry, and one sphere more, which the kernel reads through the cache; and the models of the shared cases on
+    both sides of the table's own limit.  A chain of 640 links, 5 motions of 0, 1, 2, 3 and 5 steps with joint values of
+    a few thousandths, so that the chain stays in the grid; the threshold lies between the motions' least clearances."""
+    from oracle import oracle as O
+    names = C.names()
+    for name, in_lds in (("arm-70", 1), ("arm-257", 0), ("arm-257-odd-frame", 0)):
+        case = C.case(names.index(name))
+        assert capi.motion_launch_geometry(case.tree.num_links, len(case.xyzr)).table_in_lds == in_lds, name
+    links = 640
+    assert capi.motion_launch_geometry(links, 1).table_in_lds == 1
+    most = max(s for s in range(1, 1024) if capi.motion_launch_geometry(links, s).table_in_lds)
+    assert capi.motion_launch_geometry(links, most + 1).table_in_lds == 0
+    sdf = body_cases.field(False)
+    t = kinematics_cases.tree("chain-%d" % links)
+    steps = np.array([0, 1, 2, 3, 5], dtype=np.int32)
+    rng = np.random.default_rng(links)
+    joint_from = (rng.random((5, t.num_joints)) * 2.0 - 1.0) * 0.004
+    joint_to = joint_from + (rng.random((5, t.num_joints)) * 2.0 - 1.0) * 0.004
+    base = C.world_from_base()
+    with make_tree(ctx, t) as tree:
+        for spheres in (most, most + 1):
+            xyzr, link = kinematics_cases.sphere_model(t, spheres, 31)
+            least = R.check_motions(O, sdf, C.RESOLUTION, xyzr, link, t, joint_from, joint_to, steps,
+                                    world_from_base=base).min_clearance
+            least = np.unique(least[np.isfinite(least)])
+            assert len(least) >= 2
+            threshold = float((least[(len(least) - 1) // 2] + least[(len(least) - 1) // 2 + 1]) * 0.5)
+            second_slice = False
+            for stop in (False, True):
+                want = R.check_motions(O, sdf, C.RESOLUTION, xyzr, link, t, joint_from, joint_to, steps, threshold,
+                                       stop_at_collision=stop, world_from_base=base)
+                got = ctx.check_motions(sdf, C.RESOLUTION, xyzr, link, tree, joint_from, joint_to, steps, threshold,
+                                        stop_at_collision=stop, world_from_base=base)
+                print("chain of", links, "with", spheres, "spheres, stop", stop, "statuses", got.status.tolist(),
+                      "min_sample", got.min_sample.tolist(), "min_sphere", got.min_sphere.tolist())
+                assert_same(got, want, "chain-%d with %d spheres" % (links, spheres))
+                assert len(set(want.status.tolist())) > 1
+                second_slice = second_slice or bool((want.min_sphere >= 64).any())
+            assert second_slice or spheres == most
+
+
+def test_the_two_frame_arguments_are_not_interchangeable(ctx):
+    """grid_from_world of the frame and no rotation: the same cells, so clearances, statuses and indices are the frame
+    case's bit for bit, and min_gradient stays in the grid's frame -- the frame case's turned back (g * rotation for a row
+    vector g), within 1e-12: another order of operations, so not bit for bit.  An entry point that drops one of the two
+    pointers, or swaps them, fails here or in the frame cases."""
+    case = C.case(FIRST_FRAMED)
+    r = case.rotation.reshape(3, 3)
+    with make_tree(ctx, case.tree) as tree:
+        for stop in (False, True):
+            want = case.want_stopped if stop else case.want
+            got = host_form(ctx, tree, case._replace(rotation=None), stop)
+            for name in FIELDS:
+                if name != "min_gradient":
+                    assert same_bits(getattr(got, name), getattr(want, name)), name
+            g = want.min_gradient
+            back = np.stack([(g[:, 0] * r[0, i] + g[:, 1] * r[1, i]) + g[:, 2] * r[2, i] for i in range(3)], axis=-1)
+            finite = np.isfinite(back)
+            assert finite.any() and np.array_equal(np.isfinite(got.min_gradient), finite)
+            worst = float(np.abs(got.min_gradient[finite] - back[finite]).max())
+            moved = float(np.abs(got.min_gradient[finite] - g[finite]).max())
+            print("stop", stop, "largest difference", worst, "and from the turned gradients", moved)
+            assert worst <= 1e-12 and moved > 1e-3
 
 
 def test_argument_errors_that_need_a_tree(ctx):

@@ -153,3 +153,25 @@ def test_tile_samples(lib):
         assert tile <= previous
         previous = tile
     assert t(640) == 1 and lib.vgt_hip_motion_tile_samples(8) == t(8)
+
+
+def test_launch_geometry_hook(lib):
+    """vgt_hip_testing_motion_launch_geometry: in the testing library only; its tile is vgt_hip_motion_tile_samples, the
+    sphere table is in LDS for few spheres and not beyond some count that depends on the links, and what the launcher
+    refuses the hook refuses."""
+    name = "vgt_hip_testing_motion_launch_geometry"
+    text = open(os.path.join(ROOT, "include", "vgt_hip.h")).read()
+    testing_section = text[text.index("#ifdef VGT_HIP_TESTING"):text.index("#endif /* VGT_HIP_TESTING */")]
+    assert name in testing_section and name in capi.TESTING_SIGNATURES and name not in capi.SIGNATURES
+    assert hasattr(ctypes.CDLL(capi.TESTING_LIB_PATH), name) and not hasattr(ctypes.CDLL(capi.LIB_PATH), name)
+    g = capi.motion_launch_geometry
+    for links in (1, 8, 41, 640):
+        assert g(links, 0).tile_samples == capi.motion_tile_samples(links)
+        in_lds = [g(links, s).table_in_lds for s in range(0, 400)]
+        assert in_lds[0] == 1 and in_lds[-1] == 0 and sorted(in_lds, reverse=True) == in_lds, links
+    for links, spheres in ((641, 5), (0, 5), (8, -1)):
+        with pytest.raises(ValueError):
+            g(links, spheres)
+    out = ctypes.c_int32(7)
+    testing = capi.load(testing=True)
+    assert testing.vgt_hip_testing_motion_launch_geometry(8, 5, None, ctypes.byref(out)) == 1 and out.value == 7

@@ -1,11 +1,13 @@
 """tests/motion_ref.py, the CPU restatement of vgt_hip_check_motions, held to answers derived by hand on a two-link tree;
-and the shared cases of tests/motion_cases.py held to what they must contain, so that no GPU test passes by accident.
+the restatement under a turned grid against itself without one; and the shared cases of tests/motion_cases.py held to
+what they must contain, so that no GPU test passes by accident.
 
 The hand-made scene.  Field: 8 x 4 x 4 cells of resolution 1, sdf[x, y, z] = x + 1.5, so that the corrected centre
 distance is x + 1 and the trilinear estimate at a point p with 0.5 <= p_x <= 7.5 is p_x + 0.5; the coarse gradient of an
 inner cell is (1, 0, 0).  Tree: link 0 prismatic along x at (0, 1.5, 1.5), link 1 fixed on it at (1, 0, 0).  Sphere 0: on
 link 1, radius 0.25 (clearance q + 1.25); sphere 1: on link 0, radius 0 (clearance q + 0.5, always the worst)."""
 import numpy as np
+import pytest
 
 import body_ref
 import kinematics_ref
@@ -88,6 +90,68 @@ def test_fk_status_is_the_or_of_the_considered_samples():
 def test_one_sample_when_there_are_no_steps():
     got = run([2.0], [np.nan], 0)
     assert (got.status[0], got.min_sample[0], got.min_clearance[0], got.fk_status[0]) == (R.CLEAR, 0, 2.5, 0)
+
+
+def threshold_off_every_clearance(clearances, quantile):
+    """A minimum_clearance midway between two neighbouring distinct clearances that occur, at the quantile of the sorted
+    distinct finite values (the first pair from there on that is further apart than 1e-6, so that the rounding of two more
+    transforms, 1e-15, puts no sample on the other side); with one value only, 0.01 above it."""
+    values = np.unique(clearances[np.isfinite(clearances)])
+    if len(values) == 1:
+        return float(values[0]) + 0.01
+    at = int(quantile * (len(values) - 1))
+    while values[at + 1] - values[at] <= 1e-6:
+        at += 1
+    return float((values[at] + values[at + 1]) * 0.5)
+
+
+@pytest.mark.parametrize("index", [i for i in range(len(C.CASES)) if i not in C.FRAMED],
+                         ids=[n for i, n in enumerate(C.names()) if i not in C.FRAMED])
+def test_the_restatement_under_a_turned_grid(index):
+    """The restatement under tests/projection_cases.general_frame_pair(), held to itself without a frame: the grid turned
+    and shifted and the tree with it (world_from_grid * world_from_base) is the same scene.  With a threshold that no
+    sample's clearance sits on, every integer output of every motion is equal with and without the stop flag,
+    min_clearance agrees within 1e-9 and min_gradient is the plain one turned into the world (g * rotation^T for a row
+    vector g) within 1e-12.  No motion is left out.  (With the cases' own threshold, a clearance that occurs, a sample on
+    the `<=` edge may legitimately change sides under rounding.)"""
+    import projection_cases
+    case = C.case(index)
+    assert case.grid_from_world is None and case.rotation is None
+    grid_from_world, rotation, world_from_grid = projection_cases.general_frame_pair()
+    base = projection_cases.base_under(world_from_grid, case.world_from_base)
+    tree_name, num_spheres, odd, quantile, outside = C.CASES[index]
+    threshold = threshold_off_every_clearance(case.samples.min_clearance, quantile)
+    q, first = R.interpolate(case.joint_from, case.joint_to, case.num_steps)
+    assert np.array_equal(first, case.first)
+    plain = R.check_samples(O, case.sdf, C.RESOLUTION, case.xyzr, case.link, case.tree, q, threshold, outside, None, None,
+                            case.world_from_base, case.joint_limits)
+    turned = R.check_samples(O, case.sdf, C.RESOLUTION, case.xyzr, case.link, case.tree, q, threshold, outside,
+                             grid_from_world, rotation, base, case.joint_limits)
+    assert (plain.status == body_ref.COLLISION).any()
+    r = rotation.reshape(3, 3)
+    worst = [0.0, 0.0]
+    for stop in (False, True):
+        want, got = R.reduce_motions(plain, first, stop), R.reduce_motions(turned, first, stop)
+        for field in ("status", "first_collision", "min_sample", "min_sphere", "fk_status"):
+            assert np.array_equal(getattr(got, field), getattr(want, field)), field
+        nan = np.isnan(want.min_clearance)
+        assert np.array_equal(np.isnan(got.min_clearance), nan)
+        infinite = np.isinf(want.min_clearance)
+        assert np.array_equal(got.min_clearance[infinite], want.min_clearance[infinite])
+        finite = ~nan & ~infinite
+        if finite.any():
+            worst[0] = max(worst[0], float(np.abs(got.min_clearance[finite] - want.min_clearance[finite]).max()))
+        with np.errstate(invalid="ignore", over="ignore"):
+            g = want.min_gradient
+            rotated = np.stack([(g[:, 0] * r[i, 0] + g[:, 1] * r[i, 1]) + g[:, 2] * r[i, 2] for i in range(3)], axis=-1)
+        same_kind = np.isfinite(rotated)
+        assert np.array_equal(np.isfinite(got.min_gradient), same_kind)
+        assert np.array_equal(np.isnan(got.min_gradient), np.isnan(rotated))
+        assert np.array_equal(got.min_gradient[np.isinf(rotated)], rotated[np.isinf(rotated)])
+        if same_kind.any():
+            worst[1] = max(worst[1], float(np.abs(got.min_gradient[same_kind] - rotated[same_kind]).max()))
+    print(case.name, "threshold", threshold, "largest differences: min_clearance %g, turned gradients %g" % tuple(worst))
+    assert worst[0] <= 1e-9 and worst[1] <= 1e-12
 
 
 def test_the_shared_cases_cover_what_the_gpu_tests_rely_on():

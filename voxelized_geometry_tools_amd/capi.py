@@ -214,6 +214,8 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_set_kinematics_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_motion_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_cost_workgroups": (_int, [_int]),
+    "vgt_hip_testing_motion_launch_geometry": (_int, [_i64, _i64, _p, _p]),
+    "vgt_hip_testing_cost_launch_geometry": (_int, [_i64, _i64, _int, _p, _p, _p, _p]),
     "vgt_hip_testing_set_self_collision_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1735,6 +1737,30 @@ def cost_tile_samples(num_links):
     """vgt_hip_cost_tile_samples: the configurations per tile clearance_cost uses for a tree of so many links; 0: too
     many."""
     return int(load().vgt_hip_cost_tile_samples(int(num_links)))
+
+
+MotionLaunchGeometry = collections.namedtuple("MotionLaunchGeometry", "tile_samples table_in_lds")
+CostLaunchGeometry = collections.namedtuple("CostLaunchGeometry", "tile_samples passes table_in_lds links_in_lds")
+
+
+def motion_launch_geometry(num_links, num_spheres):
+    """Testing library only (vgt_hip_testing_motion_launch_geometry): what a check_motions launch for so many links and
+    spheres is made of, from the launcher's own selection.  Raises ValueError for a tree the kernel does not take."""
+    out = [_i32(), _i32()]
+    check(load(testing=True).vgt_hip_testing_motion_launch_geometry(int(num_links), int(num_spheres),
+                                                                    *[ctypes.byref(o) for o in out]))
+    return MotionLaunchGeometry(*[int(o.value) for o in out])
+
+
+def cost_launch_geometry(num_links, num_spheres, gradient_form=True):
+    """Testing library only (vgt_hip_testing_cost_launch_geometry): what a clearance_cost launch for so many links and
+    spheres is made of in the gradient form or the cost-only form, from the launcher's own selection.  Raises ValueError
+    for a tree the kernel does not take."""
+    out = [_i32(), _i32(), _i32(), _i32()]
+    check(load(testing=True).vgt_hip_testing_cost_launch_geometry(int(num_links), int(num_spheres),
+                                                                  int(bool(gradient_form)),
+                                                                  *[ctypes.byref(o) for o in out]))
+    return CostLaunchGeometry(*[int(o.value) for o in out])
 
 
 def self_collision_tile_samples(num_links, num_spheres):

@@ -413,19 +413,11 @@ int CostTileSamples(int64_t num_links)
   return tile;
 }
 
-hipError_t LaunchClearanceCost(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                               const double* grid_from_world_host, const double* rotation_host,
-                               const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
-                               const KinematicLink* links_dev, int64_t num_links, int64_t num_joints,
-                               const double* joint_values_dev, int64_t num_configurations,
-                               const double* world_from_base_host, const double* limits_dev, double margin,
-                               const CostOutputs& out, int max_workgroups, hipStream_t stream)
+CostLaunchGeometry SelectCostGeometry(int64_t num_links, int64_t num_spheres, bool gradient)
 {
-  if (num_configurations <= 0) return hipSuccess;
+  CostLaunchGeometry geometry{0, 0, 0, 0, 0, 0, 0};
   const int tile = CostTileSamples(num_links);
-  if (tile <= 0) return hipErrorInvalidValue;
-  // (the count of skipped gradients needs the gradients: only without both does the cost-only kernel run)
-  const bool gradient = out.joint_gradient != nullptr || out.num_without_gradient != nullptr;
+  if (tile <= 0) return geometry;
   int log2_tile = 0;
   while ((1 << log2_tile) < tile) log2_tile++;
   const int log2_width = CheckSpheresWidthLog2(num_spheres);
@@ -436,20 +428,45 @@ hipError_t LaunchClearanceCost(const float* sdf_dev, int64_t nx, int64_t ny, int
   while (passes > 1 && CostLdsBytes(num_links, num_spheres, tile, passes, gradient, false, false) > kCostLdsLimit)
     passes >>= 1;
   if (CostLdsBytes(num_links, num_spheres, tile, passes, gradient, false, false) > kCostLdsLimit)
-    return hipErrorInvalidValue;  // (not with kCostMaxLinks: vgt_internal.hpp has the sum)
+    return geometry;  // (not with kCostMaxLinks: vgt_internal.hpp has the sum)
   // what the walk reads of the links first (every step of phase C's inner loop), then the sphere table
   const bool links_in_lds =
       gradient && CostLdsBytes(num_links, num_spheres, tile, passes, gradient, false, true) <= kCostLdsLimit;
   const bool table_in_lds =
       num_spheres <= kCostTableMax &&
       CostLdsBytes(num_links, num_spheres, tile, passes, gradient, true, links_in_lds) <= kCostLdsLimit;
-  const size_t lds_bytes = CostLdsBytes(num_links, num_spheres, tile, passes, gradient, table_in_lds, links_in_lds);
+  geometry.tile = tile;
+  geometry.log2_tile = log2_tile;
+  geometry.log2_width = log2_width;
+  geometry.passes = passes;
+  geometry.table_in_lds = table_in_lds ? 1 : 0;
+  geometry.links_in_lds = links_in_lds ? 1 : 0;
+  geometry.lds_bytes = CostLdsBytes(num_links, num_spheres, tile, passes, gradient, table_in_lds, links_in_lds);
+  return geometry;
+}
+
+hipError_t LaunchClearanceCost(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                               const double* grid_from_world_host, const double* rotation_host,
+                               const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                               const KinematicLink* links_dev, int64_t num_links, int64_t num_joints,
+                               const double* joint_values_dev, int64_t num_configurations,
+                               const double* world_from_base_host, const double* limits_dev, double margin,
+                               const CostOutputs& out, int max_workgroups, hipStream_t stream)
+{
+  if (num_configurations <= 0) return hipSuccess;
+  // (the count of skipped gradients needs the gradients: only without both does the cost-only kernel run)
+  const bool gradient = out.joint_gradient != nullptr || out.num_without_gradient != nullptr;
+  const CostLaunchGeometry selected = SelectCostGeometry(num_links, num_spheres, gradient);
+  if (selected.tile <= 0) return hipErrorInvalidValue;
+  const int tile = selected.tile;
+  const size_t lds_bytes = selected.lds_bytes;
   const int64_t tiles = (num_configurations + tile - 1) / tile;
   const int64_t most = max_workgroups > 0 ? max_workgroups : kCostMaxWorkgroups;
   const int64_t workgroups = tiles < most ? tiles : most;
   const CostTree tree{links_dev, limits_dev, static_cast<int>(num_links), static_cast<int>(num_joints)};
   const CostModel model{sphere_xyzr_dev, sphere_link_dev, static_cast<int>(num_spheres)};
-  const CostGeometry geometry{log2_width, log2_tile, passes, table_in_lds ? 1 : 0, links_in_lds ? 1 : 0};
+  const CostGeometry geometry{selected.log2_width, selected.log2_tile, selected.passes, selected.table_in_lds,
+                              selected.links_in_lds};
   if (gradient)
     hipLaunchKernelGGL(ClearanceCostKernel<true>, dim3(static_cast<unsigned>(workgroups)), dim3(kCostThreads), lds_bytes,
                        stream, sdf_dev, static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz), resolution,

@@ -345,6 +345,21 @@ int MotionTileSamples(int64_t num_links)
   return tile;
 }
 
+MotionLaunchGeometry SelectMotionGeometry(int64_t num_links, int64_t num_spheres)
+{
+  MotionLaunchGeometry geometry{0, 0, 0, 0, 0};
+  const int tile = MotionTileSamples(num_links);
+  if (tile <= 0) return geometry;
+  geometry.tile = tile;
+  while ((1 << geometry.log2_tile) < tile) geometry.log2_tile++;
+  geometry.log2_width = CheckSpheresWidthLog2(num_spheres);
+  const size_t pose_bytes = static_cast<size_t>(num_links) * kMotionPoseBytesPerLink * static_cast<size_t>(tile);
+  const size_t table_bytes = static_cast<size_t>(num_spheres) * 36;
+  geometry.table_in_lds = num_spheres <= kMotionTableMax && pose_bytes + table_bytes <= kMotionLdsLimit ? 1 : 0;
+  geometry.lds_bytes = pose_bytes + (geometry.table_in_lds ? table_bytes : 0);
+  return geometry;
+}
+
 hipError_t LaunchCheckMotions(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
                               const double* grid_from_world_host, const double* rotation_host,
                               const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
@@ -355,25 +370,19 @@ hipError_t LaunchCheckMotions(const float* sdf_dev, int64_t nx, int64_t ny, int6
                               int stop_at_collision, const MotionOutputs& out, int max_workgroups, hipStream_t stream)
 {
   if (num_motions <= 0) return hipSuccess;
-  const int tile = MotionTileSamples(num_links);
-  if (tile <= 0) return hipErrorInvalidValue;
-  int log2_tile = 0;
-  while ((1 << log2_tile) < tile) log2_tile++;
-  const int log2_width = CheckSpheresWidthLog2(num_spheres);
-  const size_t pose_bytes = static_cast<size_t>(num_links) * kMotionPoseBytesPerLink * static_cast<size_t>(tile);
-  const size_t table_bytes = static_cast<size_t>(num_spheres) * 36;
-  const int table_in_lds = num_spheres <= kMotionTableMax && pose_bytes + table_bytes <= kMotionLdsLimit ? 1 : 0;
-  const size_t lds_bytes = pose_bytes + (table_in_lds ? table_bytes : 0);
+  const MotionLaunchGeometry geometry = SelectMotionGeometry(num_links, num_spheres);
+  if (geometry.tile <= 0) return hipErrorInvalidValue;
   const int64_t most = max_workgroups > 0 ? max_workgroups : kMotionMaxWorkgroups;
   const int64_t workgroups = num_motions < most ? num_motions : most;
   const MotionTree tree{links_dev, limits_dev, static_cast<int>(num_links), static_cast<int>(num_joints)};
   const MotionModel model{sphere_xyzr_dev, sphere_link_dev, static_cast<int>(num_spheres)};
   const MotionBatch batch{joint_from_dev, joint_to_dev, num_steps_dev, uniform_steps, num_motions};
   const MotionQuery query{minimum_clearance, outside_is_collision ? 1 : 0, stop_at_collision ? 1 : 0};
-  hipLaunchKernelGGL(CheckMotionsKernel, dim3(static_cast<unsigned>(workgroups)), dim3(kMotionThreads), lds_bytes, stream,
-                     sdf_dev, static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz), resolution,
-                     MakeGridFromWorld(grid_from_world_host), MakeRotation(rotation_host), tree,
-                     MakeKinematicsBase(world_from_base_host), model, batch, query, log2_width, log2_tile, table_in_lds, out);
+  hipLaunchKernelGGL(CheckMotionsKernel, dim3(static_cast<unsigned>(workgroups)), dim3(kMotionThreads),
+                     geometry.lds_bytes, stream, sdf_dev, static_cast<int>(nx), static_cast<int>(ny), static_cast<int>(nz),
+                     resolution, MakeGridFromWorld(grid_from_world_host), MakeRotation(rotation_host), tree,
+                     MakeKinematicsBase(world_from_base_host), model, batch, query, geometry.log2_width, geometry.log2_tile,
+                     geometry.table_in_lds, out);
   return hipGetLastError();
 }
 }  // namespace vgt

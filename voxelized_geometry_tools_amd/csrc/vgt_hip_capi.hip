@@ -1674,6 +1674,33 @@ int vgt_hip_testing_set_cost_workgroups(int workgroups)
   return VGT_HIP_OK;
 }
 
+int vgt_hip_testing_motion_launch_geometry(int64_t num_links, int64_t num_spheres, int32_t* tile_samples,
+                                           int32_t* table_in_lds)
+{
+  if (!tile_samples || !table_in_lds) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_spheres < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "negative sphere count");
+  const vgt::MotionLaunchGeometry geometry = vgt::SelectMotionGeometry(num_links, num_spheres);
+  if (geometry.tile <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a tree the motion kernel does not take");
+  *tile_samples = geometry.tile;
+  *table_in_lds = geometry.table_in_lds;
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_cost_launch_geometry(int64_t num_links, int64_t num_spheres, int gradient_form, int32_t* tile_samples,
+                                         int32_t* passes, int32_t* table_in_lds, int32_t* links_in_lds)
+{
+  if (!tile_samples || !passes || !table_in_lds || !links_in_lds)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (num_spheres < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "negative sphere count");
+  const vgt::CostLaunchGeometry geometry = vgt::SelectCostGeometry(num_links, num_spheres, gradient_form != 0);
+  if (geometry.tile <= 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a tree the cost kernel does not take");
+  *tile_samples = geometry.tile;
+  *passes = geometry.passes;
+  *table_in_lds = geometry.table_in_lds;
+  *links_in_lds = geometry.links_in_lds;
+  return VGT_HIP_OK;
+}
+
 int vgt_hip_testing_set_self_collision_workgroups(int workgroups)
 {
   g_self_collision_workgroups.store(workgroups > 0 ? workgroups : 0);

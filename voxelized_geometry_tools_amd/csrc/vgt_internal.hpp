@@ -606,6 +606,15 @@ int MotionTileSamples(int64_t num_links);
 // it per sample, and so the most links of a tree: 640 (one sample per tile).
 constexpr size_t kMotionPoseBudget = 60 * 1024, kMotionPoseBytesPerLink = 96;
 constexpr int64_t kMotionMaxLinks = static_cast<int64_t>(kMotionPoseBudget / kMotionPoseBytesPerLink);
+// What a launch for a tree of L links and a model of S spheres is made of: the tile (0: a tree MotionTileSamples does
+// not take, and nothing else is set), the segment width, whether the sphere table sits in LDS behind the poses, and the
+// dynamic LDS.  The launcher takes all of it from here (and so does vgt_hip_testing_motion_launch_geometry).
+struct MotionLaunchGeometry
+{
+  int tile, log2_tile, log2_width, table_in_lds;
+  size_t lds_bytes;
+};
+MotionLaunchGeometry SelectMotionGeometry(int64_t num_links, int64_t num_spheres);
 // Grids of 0 to 2^31 - 1 cells; fewer than 2^31 spheres, motions and (motion, joint) pairs; a tree MotionTileSamples
 // takes.  Field, model, joint arrays, num_steps (or nullptr: uniform_steps) and outputs on the device; the three
 // transforms are host arrays (or nullptr); limits_dev: [J][2] or nullptr.  max_workgroups: 0 = the launcher's own limit
@@ -640,6 +649,16 @@ int CostTileSamples(int64_t num_links);
 // 68 B) and 20 B of resting sums: 53524 B of the 64 KiB a launch gets without an attribute.
 constexpr size_t kCostPoseBudget = 48 * 1024, kCostPoseBytesPerLink = 96;
 constexpr int64_t kCostMaxLinks = static_cast<int64_t>(kCostPoseBudget / kCostPoseBytesPerLink);
+// What a launch for a tree of L links and a model of S spheres is made of, in the gradient form or the cost-only form:
+// the tile (0: a tree CostTileSamples does not take, or a launch that does not fit, and nothing else is set), the
+// segment width, the buffered passes, whether the sphere table and what the walk reads of the links sit in LDS, and the
+// dynamic LDS.  The launcher takes all of it from here (and so does vgt_hip_testing_cost_launch_geometry).
+struct CostLaunchGeometry
+{
+  int tile, log2_tile, log2_width, passes, table_in_lds, links_in_lds;
+  size_t lds_bytes;
+};
+CostLaunchGeometry SelectCostGeometry(int64_t num_links, int64_t num_spheres, bool gradient);
 // Grids of 0 to 2^31 - 1 cells; fewer than 2^31 spheres, configurations and (configuration, joint) pairs; a tree
 // CostTileSamples takes.  Field, model, joint values and outputs on the device; the three transforms are host arrays (or
 // nullptr); limits_dev: [J][2] or nullptr.  Without joint_gradient and num_without_gradient the cost-only kernel runs,
