@@ -300,6 +300,8 @@ int vgt_hip_testing_cost_launch_geometry(int64_t num_links, int64_t num_spheres,
                                          int32_t* passes, int32_t* table_in_lds, int32_t* links_in_lds);
 /* The same for the launches of vgt_hip_check_self_collision[_poses][_dev] (one workgroup per tile of configurations). */
 int vgt_hip_testing_set_self_collision_workgroups(int workgroups);
+/* The same for the launches of vgt_hip_check_motions_with_self[_dev] (one workgroup per motion). */
+int vgt_hip_testing_set_motion_self_workgroups(int workgroups);
 /* Counting runs of vgt_hip_rasterize_spheres[_dev] (process-wide): while counters_dev is not NULL every launch adds to
  * its three uint64, on the device, the (cell, sphere) tests it made, those that covered, and the atomics it issued (a
  * counting variant of the kernel; the answers are the same).  The caller zeroes and reads them.  NULL: back to the
@@ -1148,6 +1150,92 @@ int vgt_hip_self_collision_pairs(const int32_t* sphere_link, int64_t num_spheres
  * (DESIGN.md 4p); 0: no links, or one configuration does not fit a launch's 64 KiB (96 L + 32 S + 256 bytes: 680 links
  * without spheres, 2037 spheres on one link).  Exposed so that tests put batch sizes and models on both sides of it. */
 int32_t vgt_hip_self_collision_tile_samples(int64_t num_links, int64_t num_spheres);
+
+/* ---- Motions checked against the field and against the robot itself in one call ----
+ * What a sampling planner asks of an edge in full: is the straight joint-space motion free of the environment AND of the
+ * robot itself, where does it first collide and with which of the two, how close does it come to either.  E motions in,
+ * one verdict per motion out; every sample's link poses and sphere centres are made once, used for both questions and
+ * never written to memory (csrc/motion_self_kernels.hip).  Read-only.
+ *
+ * Arguments: those of vgt_hip_check_motions, with pairs [P][2] and num_pairs behind the model as
+ * vgt_hip_check_self_collision takes them, self_minimum_clearance beside minimum_clearance, and the flag bit
+ * VGT_HIP_MOTION_SELF_NO_VALUE_IS_COLLISION beside VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION 1u and
+ * VGT_HIP_MOTION_STOP_AT_COLLISION 2u.  The field may be NULL (pass the extents as 0): its extents, resolution,
+ * grid_from_world, rotation and minimum_clearance are then not looked at.
+ *
+ * THE DEFINITION.  Nothing of the kinematics, of the sphere check or of the pair check is restated here.
+ * Samples: exactly vgt_hip_check_motions' (k == 0 and k == n > 0 take the given bits, otherwise a + t * (b - a)).
+ * The environment part is there iff the field is not NULL: per sample what vgt_hip_check_spheres_from_joints returns, as
+ * vgt_hip_check_motions says.
+ * The self part is there iff P > 0: per sample what vgt_hip_check_self_collision returns for joint_values = q with the
+ * same model, pairs, tree, world_from_base and joint_limits, minimum_clearance = self_minimum_clearance and its
+ * NO_VALUE_IS_COLLISION bit set iff flags & VGT_HIP_MOTION_SELF_NO_VALUE_IS_COLLISION: status, min_clearance, min_pair
+ * and fk_status, every bit.
+ * Neither part: VGT_HIP_ERR_INVALID_ARGUMENT.
+ * A sample COLLIDES when a part that is there says COLLISION; its cause is VGT_HIP_MOTION_CAUSE_ENVIRONMENT 1 |
+ * VGT_HIP_MOTION_CAUSE_SELF 2.  A sample is WITHOUT A VALUE when it does not collide and a part that is there says
+ * NO_VALUE.
+ * Considered samples: all of them; with flags & VGT_HIP_MOTION_STOP_AT_COLLISION only the samples 0 ... first_collision
+ * of this combined verdict: the later samples then do not exist for any output.
+ * Outputs, one entry per motion; status is required, every other output may be NULL:
+ *   status (uint8)            VGT_HIP_MOTION_COLLISION when a considered sample collides; otherwise
+ *                             VGT_HIP_MOTION_NO_VALUE when one is without a value; otherwise VGT_HIP_MOTION_CLEAR.
+ *                             VGT_HIP_MOTION_INVALID: the device form only, below.
+ *   first_collision (int32)   the least colliding k, or -1
+ *   collision_cause (uint8)   the cause bits of sample first_collision, or 0
+ *   min_clearance, min_sample, min_sphere, min_gradient [3]
+ *                             vgt_hip_check_motions' reduction of the environment part over the considered samples; NaN,
+ *                             -1, -1, NaN x 3 without an environment part
+ *   self_min_clearance (double), self_min_sample (int32), self_min_pair (int32)
+ *                             the least non-NaN self min_clearance among the considered samples; ties under == go to the
+ *                             lowest k; the value written is that sample's own bits and self_min_pair is that sample's
+ *                             min_pair.  NaN, -1, -1 when there is no such sample or no self part.
+ *   fk_status (uint8)         the OR of the considered samples' fk_status
+ * All reductions are total orders on distinct k: no output depends on the launch geometry.  Two consequences:
+ *   - without a self part every output this call shares with vgt_hip_check_motions equals that call's to the bit
+ *     (collision_cause is then 1 where first_collision is not -1);
+ *   - without VGT_HIP_MOTION_STOP_AT_COLLISION min_clearance, min_sample, min_sphere and min_gradient equal
+ *     vgt_hip_check_motions' to the bit, whatever the self part finds.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work: what vgt_hip_check_motions rejects (the field's own arguments
+ * only with a field) and, for the pair list, what vgt_hip_check_self_collision rejects: NULL pairs with P > 0 and S > 0, a
+ * negative P, P of 2^31 or more, a NaN self_minimum_clearance with P > 0; a tree or model larger than the kernel takes
+ * (vgt_hip_motion_self_tile_samples gives 0; the message gives both numbers).  The host form also looks at its arrays and
+ * names the first offender as the two calls do (num_steps, radii, pairs, links).  The device form cannot look: a motion
+ * with n < 0 gets status INVALID, first_collision -1, collision_cause 0, NaN, -1, -1, NaN x 3, NaN, -1, -1 and fk_status
+ * 0, and forms no address; a sphere_link outside [0, L) makes its sphere "without a value" for both parts and a sphere
+ * index outside [0, S) its pair, and no address is formed from such a value.
+ * E == 0 succeeds without a device.  With S == 0 the pair list is not looked at in either form (the self part, when P > 0,
+ * is NO_VALUE at every sample).  The host form stages its arrays and blocks; the device form (field, model, pairs, joint
+ * arrays, num_steps and outputs on the device; the three transforms / limits are host arrays) is enqueued on the context's
+ * stream, not blocking.  Calls that use one tree are serialised by the context. */
+#define VGT_HIP_MOTION_SELF_NO_VALUE_IS_COLLISION 4u
+#define VGT_HIP_MOTION_CAUSE_ENVIRONMENT 1
+#define VGT_HIP_MOTION_CAUSE_SELF 2
+int vgt_hip_check_motions_with_self(
+    vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+    const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+    const int32_t* sphere_link_host, int64_t num_spheres, const int32_t* pairs_host, int64_t num_pairs,
+    const vgt_hip_kinematics* tree, const double* joint_from_host, const double* joint_to_host,
+    const int32_t* num_steps_host, int32_t uniform_steps, int64_t num_motions, const double* world_from_base,
+    const double* joint_limits, double minimum_clearance, double self_minimum_clearance, uint32_t flags,
+    uint8_t* status_host, int32_t* first_collision_host, uint8_t* collision_cause_host, double* min_clearance_host,
+    int32_t* min_sample_host, int32_t* min_sphere_host, double* min_gradient_host, double* self_min_clearance_host,
+    int32_t* self_min_sample_host, int32_t* self_min_pair_host, uint8_t* fk_status_host);
+int vgt_hip_check_motions_with_self_dev(
+    vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+    const double* grid_from_world, const double* rotation, const double* sphere_xyzr_dev, const int32_t* sphere_link_dev,
+    int64_t num_spheres, const int32_t* pairs_dev, int64_t num_pairs, const vgt_hip_kinematics* tree,
+    const double* joint_from_dev, const double* joint_to_dev, const int32_t* num_steps_dev, int32_t uniform_steps,
+    int64_t num_motions, const double* world_from_base, const double* joint_limits, double minimum_clearance,
+    double self_minimum_clearance, uint32_t flags, uint8_t* status_dev, int32_t* first_collision_dev,
+    uint8_t* collision_cause_dev, double* min_clearance_dev, int32_t* min_sample_dev, int32_t* min_sphere_dev,
+    double* min_gradient_dev, double* self_min_clearance_dev, int32_t* self_min_sample_dev, int32_t* self_min_pair_dev,
+    uint8_t* fk_status_dev);
+/* The samples per tile the kernel uses for a tree of so many links carrying so many spheres: a power of two, at most 64,
+ * whose poses and centres take (96 L + 24 S) T <= 16 KiB of LDS where more than one sample fits that; 0: no
+ * links, or one sample does not fit a launch's 64 KiB (96 L + 32 S + 1792 bytes: 664 links without spheres, 1989 spheres
+ * on one link).  Exposed so that tests put step counts, models and pair lists on both sides of it. */
+int32_t vgt_hip_motion_self_tile_samples(int64_t num_links, int64_t num_spheres);
 
 /* ---- Nearest cell of the other class per voxel (the feature transform of the signed EDT) ----
  * The SDF says how far every voxel is from the other class; this says WHICH voxel that distance is measured to: the

@@ -128,6 +128,13 @@ SIGNATURES = {
                                                       ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_self_collision_pairs": (_int, [_p, _i64, _p, _i64, _p, _i64, ctypes.c_uint32, _p, _i64, _p]),
     "vgt_hip_self_collision_tile_samples": (_i32, [_i64, _i64]),
+    "vgt_hip_check_motions_with_self": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p,
+                                               _p, _i32, _i64, _p, _p, _f64, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p,
+                                               _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_check_motions_with_self_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _i64, _p, _p,
+                                                   _p, _p, _i32, _i64, _p, _p, _f64, _f64, ctypes.c_uint32, _p, _p, _p,
+                                                   _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_motion_self_tile_samples": (_i32, [_i64, _i64]),
     "vgt_hip_nearest_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "vgt_hip_nearest_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p, ctypes.c_size_t]),
     "vgt_hip_nearest_from_occupancy_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p]),
@@ -217,6 +224,7 @@ TESTING_SIGNATURES = {
     "vgt_hip_testing_motion_launch_geometry": (_int, [_i64, _i64, _p, _p]),
     "vgt_hip_testing_cost_launch_geometry": (_int, [_i64, _i64, _int, _p, _p, _p, _p]),
     "vgt_hip_testing_set_self_collision_workgroups": (_int, [_int]),
+    "vgt_hip_testing_set_motion_self_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_counters": (_int, [_p]),
     "vgt_hip_testing_class_record_bytes": (_sz, [_i64, _i64, _i64]),
     "vgt_hip_testing_class_records_dev": (_int, [_p, _p, _i64, _i64, _i64, _int, _i64, _p, _p]),
@@ -267,6 +275,10 @@ SELF_CLEAR = 0
 SELF_COLLISION = 1
 SELF_NO_VALUE = 2
 SELF_PAIRS_SKIP_ADJACENT = 1
+# flag and cause bits of check_motions_with_self (VGT_HIP_MOTION_SELF_*, VGT_HIP_MOTION_CAUSE_*)
+MOTION_SELF_NO_VALUE_IS_COLLISION = 4
+MOTION_CAUSE_ENVIRONMENT = 1
+MOTION_CAUSE_SELF = 2
 ALIGN_CONVERGED = 0
 ALIGN_ITERATION_LIMIT = 1
 ALIGN_DEGENERATE = 2
@@ -344,6 +356,12 @@ ClearanceCosts = collections.namedtuple(
 SelfCollisionChecks = collections.namedtuple(
     "SelfCollisionChecks", "status num_below num_without_value min_clearance min_pair min_direction joint_gradient "
     "fk_status pair_clearance")
+
+
+# what Context.check_motions_with_self returns: one entry per motion; min_gradient [E, 3]
+MotionSelfChecks = collections.namedtuple(
+    "MotionSelfChecks", "status first_collision collision_cause min_clearance min_sample min_sphere min_gradient "
+    "self_min_clearance self_min_sample self_min_pair fk_status")
 
 
 def _sphere_pairs(pairs):
@@ -875,6 +893,81 @@ class Context:
             _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
             flags, _ptr(status_ptr), _ptr(first_collision_ptr), _ptr(min_clearance_ptr), _ptr(min_sample_ptr),
             _ptr(min_sphere_ptr), _ptr(min_gradient_ptr), _ptr(fk_status_ptr)))
+
+    @staticmethod
+    def _motion_self_flags(outside_is_collision, stop_at_collision, self_no_value_is_collision):
+        return (SPHERES_OUTSIDE_IS_COLLISION if outside_is_collision else 0) | \
+            (MOTION_STOP_AT_COLLISION if stop_at_collision else 0) | \
+            (MOTION_SELF_NO_VALUE_IS_COLLISION if self_no_value_is_collision else 0)
+
+    def check_motions_with_self(self, sdf, resolution, spheres_xyzr, sphere_link, pairs, tree, joint_from, joint_to,
+                                num_steps, minimum_clearance=0.0, self_minimum_clearance=0.0,
+                                outside_is_collision=False, stop_at_collision=False, self_no_value_is_collision=False,
+                                grid_from_world=None, rotation=None, world_from_base=None, joint_limits=None):
+        """vgt_hip_check_motions_with_self: check_motions' motions, every sample checked against the field (sdf, or None
+        for no environment part) as check_spheres_from_joints checks a configuration and against the robot itself over
+        the sphere pairs `pairs` [P, 2] (None or empty for no self part) as check_self_collision does; poses and centres
+        are made once per sample and never leave the device.  Returns MotionSelfChecks(status uint8 (MOTION_*),
+        first_collision int32, collision_cause uint8 (MOTION_CAUSE_* bits), min_clearance float64, min_sample int32,
+        min_sphere int32, min_gradient [E, 3] float64, self_min_clearance float64, self_min_sample int32, self_min_pair
+        int32, fk_status uint8 (FK_* bits))."""
+        f = None if sdf is None else np.ascontiguousarray(sdf, dtype=np.float32)
+        if f is not None and f.ndim != 3:
+            raise ValueError("sdf must be an (nx, ny, nz) grid")
+        shape = (0, 0, 0) if f is None else f.shape
+        xyzr = np.ascontiguousarray(spheres_xyzr, dtype=np.float64).reshape(-1, 4)
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        if len(link) != len(xyzr):
+            raise ValueError("sphere_link must hold one link per sphere")
+        ab = _sphere_pairs(np.zeros((0, 2), np.int32) if pairs is None else pairs)
+        a, b = _joint_values(tree, joint_from), _joint_values(tree, joint_to)
+        if a.shape != b.shape:
+            raise ValueError("joint_from and joint_to must have the same shape")
+        e, s = a.shape[0], len(xyzr)
+        if np.ndim(num_steps) == 0:
+            steps, uniform = None, int(num_steps)
+        else:
+            steps, uniform = np.ascontiguousarray(num_steps, dtype=np.int32).reshape(-1), 0
+            if len(steps) != e:
+                raise ValueError("num_steps must hold one count per motion")
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        out = MotionSelfChecks(np.empty(e, np.uint8), np.empty(e, np.int32), np.empty(e, np.uint8),
+                               np.empty(e, np.float64), np.empty(e, np.int32), np.empty(e, np.int32),
+                               np.empty((e, 3), np.float64), np.empty(e, np.float64), np.empty(e, np.int32),
+                               np.empty(e, np.int32), np.empty(e, np.uint8))
+        flags = self._motion_self_flags(outside_is_collision, stop_at_collision, self_no_value_is_collision)
+        check(self._lib.vgt_hip_check_motions_with_self(
+            self.handle, _ptr(f), *shape, float(resolution), _ptr(xf), _ptr(rot), _ptr(xyzr), _ptr(link), s, _ptr(ab),
+            len(ab), tree._handle_or_raise(), _ptr(a), _ptr(b), _ptr(steps), uniform, e,
+            _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)), float(minimum_clearance),
+            float(self_minimum_clearance), flags, *[_ptr(o) for o in out]))
+        return out
+
+    def check_motions_with_self_dev(self, sdf_ptr, shape, resolution, spheres_xyzr_ptr, sphere_link_ptr, num_spheres,
+                                    pairs_ptr, num_pairs, tree, joint_from_ptr, joint_to_ptr, num_steps, num_motions,
+                                    status_ptr, first_collision_ptr=None, collision_cause_ptr=None,
+                                    min_clearance_ptr=None, min_sample_ptr=None, min_sphere_ptr=None,
+                                    min_gradient_ptr=None, self_min_clearance_ptr=None, self_min_sample_ptr=None,
+                                    self_min_pair_ptr=None, fk_status_ptr=None, minimum_clearance=0.0,
+                                    self_minimum_clearance=0.0, outside_is_collision=False, stop_at_collision=False,
+                                    self_no_value_is_collision=False, grid_from_world=None, rotation=None,
+                                    world_from_base=None, joint_limits=None, num_steps_ptr=None):
+        """vgt_hip_check_motions_with_self_dev: field (or None, with shape (0, 0, 0)), model, pairs, joint arrays and
+        outputs on the device (the transforms and the limits are host arrays); num_steps: the step count of every motion,
+        unless num_steps_ptr gives an int32 array [E] on the device; enqueued on the context's stream."""
+        xf = None if grid_from_world is None else np.ascontiguousarray(grid_from_world, dtype=np.float64).reshape(16)
+        rot = None if rotation is None else np.ascontiguousarray(rotation, dtype=np.float64).reshape(9)
+        flags = self._motion_self_flags(outside_is_collision, stop_at_collision, self_no_value_is_collision)
+        check(self._lib.vgt_hip_check_motions_with_self_dev(
+            self.handle, _ptr(sdf_ptr), *[int(c) for c in shape], float(resolution), _ptr(xf), _ptr(rot),
+            _ptr(spheres_xyzr_ptr), _ptr(sphere_link_ptr), int(num_spheres), _ptr(pairs_ptr), int(num_pairs),
+            tree._handle_or_raise(), _ptr(joint_from_ptr), _ptr(joint_to_ptr), _ptr(num_steps_ptr), int(num_steps or 0),
+            int(num_motions), _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)),
+            float(minimum_clearance), float(self_minimum_clearance), flags, _ptr(status_ptr), _ptr(first_collision_ptr),
+            _ptr(collision_cause_ptr), _ptr(min_clearance_ptr), _ptr(min_sample_ptr), _ptr(min_sphere_ptr),
+            _ptr(min_gradient_ptr), _ptr(self_min_clearance_ptr), _ptr(self_min_sample_ptr), _ptr(self_min_pair_ptr),
+            _ptr(fk_status_ptr)))
 
     def clearance_cost(self, sdf, resolution, spheres_xyzr, sphere_link, tree, joint_values, margin, grid_from_world=None,
                        rotation=None, world_from_base=None, joint_limits=None, with_gradient=True):
@@ -1508,6 +1601,11 @@ class Context:
         (0 = back to the product's limit)."""
         check(self._lib.vgt_hip_testing_set_self_collision_workgroups(int(workgroups)))
 
+    def set_motion_self_workgroups(self, workgroups):
+        """Testing library only (process-wide there): at most `workgroups` workgroups per launch of
+        check_motions_with_self (0 = back to the product's limit)."""
+        check(self._lib.vgt_hip_testing_set_motion_self_workgroups(int(workgroups)))
+
     def set_sphere_volume_counters(self, counters_ptr):
         """Testing library only (process-wide there): three uint64 on the device to which every rasterize_spheres launch
         adds its (cell, sphere) tests, those that covered and the atomics issued; None = back to the product's kernel."""
@@ -1767,6 +1865,12 @@ def self_collision_tile_samples(num_links, num_spheres):
     """vgt_hip_self_collision_tile_samples: the configurations per tile check_self_collision uses for a tree of so many
     links carrying so many spheres; 0: the kernel does not take the shape."""
     return int(load().vgt_hip_self_collision_tile_samples(int(num_links), int(num_spheres)))
+
+
+def motion_self_tile_samples(num_links, num_spheres):
+    """vgt_hip_motion_self_tile_samples: the samples per tile check_motions_with_self uses for a tree of so many links
+    carrying so many spheres; 0: the kernel does not take the shape."""
+    return int(load().vgt_hip_motion_self_tile_samples(int(num_links), int(num_spheres)))
 
 
 def self_collision_pairs(sphere_link, num_links, parent=None, ignored_link_pairs=None, skip_adjacent=False,

@@ -179,6 +179,8 @@ std::atomic<int> g_motion_workgroups{0};
 std::atomic<int> g_cost_workgroups{0};
 // The same from vgt_hip_testing_set_self_collision_workgroups, for the self-collision check.
 std::atomic<int> g_self_collision_workgroups{0};
+// The same from vgt_hip_testing_set_motion_self_workgroups, for the motion check with the self part.
+std::atomic<int> g_motion_self_workgroups{0};
 // The same from vgt_hip_testing_set_sphere_volume_workgroups, for the sphere rasterizer and the point cover.
 std::atomic<int> g_sphere_volume_workgroups{0};
 // What vgt_hip_testing_set_sphere_volume_counters gave: three uint64 on the device that the sphere rasterizer adds its
@@ -1704,6 +1706,12 @@ int vgt_hip_testing_cost_launch_geometry(int64_t num_links, int64_t num_spheres,
 int vgt_hip_testing_set_self_collision_workgroups(int workgroups)
 {
   g_self_collision_workgroups.store(workgroups > 0 ? workgroups : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_motion_self_workgroups(int workgroups)
+{
+  g_motion_self_workgroups.store(workgroups > 0 ? workgroups : 0);
   return VGT_HIP_OK;
 }
 
@@ -5698,6 +5706,241 @@ struct SelfCollisionArguments
   }
 };
 }  // namespace
+
+/* ------------------- motions checked against an SDF and against the robot itself in one call ------------------- */
+
+namespace
+{
+// What the two entry points share: the arguments and the checks both make before any device work.
+struct CheckMotionsWithSelfArguments
+{
+  const float* sdf;  // nullptr: no environment part
+  int64_t nx, ny, nz;
+  double resolution;
+  const double *grid_from_world, *rotation;
+  const double* sphere_xyzr;
+  const int32_t* sphere_link;
+  int64_t num_spheres;
+  const int32_t* pairs;
+  int64_t num_pairs;  // 0: no self part
+  const vgt_hip_kinematics* tree;
+  const double *joint_from, *joint_to;
+  const int32_t* num_steps;
+  int32_t uniform_steps;
+  int64_t num_motions;
+  const double *world_from_base, *joint_limits;
+  double minimum_clearance, self_minimum_clearance;
+  uint32_t flags;
+  vgt::MotionSelfOutputs out;
+
+  int64_t NumCells() const { return sdf ? nx * ny * nz : 0; }
+  // *done: nothing is left to do (E == 0).
+  int Check(const vgt_hip_ctx* ctx, bool* done) const
+  {
+    *done = false;
+    if (!ctx || !tree || !out.status || (num_spheres > 0 && (!sphere_xyzr || !sphere_link)) ||
+        (num_spheres > 0 && num_pairs > 0 && !pairs))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_spheres < 0 || num_pairs < 0 || num_motions < 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the numbers of spheres, pairs and motions must not be negative");
+    if (!sdf && num_pairs == 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "neither a field nor a pair: there is nothing to check the motions against");
+    if (!num_steps && uniform_steps < 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "uniform_steps " + std::to_string(uniform_steps) + " is negative");
+    const int64_t most = 0x7fffffffLL;
+    if (sdf)
+    {
+      if (nx < 0 || ny < 0 || nz < 0) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "grid extents must not be negative");
+      if (!(resolution > 0.0) || !std::isfinite(resolution))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "Grid must have uniform, positive resolution");
+      // (extent by extent: the product of three int64 extents can overflow)
+      if (nx > most || ny > most || nz > most || (nx > 0 && ny > 0 && nz > 0 && (nx * ny > most || nx * ny * nz > most)))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "motion checks support grids below 2^31 cells");
+      if (std::isnan(minimum_clearance)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "minimum_clearance must not be NaN");
+    }
+    if (num_pairs > 0 && std::isnan(self_minimum_clearance))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "self_minimum_clearance must not be NaN");
+    if (flags & ~(VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION | VGT_HIP_MOTION_STOP_AT_COLLISION |
+                  VGT_HIP_MOTION_SELF_NO_VALUE_IS_COLLISION))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "unknown motion check flag");
+    if (num_spheres > most || num_pairs > most || num_motions > most)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "motion checks support fewer than 2^31 spheres, pairs and motions");
+    *done = num_motions == 0;  // (before the tree is looked at)
+    return VGT_HIP_OK;
+  }
+  // What needs the tree (after E == 0, which succeeds before the tree is looked at).
+  int CheckTree(const vgt_hip_ctx* ctx) const
+  {
+    if (tree->ctx != ctx) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree belongs to another context");
+    if (vgt::MotionSelfTileSamples(tree->num_links, num_spheres) == 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                  "motion checks with the self part take at least one link and 96 bytes per link + 32 per sphere + " +
+                      std::to_string(vgt::kMotionSelfRecordBytes) + " within " +
+                      std::to_string(vgt::kMotionSelfLdsLimit) + ", this model has " + std::to_string(tree->num_links) +
+                      " links and " + std::to_string(num_spheres) + " spheres");
+    if (tree->num_joints > 0 && (!joint_from || !joint_to)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_motions * tree->num_joints >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "motion checks support fewer than 2^31 (motion, joint) pairs");
+    return VGT_HIP_OK;
+  }
+  // The host form's own checks: it can look at the step counts, the model and the pairs (the links once the tree is
+  // known).
+  int CheckHostArrays() const
+  {
+    for (int64_t e = 0; num_steps && e < num_motions; e++)
+      if (num_steps[e] < 0)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "motion " + std::to_string(e) + ": num_steps " + std::to_string(num_steps[e]));
+    for (int64_t s = 0; s < num_spheres; s++)
+      if (!(sphere_xyzr[4 * s + 3] >= 0.0))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "sphere " + std::to_string(s) + ": the radius must not be negative or NaN");
+    for (int64_t p = 0; num_spheres > 0 && p < num_pairs; p++)
+    {
+      const int64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+      for (const int64_t sphere : {a, b})
+        if (sphere < 0 || sphere >= num_spheres)
+          return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "pair " + std::to_string(p) + ": sphere " + std::to_string(sphere) +
+                                                        " is outside [0, " + std::to_string(num_spheres) + ")");
+      if (a >= b)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "pair " + std::to_string(p) + ": (" + std::to_string(a) + ", " +
+                                                      std::to_string(b) + ") is not ascending");
+    }
+    return VGT_HIP_OK;
+  }
+  int CheckHostLinks() const
+  {
+    for (int64_t s = 0; s < num_spheres; s++)
+      if (sphere_link[s] < 0 || sphere_link[s] >= tree->num_links)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(s) + ": link " +
+                                                      std::to_string(sphere_link[s]) + " is not in [0, num_links)");
+    return VGT_HIP_OK;
+  }
+  // Enqueues the check on `stream`; the context's mutex is held (the tree's limits buffer is one per tree).
+  hipError_t Enqueue(const float* sdf_dev, const double* xyzr_dev, const int32_t* link_dev, const int32_t* pairs_dev,
+                     const double* from_dev, const double* to_dev, const int32_t* steps_dev,
+                     const vgt::MotionSelfOutputs& out_dev, hipStream_t stream) const
+  {
+    const bool limited = joint_limits && tree->num_joints > 0;
+    if (limited)
+    {
+      // (pageable host memory: the runtime has taken its copy when the call returns)
+      const hipError_t err = hipMemcpyAsync(tree->limits.as<double>(), joint_limits,
+                                            static_cast<size_t>(tree->num_joints) * 2 * sizeof(double),
+                                            hipMemcpyHostToDevice, stream);
+      if (err != hipSuccess) return err;
+    }
+    return vgt::LaunchCheckMotionsWithSelf(
+        sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, xyzr_dev, link_dev, num_spheres, pairs_dev, num_pairs,
+        tree->links.as<vgt::KinematicLink>(), tree->num_links, tree->num_joints, from_dev, to_dev, steps_dev,
+        uniform_steps, num_motions, world_from_base, limited ? tree->limits.as<double>() : nullptr, minimum_clearance,
+        self_minimum_clearance, (flags & VGT_HIP_SPHERES_OUTSIDE_IS_COLLISION) ? 1 : 0,
+        (flags & VGT_HIP_MOTION_SELF_NO_VALUE_IS_COLLISION) ? 1 : 0, (flags & VGT_HIP_MOTION_STOP_AT_COLLISION) ? 1 : 0,
+        out_dev, g_motion_self_workgroups.load(), stream);
+  }
+};
+}  // namespace
+
+int32_t vgt_hip_motion_self_tile_samples(int64_t num_links, int64_t num_spheres)
+{
+  return vgt::MotionSelfTileSamples(num_links, num_spheres);
+}
+
+int vgt_hip_check_motions_with_self_dev(
+    vgt_hip_ctx* ctx, const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+    const double* grid_from_world, const double* rotation, const double* sphere_xyzr_dev, const int32_t* sphere_link_dev,
+    int64_t num_spheres, const int32_t* pairs_dev, int64_t num_pairs, const vgt_hip_kinematics* tree,
+    const double* joint_from_dev, const double* joint_to_dev, const int32_t* num_steps_dev, int32_t uniform_steps,
+    int64_t num_motions, const double* world_from_base, const double* joint_limits, double minimum_clearance,
+    double self_minimum_clearance, uint32_t flags, uint8_t* status_dev, int32_t* first_collision_dev,
+    uint8_t* collision_cause_dev, double* min_clearance_dev, int32_t* min_sample_dev, int32_t* min_sphere_dev,
+    double* min_gradient_dev, double* self_min_clearance_dev, int32_t* self_min_sample_dev, int32_t* self_min_pair_dev,
+    uint8_t* fk_status_dev)
+{
+  const CheckMotionsWithSelfArguments a{
+      sdf_dev, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_dev, sphere_link_dev, num_spheres, pairs_dev,
+      num_pairs, tree, joint_from_dev, joint_to_dev, num_steps_dev, uniform_steps, num_motions, world_from_base,
+      joint_limits, minimum_clearance, self_minimum_clearance, flags,
+      {status_dev, first_collision_dev, collision_cause_dev, min_clearance_dev, min_sample_dev, min_sphere_dev,
+       min_gradient_dev, self_min_clearance_dev, self_min_sample_dev, self_min_pair_dev, fk_status_dev}};
+  bool done = false;
+  int rc = a.Check(ctx, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  rc = a.CheckTree(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(a.Enqueue(sdf_dev, sphere_xyzr_dev, sphere_link_dev, pairs_dev, joint_from_dev, joint_to_dev, num_steps_dev,
+                        a.out, ctx->stream),
+              "check motions with self");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_check_motions_with_self(
+    vgt_hip_ctx* ctx, const float* sdf_host, int64_t nx, int64_t ny, int64_t nz, double resolution,
+    const double* grid_from_world, const double* rotation, const double* sphere_xyzr_host,
+    const int32_t* sphere_link_host, int64_t num_spheres, const int32_t* pairs_host, int64_t num_pairs,
+    const vgt_hip_kinematics* tree, const double* joint_from_host, const double* joint_to_host,
+    const int32_t* num_steps_host, int32_t uniform_steps, int64_t num_motions, const double* world_from_base,
+    const double* joint_limits, double minimum_clearance, double self_minimum_clearance, uint32_t flags,
+    uint8_t* status_host, int32_t* first_collision_host, uint8_t* collision_cause_host, double* min_clearance_host,
+    int32_t* min_sample_host, int32_t* min_sphere_host, double* min_gradient_host, double* self_min_clearance_host,
+    int32_t* self_min_sample_host, int32_t* self_min_pair_host, uint8_t* fk_status_host)
+{
+  const CheckMotionsWithSelfArguments a{
+      sdf_host, nx, ny, nz, resolution, grid_from_world, rotation, sphere_xyzr_host, sphere_link_host, num_spheres,
+      pairs_host, num_pairs, tree, joint_from_host, joint_to_host, num_steps_host, uniform_steps, num_motions,
+      world_from_base, joint_limits, minimum_clearance, self_minimum_clearance, flags,
+      {status_host, first_collision_host, collision_cause_host, min_clearance_host, min_sample_host, min_sphere_host,
+       min_gradient_host, self_min_clearance_host, self_min_sample_host, self_min_pair_host, fk_status_host}};
+  bool done = false;
+  int rc = a.Check(ctx, &done);
+  if (rc != VGT_HIP_OK || done) return rc;
+  rc = a.CheckHostArrays();
+  if (rc == VGT_HIP_OK) rc = a.CheckTree(ctx);
+  if (rc == VGT_HIP_OK) rc = a.CheckHostLinks();
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "check motions with self";
+  const size_t e = static_cast<size_t>(num_motions), s = static_cast<size_t>(num_spheres);
+  const size_t joints = static_cast<size_t>(tree->num_joints);
+  // (a tree without joints: one double stands in, so that the kernel has an address it never reads)
+  const double none = 0.0;
+  // (eleven outputs and seven inputs, and a staging holds eight arrays: three of them, each inside the one before's body)
+  vgt::HostStaging inputs;
+  const auto sdf = inputs.In(sdf_host, static_cast<size_t>(a.NumCells()));
+  const auto xyzr = inputs.In(sphere_xyzr_host, s * 4);
+  const auto link = inputs.In(sphere_link_host, s);
+  const auto list = inputs.In(num_spheres > 0 ? pairs_host : nullptr, static_cast<size_t>(num_pairs) * 2);
+  const auto from = joints > 0 ? inputs.In(joint_from_host, e * joints) : inputs.In(&none, 1);
+  const auto to = joints > 0 ? inputs.In(joint_to_host, e * joints) : inputs.In(&none, 1);
+  const auto steps = inputs.In(num_steps_host, e);
+  return inputs.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
+    vgt::HostStaging outputs;
+    const auto status = outputs.Out(status_host, e);
+    const auto first_collision = outputs.Out(first_collision_host, e);
+    const auto collision_cause = outputs.Out(collision_cause_host, e);
+    const auto min_clearance = outputs.Out(min_clearance_host, e);
+    const auto min_sample = outputs.Out(min_sample_host, e);
+    const auto min_sphere = outputs.Out(min_sphere_host, e);
+    const auto min_gradient = outputs.Out(min_gradient_host, e * 3);
+    const auto fk_status = outputs.Out(fk_status_host, e);
+    return outputs.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+      vgt::HostStaging self_outputs;
+      const auto self_min_clearance = self_outputs.Out(self_min_clearance_host, e);
+      const auto self_min_sample = self_outputs.Out(self_min_sample_host, e);
+      const auto self_min_pair = self_outputs.Out(self_min_pair_host, e);
+      return self_outputs.RunLocked(stream, what, FailHip, [&](hipStream_t) {
+        const vgt::MotionSelfOutputs out{status.dev(),          first_collision.dev(),    collision_cause.dev(),
+                                         min_clearance.dev(),   min_sample.dev(),         min_sphere.dev(),
+                                         min_gradient.dev(),    self_min_clearance.dev(), self_min_sample.dev(),
+                                         self_min_pair.dev(),   fk_status.dev()};
+        return HipResult(what, a.Enqueue(sdf.dev(), xyzr.dev(), link.dev(), list.dev(), from.dev(), to.dev(), steps.dev(),
+                                         out, stream));
+      });
+    });
+  });
+}
 
 int32_t vgt_hip_self_collision_tile_samples(int64_t num_links, int64_t num_spheres)
 {

@@ -709,6 +709,47 @@ hipError_t LaunchSelfCollision(const double* sphere_xyzr_dev, const int32_t* sph
                                int no_value_is_collision, const SelfCollisionOutputs& out, int max_workgroups,
                                hipStream_t stream);
 
+// --- launcher (motion_self_kernels.hip): motions checked against an SDF and against the robot itself in one walk ---
+// The definition of every output: include/vgt_hip.h, vgt_hip_check_motions_with_self.  status is required, every other
+// output may be nullptr.
+struct MotionSelfOutputs
+{
+  uint8_t* status;
+  int32_t* first_collision;
+  uint8_t* collision_cause;
+  double* min_clearance;
+  int32_t* min_sample;
+  int32_t* min_sphere;
+  double* min_gradient;  // [E][3]
+  double* self_min_clearance;
+  int32_t* self_min_sample;
+  int32_t* self_min_pair;
+  uint8_t* fk_status;
+};
+// What a launch may take of dynamic LDS (what it gets without an attribute), and what a link and a sphere take of it per
+// sample of a tile: the twelve used elements of a pose, the three of a centre.  Beside them a launch holds 8 B per sphere
+// (the radii) and 1792 B (per slot of a tile the environment part's worst sphere, its clearance and cell, and the status).
+constexpr size_t kMotionSelfLdsLimit = 64 * 1024, kMotionSelfPoseBytesPerLink = 96, kMotionSelfCentreBytes = 24,
+                 kMotionSelfRecordBytes = 64 * 28;
+// The samples of a tile for a tree of so many links carrying so many spheres: the largest power of two T <= 64 whose
+// poses and centres, (96 L + 24 S) T bytes, stay within the build's VGT_MOTION_SELF_TILE_BYTES (16 KiB), 1 where two
+// samples exceed that; 0: no links, or one sample does not fit the LDS of a launch (96 L + 32 S + 1792 > 64 KiB).
+int MotionSelfTileSamples(int64_t num_links, int64_t num_spheres);
+// As LaunchCheckMotions, with the pair list of LaunchSelfCollision (pairs_dev [P][2]; P == 0: no self part) and a field
+// that may be nullptr (no environment part, the extents are not looked at); one of the two parts must be there.  A shape
+// MotionSelfTileSamples takes.  max_workgroups: 0 = the launcher's own limit
+// (vgt_hip_testing_set_motion_self_workgroups).
+hipError_t LaunchCheckMotionsWithSelf(const float* sdf_dev, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                      const double* grid_from_world_host, const double* rotation_host,
+                                      const double* sphere_xyzr_dev, const int32_t* sphere_link_dev, int64_t num_spheres,
+                                      const int32_t* pairs_dev, int64_t num_pairs, const KinematicLink* links_dev,
+                                      int64_t num_links, int64_t num_joints, const double* joint_from_dev,
+                                      const double* joint_to_dev, const int32_t* num_steps_dev, int32_t uniform_steps,
+                                      int64_t num_motions, const double* world_from_base_host, const double* limits_dev,
+                                      double minimum_clearance, double self_minimum_clearance, int outside_is_collision,
+                                      int no_value_is_collision, int stop_at_collision, const MotionSelfOutputs& out,
+                                      int max_workgroups, hipStream_t stream);
+
 // --- launchers (voxelizer_kernels.hip) ---
 struct RaycastGridF32
 {
