@@ -277,7 +277,7 @@ int vgt_hip_testing_set_sphere_volume_workgroups(int workgroups);
 int vgt_hip_testing_set_align_workgroups(int workgroups);
 /* The same for the launches of vgt_hip_forward_kinematics[_dev] (workgroups of 64 configurations) and
  * vgt_hip_clearance_joint_gradient[_dev], so that a few hundred configurations already make their persistent waves
- * stride. */
+ * stride.  It caps the launch of vgt_hip_solve_ik[_dev] (workgroups of 64 problems) in the same way. */
 int vgt_hip_testing_set_kinematics_workgroups(int workgroups);
 /* The same for the launches of vgt_hip_check_motions[_dev] (one workgroup per motion), so that a few motions already make
  * its persistent waves stride. */
@@ -903,6 +903,98 @@ int vgt_hip_check_spheres_from_joints(vgt_hip_ctx* ctx, const float* sdf_host, i
                                       int32_t* num_outside_host, double* min_gradient_host,
                                       double* sphere_clearance_host, double* sphere_gradient_host,
                                       uint8_t* fk_status_host, double* joint_gradient_host);
+
+/* ---- Inverse kinematics: tip poses to joint values, batched over targets and seeds ----
+ * The step in front of every joint-driven call: a task arrives as the pose of a tool frame, and a planner turns it into
+ * goal configurations -- many of them, from many seeds -- before it keeps those that pass
+ * vgt_hip_check_spheres_from_joints and vgt_hip_check_self_collision.  B problems (a target pose and a seed row of joint
+ * values) in, one row of joint values per problem out, after up to K damped least-squares steps that bring one chosen
+ * link (the tip) of a vgt_hip_kinematics tree to its target.  Everything happens on the device, in one launch
+ * (csrc/ik_kernels.hip); nothing is synchronised with the host between iterations.
+ * Inputs:
+ *   tree, tip_link   the tree as it is, and a link in [0, L).  The chain is the set of links on the way from the tip to
+ *                    the base; the call finds it from the tree.
+ *   targets          [T][16] doubles, column-major world_from_tip; elements 0-2, 4-6, 8-10 and 12-14 are read.
+ *   seeds_per_target R >= 1: B = T * R, and problem b aims at target b / R (a planner's restarts need no tiled copy of
+ *                    the targets).
+ *   seeds            [B][J] doubles.
+ *   world_from_base, joint_limits [J][2]   as for vgt_hip_forward_kinematics: host arrays in both forms, each may be NULL.
+ *   task_weights     6 doubles w (a host array in both forms, NULL = all 1) for (x, y, z, rx, ry, rz), each finite and
+ *                    >= 0.  A weight of 0 removes that component from both the step and the convergence test:
+ *                    (1, 1, 1, 0, 0, 0) is position-only IK.
+ *   max_iterations   K in [0, 10000]; K = 0 evaluates the seeds only.  damping lambda >= 0, finite.  max_step > 0,
+ *                    +infinity is allowed.  position_tolerance, rotation_tolerance >= 0.
+ *
+ * THE DEFINITION.  Everything in double, without contraction, every operator rounded on its own.
+ * evaluate(q): the poses of the chain's links exactly as vgt_hip_forward_kinematics defines them for the row q (links off
+ *   the chain are not computed); m is the tip's.  With t* and r*_c the target's translation and rotation columns and r_c
+ *   those of m, cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0) and dot(a, b) = (a0*b0 + a1*b1) + a2*b2:
+ *     e_r = t*_r - m[12+r] for r = 0, 1, 2;   x_c = cross(r_c, r*_c);   (e_3, e_4, e_5) = ((x_0 + x_1) + x_2) * 0.5
+ *     componentwise;   trace = (dot(r_0, r*_0) + dot(r_1, r*_1)) + dot(r_2, r*_2).
+ *   The orientation error is sin(theta) times the axis of the rotation that is left: no inverse trigonometry, exact to
+ *   first order.
+ * converged: every |e_i| with w_i != 0 is <= its tolerance (position_tolerance for i < 3, rotation_tolerance for i >= 3;
+ *   NaN compares false); and, when all three rotational weights are non-zero, trace > 1 -- which excludes the half turn,
+ *   where the cross products vanish.
+ * columns: for every chain link i that is not FIXED, walked from the tip to the base, with a the expression a_r of
+ *   vgt_hip_clearance_joint_gradient for the pose of link i, o the translation of that pose and p the translation of m:
+ *     REVOLUTE   d = p - o;  c = (cross(a, d), a)      (the translational half is that call's expression u)
+ *     PRISMATIC  c = (a, +0.0, +0.0, +0.0)
+ *   then c_k <- w_k * c_k.  As there, the columns are derivatives only for revolute axes of unit length; with another
+ *   length they are the definition, not a derivative.
+ * step:
+ *   A = sum of c c^T over the chain in walk order: the 21 entries j <= k each start at +0.0, then A_jk = A_jk + c_j*c_k;
+ *   A_jj = A_jj + lambda*lambda;
+ *   A y = (w_i * e_i) by the L D L^T sequence of vgt_hip_align_points' "solve" with b = the weighted e, without its
+ *   damping line and without its final negation (y is its x).  A D_j that is not > 0, or a y with a component that is
+ *   not finite: VGT_HIP_IK_DEGENERATE.
+ *   dq_i = ((((c_0*y_0 + c_1*y_1) + c_2*y_2) + c_3*y_3) + c_4*y_4) + c_5*y_5 per moving chain link;
+ *   mx = +0.0, then in walk order mx = |dq_i| where |dq_i| > mx;  if mx > max_step: s = max_step / mx, dq_i = dq_i * s;
+ *   q_j = q_j + dq_i for j = joint_index[i];  with limits: q_j = lower_j where q_j < lower_j, then q_j = upper_j where
+ *   q_j > upper_j.
+ * loop, per problem: evaluate the seed; after EVERY evaluation, in this order: a chain link that is not computable (the
+ *   forward kinematics' bit 1) stops the problem as VGT_HIP_IK_NOT_COMPUTABLE; a converged problem stops as
+ *   VGT_HIP_IK_CONVERGED; a problem that has taken K steps stops as VGT_HIP_IK_ITERATION_LIMIT; otherwise it takes a
+ *   step, which may stop it as VGT_HIP_IK_DEGENERATE, and is evaluated again.  A problem that stops is returned exactly
+ *   as it stood at its last evaluation and costs nothing further.  Every output is this one fixed sequence of
+ *   operations: the answer does not depend on the launch geometry.
+ * Two moving links on one chain that read one column (a mimic joint on the chain) would need a column sum per joint:
+ * such a (tree, tip) is refused, and the message names both links.  A mimic joint off the chain is fine.
+ * Outputs per problem (`status` is required, every other output may be NULL):
+ *   joints_out [J]     the row at the last evaluation; columns that no chain link reads are the seed's, bit for bit.  It
+ *                      may be the seed array.
+ *   status (uint8), iterations (int32: the steps taken), error [6] (the unweighted e at the returned row),
+ *   tip_pose [16]      m, written with 0, 0, 0, 1 like link_poses;
+ *   fk_status (uint8)  VGT_HIP_FK_NOT_COMPUTABLE from the chain's links, VGT_HIP_FK_OUTSIDE_LIMITS by the forward
+ *                      kinematics' test over all J columns of the returned row.
+ * VGT_HIP_ERR_INVALID_ARGUMENT before any device work, outputs untouched: a NULL required pointer (ctx, tree, targets,
+ * status; seeds when J > 0), T <= 0 or R <= 0, B >= 2^31, a tip outside [0, L), a tree of another context, K, lambda,
+ * max_step, a tolerance or a weight outside the ranges above, a mimic joint on the chain, a chain with more than
+ * vgt_hip_ik_max_chain_joints() moving links (a constant of the kernel, which keeps six doubles per moving link and lane
+ * in LDS; at least 16: a 7-joint arm on a lift on a 6-joint floating base), and in the device form a missing or too
+ * small workspace.  The host form blocks; the device form (targets, seeds and outputs on the device) is enqueued on the
+ * context's stream.  The working rows are those of joints_out; only when joints_out_dev is NULL does the device form
+ * need vgt_hip_solve_ik_workspace_bytes(J, B) bytes of scratch (0 for sizes the call refuses), which must stay untouched
+ * until the call is done.  Calls that use one tree are serialised by the context. */
+#define VGT_HIP_IK_CONVERGED 0
+#define VGT_HIP_IK_ITERATION_LIMIT 1
+#define VGT_HIP_IK_DEGENERATE 2
+#define VGT_HIP_IK_NOT_COMPUTABLE 3
+int32_t vgt_hip_ik_max_chain_joints(void);
+int vgt_hip_solve_ik(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, int32_t tip_link, const double* targets_host,
+                     int64_t num_targets, int64_t seeds_per_target, const double* seeds_host,
+                     const double* world_from_base, const double* joint_limits, const double* task_weights,
+                     int32_t max_iterations, double damping, double max_step, double position_tolerance,
+                     double rotation_tolerance, double* joints_out_host, uint8_t* status_host, int32_t* iterations_host,
+                     double* error_host, double* tip_pose_host, uint8_t* fk_status_host);
+size_t vgt_hip_solve_ik_workspace_bytes(int64_t num_joints, int64_t num_problems);
+int vgt_hip_solve_ik_dev(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, int32_t tip_link, const double* targets_dev,
+                         int64_t num_targets, int64_t seeds_per_target, const double* seeds_dev,
+                         const double* world_from_base, const double* joint_limits, const double* task_weights,
+                         int32_t max_iterations, double damping, double max_step, double position_tolerance,
+                         double rotation_tolerance, double* joints_out_dev, uint8_t* status_dev, int32_t* iterations_dev,
+                         double* error_dev, double* tip_pose_dev, uint8_t* fk_status_dev, void* workspace_dev,
+                         size_t workspace_bytes);
 
 /* ---- Motions between joint configurations checked against an SDF ----
  * The question a sampling planner asks of an edge: is the straight joint-space motion from q_a to q_b free, where does it

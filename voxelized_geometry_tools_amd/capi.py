@@ -108,6 +108,12 @@ SIGNATURES = {
     "vgt_hip_clearance_joint_gradient_dev": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "vgt_hip_check_spheres_from_joints": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p,
                                                  _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "vgt_hip_ik_max_chain_joints": (_i32, []),
+    "vgt_hip_solve_ik": (_int, [_p, _p, _i32, _p, _i64, _i64, _p, _p, _p, _p, _i32, _f64, _f64, _f64, _f64, _p, _p, _p,
+                                _p, _p, _p]),
+    "vgt_hip_solve_ik_workspace_bytes": (_sz, [_i64, _i64]),
+    "vgt_hip_solve_ik_dev": (_int, [_p, _p, _i32, _p, _i64, _i64, _p, _p, _p, _p, _i32, _f64, _f64, _f64, _f64, _p, _p,
+                                    _p, _p, _p, _p, _p, _sz]),
     "vgt_hip_check_motions": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64, _p,
                                      _p, _f64, ctypes.c_uint32, _p, _p, _p, _p, _p, _p, _p]),
     "vgt_hip_check_motions_dev": (_int, [_p, _p, _i64, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _i64,
@@ -263,6 +269,11 @@ SPHERES_KEEP = 1
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1, 2
 FK_NOT_COMPUTABLE = 1
 FK_OUTSIDE_LIMITS = 2
+# statuses of solve_ik (VGT_HIP_IK_*)
+IK_CONVERGED = 0
+IK_ITERATION_LIMIT = 1
+IK_DEGENERATE = 2
+IK_NOT_COMPUTABLE = 3
 # flag and statuses of check_motions (VGT_HIP_MOTION_*)
 MOTION_STOP_AT_COLLISION = 2
 MOTION_CLEAR = 0
@@ -339,6 +350,19 @@ def _cloud_poses(poses):
 # what Context.check_spheres_from_joints returns: SphereChecks' fields, then fk_status [B] uint8 (FK_* bits) and
 # joint_gradient [B, J] (None unless asked for)
 JointSphereChecks = collections.namedtuple("JointSphereChecks", SphereChecks._fields + ("fk_status", "joint_gradient"))
+
+
+# what Context.solve_ik returns: one entry per problem; joints [B, J], error [B, 6], tip_pose [B, 16] column-major
+IkSolutions = collections.namedtuple("IkSolutions", "joints status iterations error tip_pose fk_status")
+
+
+def _task_weights(task_weights):
+    if task_weights is None:
+        return None
+    weights = np.ascontiguousarray(task_weights, dtype=np.float64)
+    if weights.shape != (6,):
+        raise ValueError("task_weights must hold six values")
+    return weights
 
 
 # what Context.check_motions returns: one entry per motion; min_gradient [E, 3]
@@ -804,6 +828,43 @@ class Context:
             self.handle, tree._handle_or_raise(), _ptr(link_poses_ptr), int(num_configurations), _ptr(spheres_xyzr_ptr),
             _ptr(sphere_link_ptr), int(num_spheres), _ptr(min_sphere_ptr), _ptr(min_gradient_ptr),
             _ptr(sphere_weight_ptr), _ptr(sphere_gradient_ptr), _ptr(joint_gradient_ptr)))
+
+    def solve_ik(self, tree, tip_link, targets, seeds, seeds_per_target=1, world_from_base=None, joint_limits=None,
+                 task_weights=None, max_iterations=50, damping=0.01, max_step=0.5, position_tolerance=1e-6,
+                 rotation_tolerance=1e-6):
+        """vgt_hip_solve_ik: targets [T, 16] column-major world_from_tip (or [T, 4, 4] matrices, transposed here) and
+        seeds [T * seeds_per_target, J] -> IkSolutions(joints [B, J], status uint8 (IK_*), iterations int32, error
+        [B, 6], tip_pose [B, 16], fk_status uint8 (FK_* bits)): up to max_iterations damped least-squares steps per
+        problem that bring link tip_link to its target (0: the seeds are evaluated only).  task_weights: six values for
+        (x, y, z, rx, ry, rz), None = all 1."""
+        aim = _cloud_poses(targets)
+        q = _joint_values(tree, seeds)
+        b = q.shape[0]
+        if b != len(aim) * int(seeds_per_target):
+            raise ValueError("seeds must hold seeds_per_target rows per target")
+        out = IkSolutions(np.empty((b, tree.num_joints), np.float64), np.empty(b, np.uint8), np.empty(b, np.int32),
+                          np.empty((b, 6), np.float64), np.empty((b, 16), np.float64), np.empty(b, np.uint8))
+        check(self._lib.vgt_hip_solve_ik(
+            self.handle, tree._handle_or_raise(), int(tip_link), _ptr(aim), len(aim), int(seeds_per_target), _ptr(q),
+            _ptr(_base_transform(world_from_base)), _ptr(_joint_limits(tree, joint_limits)),
+            _ptr(_task_weights(task_weights)), int(max_iterations), float(damping), float(max_step),
+            float(position_tolerance), float(rotation_tolerance), *[_ptr(a) for a in out]))
+        return out
+
+    def solve_ik_dev(self, tree, tip_link, targets_ptr, num_targets, seeds_ptr, status_ptr, joints_out_ptr=None,
+                     iterations_ptr=None, error_ptr=None, tip_pose_ptr=None, fk_status_ptr=None, workspace_ptr=None,
+                     workspace_bytes=0, seeds_per_target=1, world_from_base=None, joint_limits=None, task_weights=None,
+                     max_iterations=50, damping=0.01, max_step=0.5, position_tolerance=1e-6, rotation_tolerance=1e-6):
+        """vgt_hip_solve_ik_dev: targets, seeds and outputs on the device (the base transform, the limits and the
+        weights are host arrays); joints_out_ptr may be seeds_ptr, and only without it does the call need the workspace
+        (solve_ik_workspace_bytes); enqueued on the context's stream."""
+        check(self._lib.vgt_hip_solve_ik_dev(
+            self.handle, tree._handle_or_raise(), int(tip_link), _ptr(targets_ptr), int(num_targets),
+            int(seeds_per_target), _ptr(seeds_ptr), _ptr(_base_transform(world_from_base)),
+            _ptr(_joint_limits(tree, joint_limits)), _ptr(_task_weights(task_weights)), int(max_iterations),
+            float(damping), float(max_step), float(position_tolerance), float(rotation_tolerance), _ptr(joints_out_ptr),
+            _ptr(status_ptr), _ptr(iterations_ptr), _ptr(error_ptr), _ptr(tip_pose_ptr), _ptr(fk_status_ptr),
+            _ptr(workspace_ptr), int(workspace_bytes)))
 
     def check_spheres_from_joints(self, sdf, resolution, spheres_xyzr, sphere_link, tree, joint_values,
                                   minimum_clearance=0.0, outside_is_collision=False, per_sphere=False,
@@ -1583,7 +1644,8 @@ class Context:
 
     def set_kinematics_workgroups(self, workgroups):
         """Testing library only (process-wide there): at most `workgroups` workgroups per launch of forward_kinematics
-        and clearance_joint_gradient (0 = back to the product's limit)."""
+        and clearance_joint_gradient (0 = back to the product's limit).  It caps the launch of solve_ik in the same
+        way."""
         check(self._lib.vgt_hip_testing_set_kinematics_workgroups(int(workgroups)))
 
     def set_motion_workgroups(self, workgroups):
@@ -1819,6 +1881,16 @@ def sdf_workspace_bytes(shape, variant=0):
     """Workspace of the device-resident SDF entry points (variant != 0: a cross-check pipeline of the testing library)."""
     lib = load(testing=int(variant) != 0)
     return int(lib.vgt_hip_sdf_workspace_bytes_for_variant(*[int(s) for s in shape], int(variant)))
+
+
+def ik_max_chain_joints():
+    """vgt_hip_ik_max_chain_joints: the most moving links solve_ik takes on a chain (a constant of the kernel)."""
+    return int(load().vgt_hip_ik_max_chain_joints())
+
+
+def solve_ik_workspace_bytes(num_joints, num_problems):
+    """Workspace of Context.solve_ik_dev without joints_out_ptr; 0 for sizes the call refuses."""
+    return int(load().vgt_hip_solve_ik_workspace_bytes(int(num_joints), int(num_problems)))
 
 
 def kinematics_lds_links():

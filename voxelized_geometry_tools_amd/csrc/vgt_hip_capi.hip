@@ -139,6 +139,8 @@ struct vgt_hip_kinematics
   int lds_links = 0;         // the LDS slots of the tree (vgt::AssignKinematicsLdsSlots)
   vgt::DeviceTemp links;     // [num_links] vgt::KinematicLink
   vgt::DeviceTemp limits;    // [num_joints][2] doubles: the joint_limits of the call being enqueued
+  vgt::DeviceTemp chain;     // [num_links] int32: the chain of the vgt_hip_solve_ik call being enqueued, base first
+  std::vector<vgt::KinematicLink> host_links;  // the records as uploaded: vgt_hip_solve_ik finds its chain here
 };
 
 // Device copy of a grid of cell records (occupancy + optional object id) and the buffers the
@@ -4954,6 +4956,7 @@ int vgt_hip_kinematics_create(vgt_hip_ctx* ctx, int64_t num_links, int64_t num_j
   const size_t bytes = links.size() * sizeof(vgt::KinematicLink);
   hipError_t err = tree->links.Allocate(bytes);
   if (err == hipSuccess) err = tree->limits.Allocate(static_cast<size_t>(num_joints > 0 ? num_joints : 1) * 2 * sizeof(double));
+  if (err == hipSuccess) err = tree->chain.Allocate(static_cast<size_t>(num_links) * sizeof(int32_t));
   if (err == hipSuccess)
   {
     std::lock_guard<std::mutex> lock(ctx->mutex);
@@ -4965,6 +4968,7 @@ int vgt_hip_kinematics_create(vgt_hip_ctx* ctx, int64_t num_links, int64_t num_j
     delete tree;
     return FailHip("Failed to upload the kinematic tree", err);
   }
+  tree->host_links = std::move(links);
   AdoptChild(ctx);
   *out_tree = tree;
   return VGT_HIP_OK;
@@ -5071,6 +5075,181 @@ int vgt_hip_clearance_joint_gradient(vgt_hip_ctx* ctx, const vgt_hip_kinematics*
   return staging.Run(*ctx, what, FailHip, [&](hipStream_t stream) {
     return HipResult(what, a.Launch(poses.dev(), xyzr.dev(), link.dev(), min_sphere.dev(), min_gradient.dev(),
                                     weight.dev(), gradient.dev(), out.dev(), stream));
+  });
+}
+
+/* ------------------- inverse kinematics: tip poses to joint values ------------------- */
+
+namespace
+{
+// What the two inverse-kinematics entry points share: the arguments, the checks both make before any device work (which
+// find the chain) and the enqueue.
+struct SolveIkArguments
+{
+  const vgt_hip_kinematics* tree;
+  int32_t tip_link;
+  const double* targets;
+  int64_t num_targets, seeds_per_target;
+  const double* seeds;
+  const double* world_from_base;
+  const double* joint_limits;
+  const double* task_weights;
+  int32_t max_iterations;
+  double damping, max_step, position_tolerance, rotation_tolerance;
+  const uint8_t* status;
+
+  std::vector<int32_t> chain;  // the links from the base to the tip (Check)
+  int moving = 0;              // how many of them are not fixed
+
+  int64_t NumProblems() const { return num_targets * seeds_per_target; }
+
+  int Check(const vgt_hip_ctx* ctx)
+  {
+    if (!ctx || !tree || !targets || !status) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (num_targets <= 0 || seeds_per_target <= 0)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "inverse kinematics needs at least one target and one seed per target");
+    if (num_targets >= kTwoTo31 || seeds_per_target >= kTwoTo31 || NumProblems() >= kTwoTo31)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "inverse kinematics supports fewer than 2^31 problems");
+    if (tree->ctx != ctx) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the kinematic tree belongs to another context");
+    if (tree->num_joints > 0 && !seeds) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (tip_link < 0 || tip_link >= tree->num_links)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "tip link " + std::to_string(tip_link) + " is not in [0, " +
+                                                    std::to_string(tree->num_links) + ")");
+    if (max_iterations < 0 || max_iterations > 10000)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "max_iterations must lie in [0, 10000]");
+    if (!(damping >= 0.0) || !std::isfinite(damping))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the damping must be finite and not negative");
+    if (!(max_step > 0.0)) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "max_step must be positive (+infinity is allowed)");
+    if (!(position_tolerance >= 0.0) || !(rotation_tolerance >= 0.0))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a tolerance must not be negative");
+    for (int k = 0; task_weights && k < 6; k++)
+      if (!(task_weights[k] >= 0.0) || !std::isfinite(task_weights[k]))
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "a task weight must be finite and not negative");
+    const std::vector<vgt::KinematicLink>& links = tree->host_links;
+    std::vector<int32_t> reader;  // per column the moving chain link that reads it, -1: none
+    try
+    {
+      for (int32_t i = tip_link; i >= 0; i = links[static_cast<size_t>(i)].parent) chain.push_back(i);
+      reader.assign(static_cast<size_t>(tree->num_joints), -1);
+    }
+    catch (const std::bad_alloc&)
+    {
+      return Fail(VGT_HIP_ERR_RUNTIME, "out of host memory");
+    }
+    std::reverse(chain.begin(), chain.end());
+    int64_t count = 0;
+    for (const int32_t i : chain)
+    {
+      const vgt::KinematicLink& link = links[static_cast<size_t>(i)];
+      if (link.joint_type == vgt::kJointFixed) continue;
+      int32_t& first = reader[static_cast<size_t>(link.joint_index)];
+      if (first >= 0)
+        return Fail(VGT_HIP_ERR_INVALID_ARGUMENT,
+                    "links " + std::to_string(first) + " and " + std::to_string(i) + " on the chain to link " +
+                        std::to_string(tip_link) + " both read column " + std::to_string(link.joint_index) +
+                        ": inverse kinematics does not take a mimic joint on the chain");
+      first = i;
+      count++;
+    }
+    if (count > vgt::kIkMaxChainJoints)
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the chain to link " + std::to_string(tip_link) + " has " +
+                                                    std::to_string(count) + " moving links; inverse kinematics takes at most " +
+                                                    std::to_string(vgt::kIkMaxChainJoints));
+    moving = static_cast<int>(count);
+    return VGT_HIP_OK;
+  }
+
+  // Enqueues the call on `stream`; the context's mutex is held (the tree's chain and limits buffers are one per tree).
+  hipError_t Enqueue(const double* targets_dev, const double* seeds_dev, const vgt::IkOutputs& out, hipStream_t stream) const
+  {
+    // (pageable host memory: the runtime has taken its copies when the calls return)
+    hipError_t err = hipMemcpyAsync(tree->chain.as<int32_t>(), chain.data(), chain.size() * sizeof(int32_t),
+                                    hipMemcpyHostToDevice, stream);
+    const bool limited = joint_limits && tree->num_joints > 0;
+    if (err == hipSuccess && limited)
+      err = hipMemcpyAsync(tree->limits.as<double>(), joint_limits,
+                           static_cast<size_t>(tree->num_joints) * 2 * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (err != hipSuccess) return err;
+    vgt::IkOptions options{max_iterations, damping, max_step, position_tolerance, rotation_tolerance, {1, 1, 1, 1, 1, 1}};
+    for (int k = 0; task_weights && k < 6; k++) options.weights[k] = task_weights[k];
+    return vgt::LaunchSolveIk(tree->links.as<vgt::KinematicLink>(), tree->num_joints, tree->chain.as<int32_t>(),
+                              static_cast<int>(chain.size()), moving, targets_dev, seeds_per_target, seeds_dev,
+                              NumProblems(), world_from_base, limited ? tree->limits.as<double>() : nullptr, options, out,
+                              g_kinematics_workgroups.load(), stream);
+  }
+};
+}  // namespace
+
+int32_t vgt_hip_ik_max_chain_joints(void) { return vgt::kIkMaxChainJoints; }
+
+size_t vgt_hip_solve_ik_workspace_bytes(int64_t num_joints, int64_t num_problems)
+{
+  if (num_joints < 0 || num_joints >= kTwoTo31 || num_problems <= 0 || num_problems >= kTwoTo31) return 0;
+  return static_cast<size_t>(num_joints) * static_cast<size_t>(num_problems) * sizeof(double);
+}
+
+int vgt_hip_solve_ik_dev(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, int32_t tip_link, const double* targets_dev,
+                         int64_t num_targets, int64_t seeds_per_target, const double* seeds_dev,
+                         const double* world_from_base, const double* joint_limits, const double* task_weights,
+                         int32_t max_iterations, double damping, double max_step, double position_tolerance,
+                         double rotation_tolerance, double* joints_out_dev, uint8_t* status_dev, int32_t* iterations_dev,
+                         double* error_dev, double* tip_pose_dev, uint8_t* fk_status_dev, void* workspace_dev,
+                         size_t workspace_bytes)
+{
+  SolveIkArguments a{tree, tip_link, targets_dev, num_targets, seeds_per_target, seeds_dev, world_from_base, joint_limits,
+                     task_weights, max_iterations, damping, max_step, position_tolerance, rotation_tolerance, status_dev,
+                     {}, 0};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  double* rows = joints_out_dev;
+  if (!rows && tree->num_joints > 0)
+  {
+    if (!workspace_dev) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "without joints_out the call needs its workspace");
+    if (workspace_bytes < vgt_hip_solve_ik_workspace_bytes(tree->num_joints, a.NumProblems()))
+      return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "the workspace is smaller than vgt_hip_solve_ik_workspace_bytes says");
+    rows = static_cast<double*>(workspace_dev);
+  }
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(a.Enqueue(targets_dev, seeds_dev, {rows, status_dev, iterations_dev, error_dev, tip_pose_dev, fk_status_dev},
+                        ctx->stream),
+              "solve ik");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_solve_ik(vgt_hip_ctx* ctx, const vgt_hip_kinematics* tree, int32_t tip_link, const double* targets_host,
+                     int64_t num_targets, int64_t seeds_per_target, const double* seeds_host,
+                     const double* world_from_base, const double* joint_limits, const double* task_weights,
+                     int32_t max_iterations, double damping, double max_step, double position_tolerance,
+                     double rotation_tolerance, double* joints_out_host, uint8_t* status_host, int32_t* iterations_host,
+                     double* error_host, double* tip_pose_host, uint8_t* fk_status_host)
+{
+  SolveIkArguments a{tree, tip_link, targets_host, num_targets, seeds_per_target, seeds_host, world_from_base,
+                     joint_limits, task_weights, max_iterations, damping, max_step, position_tolerance,
+                     rotation_tolerance, status_host, {}, 0};
+  const int rc = a.Check(ctx);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const char* what = "solve ik";
+  const size_t b = static_cast<size_t>(a.NumProblems()), joints = static_cast<size_t>(tree->num_joints);
+  vgt::HostStaging staging;
+  // (a tree without joints: one double stands in, so that the kernel has an address it never reads)
+  const double none = 0.0;
+  const auto targets = staging.In(targets_host, static_cast<size_t>(num_targets) * 16);
+  const auto seeds = joints > 0 ? staging.In(seeds_host, b * joints) : staging.In(&none, 1);
+  // the working rows: the caller's output, or scratch when the caller does without it
+  const auto rows = joints_out_host ? staging.Out(joints_out_host, b * joints)
+                                    : staging.Scratch<double>((b * joints > 0 ? b * joints : 1) * sizeof(double));
+  const auto status = staging.Out(status_host, b);
+  const auto iterations = staging.Out(iterations_host, b);
+  const auto error = staging.Out(error_host, b * 6);
+  const auto tip_pose = staging.Out(tip_pose_host, b * 16);
+  const auto fk_status = staging.Out(fk_status_host, b);
+  return staging.Run(*ctx, what, FailHip, [&](hipStream_t s) {
+    return HipResult(what, a.Enqueue(targets.dev(), seeds.dev(),
+                                     {rows.dev(), status.dev(), iterations.dev(), error.dev(), tip_pose.dev(),
+                                      fk_status.dev()},
+                                     s));
   });
 }
 

@@ -585,6 +585,35 @@ hipError_t LaunchClearanceJointGradient(const KinematicLink* links_dev, int64_t 
                                         const double* sphere_gradient_dev, double* joint_gradient_dev,
                                         int max_workgroups, hipStream_t stream);
 
+// --- launcher (ik_kernels.hip): tip poses to joint values ---
+// The definition, every output and the statuses: include/vgt_hip.h, vgt_hip_solve_ik.
+// The kernel keeps six doubles per lane and moving chain link in LDS: 3 KiB per link for a workgroup of one wave, 48 KiB
+// at this many.
+constexpr int kIkMaxChainJoints = 16;
+struct IkOptions
+{
+  int max_iterations;
+  double damping, max_step, position_tolerance, rotation_tolerance;
+  double weights[6];
+};
+struct IkOutputs
+{
+  double* joints;  // [B][J]: the working rows, required when J > 0
+  uint8_t* status;
+  int32_t* iterations;
+  double* error;
+  double* tip_pose;
+  uint8_t* fk_status;
+};
+// chain_dev: the chain's links, base first (each the parent of the next, the first on the base); moving_links: how many of
+// them are not fixed, at most kIkMaxChainJoints, no two reading one column.  Problem b aims at targets_dev[b /
+// seeds_per_target].  out.joints may be seeds_dev; every other output but out.status may be nullptr.  max_workgroups:
+// 0 = the launcher's own limit (vgt_hip_testing_set_kinematics_workgroups).
+hipError_t LaunchSolveIk(const KinematicLink* links_dev, int64_t num_joints, const int32_t* chain_dev, int chain_links,
+                         int moving_links, const double* targets_dev, int64_t seeds_per_target, const double* seeds_dev,
+                         int64_t num_problems, const double* world_from_base_host, const double* limits_dev,
+                         const IkOptions& options, const IkOutputs& out, int max_workgroups, hipStream_t stream);
+
 // --- launcher (motion_kernels.hip): motions between joint configurations checked against an SDF ---
 // The definition of every output: include/vgt_hip.h, vgt_hip_check_motions.  status is required, every other output may
 // be nullptr.
