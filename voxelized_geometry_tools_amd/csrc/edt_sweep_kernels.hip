@@ -26,7 +26,8 @@
 //   * Sweep 2 walks the line backwards: the owner of a row is found by comparing the two topmost members at that
 //     row (values along the envelope are unimodal), (Gs - Gt) + 2 q (rt - rs) <= 0 pops.  The distances to the
 //     bounding rows of the other class are running counters fed by the line's sign bits (one word per 32 rows, kept
-//     in the scratch buffer between the sweeps); waves whose 64 lines hold one class only skip that part, and a wave with
+//     in the scratch buffer between the sweeps; the Y pass takes them back in blocks of kInfoBlock words, a block ahead,
+//     the X pass word by word with a take-over per band: profiles/r9/sign_blocks.md); waves whose 64 lines hold one class only skip that part, and a wave with
 //     class changes skips it band by band: where no change touches a band in any lane and the top entry's parabola stays
 //     below the squared distance to the nearest change at both ends of the band, the candidates can decide nothing
 //     (two votes per band; profiles/r7/class_band_skip.md).
@@ -51,7 +52,9 @@
 // cycles in s_waitcnt: profiles/r8/sweep_waits.md), not by HBM and not by instruction issue: rows are processed kBand at a
 // time (registers), the code below keeps rare paths (refills, exact final conversion) out of the straight-line code,
 // values of loads issued long ago are taken over where the source says (TakeLoaded) and not where a full drain of the
-// store queue stands in front of them, and register and LDS use are sized for kWaves waves per SIMD.
+// store queue stands in front of them, nothing that was loaded is carried across sweep 2's back edge (sign words come in
+// blocks or are taken over inside the band, refill chunks are requested and committed inside one band), so a full band
+// that refills nothing waits for no store (profiles/r9/sign_blocks.md), and register and LDS use are sized for kWaves waves per SIMD.
 #include "edt_device.hpp"
 #include "edt_line_geom.hpp"
 
@@ -79,6 +82,14 @@ namespace
 #endif
 constexpr int kBand = VGT_SWEEP_BAND;    // rows held in registers at a time: 8, 16 or 32
 constexpr int kWord = 32;                // rows per sign word
+#ifndef VGT_SWEEP_INFO_BLOCK
+#define VGT_SWEEP_INFO_BLOCK 2
+#endif
+// Sign words the Y pass's sweep 2 takes at a time: a block of kInfoBlock words is kInfoBlock back-to-back 512-byte loads of
+// the scratch's [word][lane] layout.  Blocks are counted from the line's last word down; word indices below zero are read
+// as word 0 (and never used), so no load leaves the slot.  (2 and 4 measure the same, 8 spills: profiles/r9/sign_blocks.md.)
+constexpr int kInfoBlock = VGT_SWEEP_INFO_BLOCK;
+static_assert(kInfoBlock >= 1, "sizes");
 #ifndef VGT_SWEEP_RING_WIDE
 #define VGT_SWEEP_RING_WIDE 16
 #endif
@@ -108,6 +119,10 @@ static_assert(kWord % kBand == 0 && kBand % 2 == 0, "sizes");
 uint64_t class_band_tally[3] = {0, 0, 0};
 // Sweep 1's checks of the ring, per lane, and those that spilled a chunk (a check spills one chunk or none: asserted there).
 uint64_t ring_checks = 0, ring_spills = 0;
+// Sign words: every lane poisons its words of the slot when it takes an item, and sweep 2 asserts that no word it USES
+// (loads may fetch more) is poison: it reads what sweep 1 wrote for this item.  A carry is at most kFar, never the poison.
+constexpr uint32_t kInfoPoison = 0xdeadbeefu;
+uint64_t sign_word_reads = 0;
 #endif
 
 
@@ -428,7 +443,11 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   using Entry = typename C::Entry;
   // the Y pass reads class records, the X pass the Y pass's int32 field
   constexpr bool kRecords = std::is_same<InT, ClassRecord>::value;
-  constexpr bool kTakeSignWords = kFinal;  // sweep 2 takes its sign words over band by band (X pass)
+  // Sweep 2 takes its sign words in blocks (Y pass) or band by band (X pass): each pass keeps what its own A / B says
+  // (profiles/r9/sign_blocks.md: blocks gain nothing on the X pass, whose band-by-band take-over already left no drain).
+  // (one choice: the per-word request of earlier rounds, with its drain per band, is gone)
+  constexpr bool kSignBlocks = !kFinal;
+  constexpr bool kTakeSignWords = !kSignBlocks;
   static_assert(!(kRecords && kFinal), "records feed the Y pass");
   constexpr int kRing = RingShape<kPacked>::kRing;
   constexpr int kChunk = RingShape<kPacked>::kChunk;
@@ -501,6 +520,9 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   item = fetch_item();
 #endif
   if (item >= g.items) break;
+#ifdef VGT_HOST_EMULATION
+  for (int64_t w = 0; w < g.nwords + 1; w++) wave_info[w * kWaveSize + lane] = make_uint2(kInfoPoison, kInfoPoison);
+#endif
   const int outer = item / g.zsegs;
   const int z0 = (item - outer * g.zsegs) * kWaveSize;
   // (a batch of grids: which grid, and the outer index inside it -- one grid: 0 and `outer`)
@@ -984,6 +1006,10 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
     for (int w = nwords - 1; w >= 0; w--)
     {
       const uint32_t sw = info.x;
+#ifdef VGT_HOST_EMULATION
+      assert(info.y != kInfoPoison);
+      sign_word_reads++;
+#endif
       if (w > 0) info = LoadPair(wave_info + static_cast<int64_t>(w - 1) * kWaveSize + lane);
       const int valid = min(kWord, n - w * kWord);
       if constexpr (kFinal)
@@ -1011,33 +1037,43 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   else
   {
     // Every kStep rows the chunks requested at the last step go into the ring and up to two more are requested
-    // when the ring has room (between two steps the ring only shrinks).
+    // when the ring has room (between two steps the ring only shrinks).  (kSplitRefill, below: a band's first step only
+    // requests, its last only commits.)
     pf_count = 0;  // (sweep 1 may leave a request behind: dropped)
-    auto refill_step = [&]() {
+    auto refill_step = [&](auto commits, auto requests, Entry (&buf0)[kChunk], Entry (&buf1)[kChunk], int& count) {
+      constexpr bool kCommits = decltype(commits)::value, kRequests = decltype(requests)::value;
       // (bitwise, not short-circuit: see check_ring)
       const bool refilling =
-          static_cast<int>(pf_count != 0) |
-          (static_cast<int>(L != 0) & static_cast<int>(D - L <= (static_cast<uint32_t>(kRing - kChunk) << kShift)));
+          (kCommits ? static_cast<int>(count != 0) : 0) |
+          (kRequests ? (static_cast<int>(L != 0) & static_cast<int>(D - L <= (static_cast<uint32_t>(kRing - kChunk) << kShift))) : 0);
       if (__builtin_amdgcn_ballot_w64(refilling) != 0ull)
       {
-        if (pf_count > 0) commit(pf0);
-        if (pf_count > 1) commit(pf1);
-        pf_count = 0;
+        if constexpr (kCommits)
+        {
+          if (count > 0) commit(buf0);
+          if (count > 1) commit(buf1);
+          count = 0;
+        }
         const uint32_t resident = D - L;  // (after the commits)
+        if constexpr (kRequests)
         if (static_cast<int>(L != 0) & static_cast<int>(resident <= (static_cast<uint32_t>(kRing - kChunk) << kShift)))
         {
-          LoadChunk(spill_ptr(L - kChunkSlots), pf0);
-          pf_count = 1;
+          LoadChunk(spill_ptr(L - kChunkSlots), buf0);
+          count = 1;
           if (static_cast<int>(L != kChunkSlots) &
               static_cast<int>(resident <= (static_cast<uint32_t>(kRing - 2 * kChunk) << kShift)))
           {
-            LoadChunk(spill_ptr(L - 2 * kChunkSlots), pf1);
-            pf_count = 2;
+            LoadChunk(spill_ptr(L - 2 * kChunkSlots), buf1);
+            count = 2;
           }
         }
       }
     };
     constexpr int kStep = (kChunk < 8) ? 8 : kChunk;  // rows between two refill steps
+    // A band that holds two steps requests at its first (top row) and commits at its last: the requested chunks then live
+    // inside the band's code and not across the loop's back edge, where the allocator renames them on every band -- sixteen
+    // copies and, in front of them, a wait that leaves at most eight of the band's row stores in flight.
+    constexpr bool kSplitRefill = kBand >= 2 * kStep;
 
     if (C::IsUnknown(e3))  // (sweep 1 loads the third entry lazily)
     {
@@ -1069,10 +1105,38 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
     uint32_t above_bit0 = 0;   // class of the first row of the word above
     // sign words: this word's and the next lower word's are in registers, the one below that is on its way
     const int nwords = g.nwords;
-    uint2 info = LoadPair(wave_info + static_cast<int64_t>(nwords - 1) * kWaveSize + lane);
-    uint2 info_below = make_uint2(0u, 0u);
-    if (nwords > 1) info_below = LoadPair(wave_info + static_cast<int64_t>(nwords - 2) * kWaveSize + lane);
-    uint2 info_next = make_uint2(0u, 0u);
+    uint2 info = make_uint2(0u, 0u);
+    [[maybe_unused]] uint2 info_below = make_uint2(0u, 0u), info_next = make_uint2(0u, 0u);  // (kTakeSignWords only)
+    // In blocks (kSignBlocks, the Y pass): the words travel like the class records of that pass's sweep 1.  `blk_cur` holds
+    // the words still to come of the block at work, the next one in its last place (a word that starts moves the others up by one:
+    // fixed registers, no indexed access), in registers on every path; `blk_nxt` is the block below, requested one block --
+    // kInfoBlock * kWord rows -- earlier.  At the top of a block's lowest word that word goes to `info`, the next block
+    // moves up and is taken over (in front of the band's row stores), and the block after it is requested in a region of
+    // its own (see sweep 1 of the Y pass for why two regions).  The band code reads registers: no load of a sign word and
+    // no wait for one between two rotations.
+    [[maybe_unused]] uint2 blk_cur[kInfoBlock], blk_nxt[kInfoBlock];
+    // the kInfoBlock words that end with `last_word` (which may be negative), lowest first
+    [[maybe_unused]] auto load_info_block = [&](int last_word, uint2 (&dst)[kInfoBlock]) {
+#pragma unroll
+      for (int j = 0; j < kInfoBlock; j++)
+        dst[j] = LoadPair(wave_info + static_cast<int64_t>(max(last_word - (kInfoBlock - 1) + j, 0)) * kWaveSize + lane);
+    };
+    if constexpr (kSignBlocks)
+    {
+      load_info_block(nwords - 1, blk_cur);
+      load_info_block(nwords - 1 - kInfoBlock, blk_nxt);
+#pragma unroll
+      for (int j = 0; j < kInfoBlock; j++)
+      {
+        TakeLoaded(blk_cur[j].x);
+        TakeLoaded(blk_cur[j].y);
+      }
+    }
+    else
+    {
+      info = LoadPair(wave_info + static_cast<int64_t>(nwords - 1) * kWaveSize + lane);
+      if (nwords > 1) info_below = LoadPair(wave_info + static_cast<int64_t>(nwords - 2) * kWaveSize + lane);
+    }
     // (the first band needs both at once; taken over here, the loop below sees registers on every path)
     if constexpr (kTakeSignWords)
     {
@@ -1088,21 +1152,74 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
     {
       __builtin_assume(r0 >= 0 && r0 < 16384);
       const int sub = r0 & (kWord - 1);
+      if constexpr (kSignBlocks)
+      {
+        const int w = r0 / kWord;
+        const bool begins = sub + kBand == kWord || r0 == last_band;
+        if (begins)
+        {
+          if (r0 != last_band) above_bit0 = info.x & 1u;
+          info = blk_cur[kInfoBlock - 1];
+#pragma unroll
+          for (int j = kInfoBlock - 1; j > 0; j--) blk_cur[j] = blk_cur[j - 1];
+#ifdef VGT_HOST_EMULATION
+          assert(info.y != kInfoPoison);
+          sign_word_reads++;
+#endif
+        }
+        // (the block's lowest word is in `info` now: the next block moves up.  At the loop's top level, like the record blocks.)
+        int moves_up = static_cast<int>(begins && (nwords - 1 - w) % kInfoBlock == kInfoBlock - 1 && w > 0);
+        if (moves_up)
+        {
+#pragma unroll
+          for (int j = 0; j < kInfoBlock; j++)
+          {
+            blk_cur[j] = blk_nxt[j];
+            TakeLoaded(blk_cur[j].x);
+            TakeLoaded(blk_cur[j].y);
+          }
+        }
+#ifndef VGT_HOST_EMULATION
+        asm volatile("" : "+v"(moves_up));
+        moves_up = __builtin_amdgcn_readfirstlane(moves_up);
+#endif
+        // (below word 0: word 0 again, fetched and never used, instead of a third condition)
+        if (moves_up) load_info_block(w - 1 - kInfoBlock, blk_nxt);
+      }
       if (sub + kBand == kWord || r0 == last_band)
       {
         // a new word starts (from its top)
         const int w = r0 / kWord;
-        if (r0 != last_band)
+        if constexpr (!kSignBlocks)
         {
-          above_bit0 = info.x & 1u;
-          info = info_below;
-          info_below = info_next;
+          if (r0 != last_band)
+          {
+            above_bit0 = info.x & 1u;
+            info = info_below;
+            info_below = info_next;
+          }
+#ifdef VGT_HOST_EMULATION
+          assert(info.y != kInfoPoison);
+          sign_word_reads++;
+#endif
         }
         if (classes)
         {
           const uint32_t sw = info.x;
           const int valid = min(kWord, n - w * kWord);
-          const uint32_t prev_bit = (w > 0) ? (info_below.x >> (kWord - 1)) : (sw & 1u);
+          uint32_t prev_bit = sw & 1u;
+          if constexpr (kSignBlocks)
+          {
+            if (w > 0)  // (the word below is the next to come)
+            {
+              prev_bit = blk_cur[kInfoBlock - 1].x >> (kWord - 1);
+#ifdef VGT_HOST_EMULATION
+              assert(blk_cur[kInfoBlock - 1].y != kInfoPoison);
+#endif
+            }
+          }
+          else if (w > 0)
+            prev_bit = info_below.x >> (kWord - 1);
           xdn_word = sw ^ ((sw << 1) | prev_bit);                    // bit k: row k differs from the row below it
           xup_word = sw ^ ((sw >> 1) | (above_bit0 << (kWord - 1)));  // bit k: row k differs from the row above it
           if (r0 == last_band) xup_word &= ~(1u << (valid - 1));      // nothing above the last row
@@ -1111,14 +1228,12 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
       // X pass: the word two below this band's is requested by EVERY band of a word (the same pair again) and taken over at
       // the band's end (see rows()): request and wait stand in one stretch of code with the band's row stores between
       // them, which the compiler can count.  (A request per word is copied at the loop's end, where the copies of the band
-      // code have joined, behind a wait for everything: a drain of the row stores per band.  That is what the Y pass
-      // still does: there the take-over measured slower, see profiles/r8/sweep_waits.md.)
+      // code have joined, behind a wait for everything: a drain of the row stores per band.  In the Y pass this take-over
+      // measured slower, profiles/r8/sweep_waits.md; its words come in blocks, above.)
       const bool word_begins = sub + kBand == kWord || r0 == last_band;
       [[maybe_unused]] uint2 info_fresh = make_uint2(0u, 0u);
       if constexpr (kTakeSignWords)
         info_fresh = LoadPair(wave_info + static_cast<int64_t>(max(r0 / kWord - 2, 0)) * kWaveSize + lane);
-      else if (word_begins && r0 >= 2 * kWord)
-        info_next = LoadPair(wave_info + static_cast<int64_t>(r0 / kWord - 2) * kWaveSize + lane);
       const uint32_t swb = info.x >> sub;  // bit k: class of row r0 + k
       // distances to the nearest row of the other class below, for 8 rows at a time (dp[k & 7]): counted upwards from
       // the carry of the word and the class changes below the group
@@ -1131,6 +1246,9 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
         constexpr bool kClasses = decltype(with_classes)::value;
         constexpr bool kTable = decltype(from_table)::value;  // every result of this band is below kSmallD2
         constexpr int kGroup = kGuard ? 1 : VGT_SWEEP_GROUP;  // rows finished together (X pass)
+        // (kSplitRefill: the chunks a band requests at its top and commits at its last step -- values of this band alone;
+        // their number stays in pf_count, which a refill_now in between clears, and is zero from one band to the next)
+        [[maybe_unused]] Entry band_pf0[kChunk], band_pf1[kChunk];
         [[maybe_unused]] float& lo_acc = lo_value;  // (named here: the uses below sit in code that depends on kGroup)
         [[maybe_unused]] float& hi_acc = hi_value;
         [[maybe_unused]] uint32_t grp_best[kGroup];
@@ -1138,7 +1256,16 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
 #pragma unroll
         for (int k = kBand - 1; k >= 0; k--)
         {
-          if (k % kStep == kStep - 1) refill_step();
+          if (k % kStep == kStep - 1)
+          {
+            if constexpr (kSplitRefill)
+            {
+              if (k == kBand - 1) refill_step(std::false_type{}, std::true_type{}, band_pf0, band_pf1, pf_count);
+              if (k == kStep - 1) refill_step(std::true_type{}, std::false_type{}, band_pf0, band_pf1, pf_count);
+            }
+            else
+              refill_step(std::true_type{}, std::true_type{}, pf0, pf1, pf_count);
+          }
           if (kClasses && k % 8 == 7)
           {
             const int first = sub + k - 7;  // position of the group's first row in the word
