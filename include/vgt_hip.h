@@ -266,6 +266,23 @@ int vgt_hip_testing_set_host_pipeline_min_voxels(int64_t min_voxels);
  * whatever the number of items: lets the tests and benches run either formulation on any length.  Negative: back to the
  * product's rule (64 rows; the Y pass of launches of at most 1024 items: 128). */
 int vgt_hip_testing_set_short_line_rows(int rows);
+/* After a vgt_hip_sdf_dev call with `workspace_dev` (waits for the stream): counts[0] = Z lines of one class among the
+ * counts[1] lines that pass 1's counting workgroups saw (one workgroup in 32): the ratio the X pass chose its kernel by. */
+int vgt_hip_testing_one_class_counts(vgt_hip_ctx* ctx, const void* workspace_dev, int64_t nx, int64_t ny, int64_t nz,
+                                     uint32_t* counts);
+/* At most `slots` workgroups per launch of the sweep passes (process-wide), so that a small grid is a launch of several rounds
+ * of items; 0 or negative: back to the product's 4096. */
+int vgt_hip_testing_set_sweep_slots(int slots);
+/* Which kernel the plain X pass with 32-bit stack entries runs on a whole single grid (csrc/edt_sweep_kernels.hip, kCoarse;
+ * process-wide): 0 = by scene, the product's rule -- where the launch qualifies (lines of 512 rows and more, two rounds of
+ * items) both kernels are enqueued and pass 1's count of one-class lines decides on the device; 1 = the coarse-hull kernel
+ * wherever it applies (lines of more than 64 rows), whatever it costs; 2 = never.  Results are bit-identical. */
+int vgt_hip_testing_set_coarse_hull(int mode);
+/* After a vgt_hip_sdf_dev call with `workspace_dev` (waits for the stream): which plain X kernel did the work, as the kernel
+ * itself wrote it to its scratch head.  0 = neither (another kernel), 1 = plain, 2 = coarse hull; + 4 when both were
+ * enqueued and the device chose. */
+int vgt_hip_testing_x_pass_choice(vgt_hip_ctx* ctx, const void* workspace_dev, int64_t nx, int64_t ny, int64_t nz,
+                                  int32_t* choice);
 /* At most `workgroups` workgroups per launch of vgt_hip_check_spheres[_dev] (process-wide), so that a few configurations
  * already make its persistent waves stride; 0 or negative: back to the product's limit. */
 int vgt_hip_testing_set_check_spheres_workgroups(int workgroups);

@@ -53,14 +53,20 @@ def main():
                        "--kernel-trace --stats of the same build, AverageNs); bench.py reports the traffic only when "
                        "the kernel it times agrees within 10 % (the profiler's own run is a few per cent slower than an unprofiled one).",
                "kernels": {}}
-    per = collections.defaultdict(lambda: collections.defaultdict(list))
+    # (a pass may be several kernels of which one does the work -- the X pass by scene enqueues two and one returns at
+    # once --: the pass's bytes are those of the kernel that moved the most)
+    by_name = collections.defaultdict(lambda: collections.defaultdict(lambda: collections.defaultdict(list)))
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         files = glob.glob(os.path.join(out, "pmc_" + counter, "*", "*counter_collection.csv"))
         for f in files:
             for row in csv.DictReader(open(f)):
                 k = classify(row["Kernel_Name"])
                 if k and row["Counter_Name"] == counter:
-                    per[k][counter].append(float(row["Counter_Value"]))
+                    by_name[k][row["Kernel_Name"]][counter].append(float(row["Counter_Value"]))
+    per, worker = {}, {}
+    for k, names in by_name.items():
+        worker[k] = max(names, key=lambda name: sum(sum(v) / max(len(v), 1) for v in names[name].values()))
+        per[k] = names[worker[k]]
     for k, d in per.items():
         fetch = sum(d["FETCH_SIZE"]) / max(len(d["FETCH_SIZE"]), 1) * 1024.0
         write = sum(d["WRITE_SIZE"]) / max(len(d["WRITE_SIZE"]), 1) * 1024.0
@@ -74,11 +80,15 @@ def main():
         rows = list(csv.reader(open(stats[0])))
         with open(os.path.join(out, "rocprof_kernel_stats.csv"), "w") as fh:
             csv.writer(fh).writerows(rows[:12])
-        for row in csv.DictReader(open(stats[0])):
-            k = classify(row["Name"])
-            if k in summary["kernels"] and "kernel_ns" not in summary["kernels"][k]:
-                summary["kernels"][k]["kernel_ns"] = float(row["AverageNs"])
-                summary["kernels"][k]["kernel_name"] = row["Name"][:160]
+        # (the working kernel's row; should the two files spell the names differently, the pass's first row -- the stats are
+        # sorted by total time)
+        for exact in (True, False):
+            for row in csv.DictReader(open(stats[0])):
+                k = classify(row["Name"])
+                if k in summary["kernels"] and "kernel_ns" not in summary["kernels"][k] and \
+                        (not exact or row["Name"][:140] == worker[k][:140]):
+                    summary["kernels"][k]["kernel_ns"] = float(row["AverageNs"])
+                    summary["kernels"][k]["kernel_name"] = row["Name"][:160]
     json.dump(summary, open(os.path.join(out, "pmc_hbm_traffic.json"), "w"), indent=1)
     # SQ counters of the three SDF kernels (one pass, 8 SQ slots)
     sq = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -15,9 +15,16 @@ for f in glob.glob("/tmp/pmc_v/*/*counter_collection.csv"):
         n = row["Kernel_Name"]
         if "PassKernel" not in n: continue
         k = "X" if ("float" in n.split("PassKernel")[1][:20]) else "Y"
-        acc[k][row["Counter_Name"]].append(float(row["Counter_Value"]))
-for k in sorted(acc):
-    v = {c: sum(x) / len(x) for c, x in acc[k].items()}
+        acc[(k, n)][row["Counter_Name"]].append(float(row["Counter_Value"]))
+# (a pass may be two kernels of which one returns at once -- the X pass by scene --: the one that executed the most counts)
+work = {}
+for (k, n), counters in acc.items():
+    valu = sum(counters["SQ_INSTS_VALU"]) / len(counters["SQ_INSTS_VALU"])
+    if k not in work or valu > work[k][0]:
+        work[k] = (valu, counters, n)
+for k in sorted(work):
+    v = {c: sum(x) / len(x) for c, x in work[k][1].items()}
+    print(sys.argv[1], k, "kernel: SweepPassKernel" + work[k][2].split("PassKernel")[1][:48])
     print(sys.argv[1], k, "VALU/voxel %.1f  SALU/voxel %.1f  LDS/voxel %.2f  wait %.2f" % (v["SQ_INSTS_VALU"] * 64 / 2**30, v["SQ_INSTS_SALU"] * 64 / 2**30, v["SQ_INSTS_LDS"] * 64 / 2**30, v["SQ_WAIT_ANY"] / v["SQ_WAVE_CYCLES"]))
 PY
 done

@@ -221,6 +221,10 @@ TESTING_SIGNATURES = {
     "vgt_hip_debug_finalize_check": (_int, [_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _p, _p]),
     "vgt_hip_testing_set_host_pipeline_min_voxels": (_int, [ctypes.c_int64]),
     "vgt_hip_testing_set_short_line_rows": (_int, [_int]),
+    "vgt_hip_testing_set_coarse_hull": (_int, [_int]),
+    "vgt_hip_testing_set_sweep_slots": (_int, [_int]),
+    "vgt_hip_testing_one_class_counts": (_int, [_p, _p, _i64, _i64, _i64, _p]),
+    "vgt_hip_testing_x_pass_choice": (_int, [_p, _p, _i64, _i64, _i64, _p]),
     "vgt_hip_testing_set_check_spheres_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_sphere_volume_workgroups": (_int, [_int]),
     "vgt_hip_testing_set_align_workgroups": (_int, [_int]),
@@ -1626,6 +1630,32 @@ class Context:
         """Testing library only: lines of at most `rows` rows take the short-line kernels whatever the item count
         (0 = sweeps everywhere, negative = back to the product's rule)."""
         check(self._lib.vgt_hip_testing_set_short_line_rows(int(rows)))
+
+    def one_class_counts(self, workspace_ptr, shape):
+        """Testing library only: (Z lines of one class, lines counted) of pass 1's sample in the last sdf_dev call with
+        this workspace (waits for the stream)."""
+        counts = (ctypes.c_uint32 * 2)()
+        check(self._lib.vgt_hip_testing_one_class_counts(self.handle, _ptr(workspace_ptr), *[int(v) for v in shape],
+                                                         ctypes.cast(counts, ctypes.c_void_p)))
+        return int(counts[0]), int(counts[1])
+
+    def set_sweep_slots(self, slots):
+        """Testing library only (process-wide there): at most `slots` workgroups per sweep launch (0 = back to the
+        product's 4096)."""
+        check(self._lib.vgt_hip_testing_set_sweep_slots(int(slots)))
+
+    def set_coarse_hull(self, mode):
+        """Testing library only (process-wide there): the plain X pass's kernel on whole single grids -- 0 by scene (the
+        product's rule), 1 the coarse-hull kernel wherever it applies, 2 never."""
+        check(self._lib.vgt_hip_testing_set_coarse_hull(int(mode)))
+
+    def x_pass_choice(self, workspace_ptr, shape):
+        """Testing library only: which plain X kernel did the work of the last sdf_dev call with this workspace (waits for
+        the stream): 0 neither, 1 plain, 2 coarse hull; + 4 when both were enqueued and the device chose."""
+        choice = ctypes.c_int32(-1)
+        check(self._lib.vgt_hip_testing_x_pass_choice(self.handle, _ptr(workspace_ptr), *[int(v) for v in shape],
+                                                      ctypes.byref(choice)))
+        return int(choice.value)
 
     def set_check_spheres_workgroups(self, workgroups):
         """Testing library only (process-wide there): at most `workgroups` workgroups per check_spheres launch (0 = back

@@ -72,6 +72,9 @@ __global__ void InitMinMaxKernel(uint32_t* minmax_enc, int count)
     minmax_enc[2 * i] = 0xffffffffu;
     minmax_enc[2 * i + 1] = 0u;
   }
+  // (one grid: pass 1's counts of one-class lines and of lines seen, which the X pass chooses its kernel by, start at zero
+  // in the same dispatch)
+  if (count == 1 && threadIdx.x == 0) minmax_enc[kOneClassWord] = minmax_enc[kOneClassWord + 1] = 0u;
 }
 __global__ void DecodeMinMaxKernel(const uint32_t* minmax_enc, float* out, int count)
 {

@@ -16,7 +16,9 @@ struct SweepGeom
   int outers;            // outer indices
   int groups;            // workgroup b draws from counter b % groups, which deals the outer indices = b (mod groups)
   int nwords;            // ceil(n / 32)
-  int chunks;            // spill chunks per lane
+  int chunks;            // spill chunks per lane (a launch that may run the coarse-hull X kernel: + CoarseChunks(n))
+  int by_scene;          // X pass launched as a pair: a kernel reads pass 1's one-class line counts first and leaves at once
+                         // unless the scene is its own
   int64_t row_stride;    // elements between consecutive rows
   int64_t outer_stride;  // elements between consecutive outer indices
   int nx, ny;

@@ -44,9 +44,16 @@
 //     than for vector instructions; a chunk of the ring is addressed ONCE (it never wraps), which turns its eight LDS
 //     accesses into four paired instructions; conditions of rare paths are combined bitwise, not with || and &&.
 //
-//   * What rounds 5 and 6 measured and did not keep (profiles/r5, r6/experiments.md): a coarse hull in front of the X sweep,
-//     handing lower halves of second sweeps to idle workgroups, a packed-word form of sweep 1 (fewer instructions per row,
-//     hardly less time: a row costs its dependent chain, not its instruction count).
+//   * A coarse hull in front of the plain X sweep, on sparse scenes only (kCoarse: an instantiation of its own).  The line is
+//     swept over every 32nd row first; a row strictly above the chord between the two vertices of that hull around it is
+//     no vertex of the line's hull and never touches the stack: 70 % fewer pops in sweep 1.  On a dense scene the subsample
+//     is convex and the first sweep buys nothing, and a launch of one round of items ends with its slowest item either way
+//     (round 5 measured +6 % on both), so LaunchSweep enqueues the plain and the coarse kernel one behind the other where
+//     the launch qualifies, and each reads pass 1's count of one-class Z lines first and returns at once unless the scene is
+//     its own: no host synchronisation, no kernel waits for another (profiles/r10/coarse_by_scene.md).
+//   * What rounds 5 and 6 measured and did not keep (profiles/r5, r6/experiments.md): handing lower halves of second sweeps
+//     to idle workgroups, a packed-word form of sweep 1 (fewer instructions per row, hardly less time: a row costs its
+//     dependent chain, not its instruction count).
 //
 // The kernels are bound by the latency of their dependent chains and by what their waves wait for (a third of their
 // cycles in s_waitcnt: profiles/r8/sweep_waits.md), not by HBM and not by instruction issue: rows are processed kBand at a
@@ -60,6 +67,9 @@
 
 #include <cstdlib>
 #include <type_traits>
+#ifdef VGT_HOST_EMULATION
+#include <vector>
+#endif
 
 namespace vgt
 {
@@ -104,6 +114,26 @@ static_assert(kInfoBlock >= 1, "sizes");
 constexpr int kSweepGroups = VGT_SWEEP_GROUPS;  // work counters (= XCDs of an MI355X)
 constexpr int kCounterStride = 32;              // ints between two counters (128 bytes)
 constexpr int kMaxSweepSlots = 4096;
+// ---- The coarse-hull form of the plain X pass with 32-bit entries (kCoarse, see SweepPassKernel) ----
+constexpr int kCoarseStride = 32;   // every how many rows the coarse hull takes one (a multiple of kBand; 8 and 64: worse, r5)
+constexpr int kCoarseShortest = 2 * kCoarseStride + 1;  // rows of the shortest line the kernel takes (and has scratch for)
+#ifdef VGT_HOST_EMULATION
+constexpr int kCoarseMinRows = kCoarseShortest;  // (the CPU tests run it on every line it takes)
+constexpr int kCoarseMinRounds = 0;
+#else
+constexpr int kCoarseMinRows = 512;  // shorter lines: the first sweep does not pay (profiles/r5/experiments.md)
+constexpr int kCoarseMinRounds = 2;  // launches of fewer rounds of items end with their slowest item: +5.8 % there (r5)
+#endif
+// Shares of one-class Z lines (pass 1's count over the lines it counted) between which the coarse-hull kernel runs, in
+// 32nds: [18/32, 27/32).  From the table in profiles/r10/coarse_by_scene.md: the kernel wins where large obstacles stand in
+// free space (D1: 0.77 at 1024^3, 0.60 at 1024 x 512 x 512) and loses on dense scenes (salt p = 0.001: 0.36, p = 0.01 and
+// unknown mix: 0.00) AND on nearly empty ones with isolated voxels (salt p = 1e-4: 0.90, 1e-5: 0.99), whose far fields are
+// convex at the subsample's scale; each bound lies midway between the nearest measured scenes on either side.
+constexpr uint32_t kCoarseShareLow = 18, kCoarseShareHigh = 27, kCoarseShareDen = 32;
+// Chunks of 8 entries per lane of a slot's coarse area: the subsample's hull at full depth behind the four sentinels.
+__host__ __device__ constexpr int CoarseChunks(int n) { return (n / kCoarseStride + 1 + 4 + 7) / 8 + 1; }
+// scratch head, second int: which of the plain X kernels did the work (1 = plain, 2 = coarse hull; + 4 in a launch by scene)
+constexpr int kChoiceWord = 1;
 template <bool kPacked>
 struct RingShape
 {
@@ -111,6 +141,8 @@ struct RingShape
   static constexpr int kChunk = kPacked ? VGT_SWEEP_CHUNK : VGT_SWEEP_CHUNK_WIDE;
   static_assert(kBand % kChunk == 0 && kRing >= 4 * kChunk && (kRing & (kRing - 1)) == 0 && kChunk % 4 == 0, "sizes");
 };
+// (the coarse area is laid out in chunks of eight entries: diagnostic builds with another chunk size go without that kernel)
+constexpr bool kCoarseBuilt = RingShape<true>::kChunk == 8;
 constexpr int kFar = 32768;              // "no row of the other class": kFar^2 is above every real squared distance
 static_assert(kWord % kBand == 0 && kBand % 2 == 0, "sizes");
 #ifdef VGT_HOST_EMULATION
@@ -123,6 +155,13 @@ uint64_t ring_checks = 0, ring_spills = 0;
 // (loads may fetch more) is poison: it reads what sweep 1 wrote for this item.  A carry is at most kFar, never the poison.
 constexpr uint32_t kInfoPoison = 0xdeadbeefu;
 uint64_t sign_word_reads = 0;
+// Rows with a site that the coarse-hull kernel's chord test kept off the stack (item, lane, row): the drivers check them
+// against the hull of the whole line.
+struct CoarseDrop
+{
+  int item, lane, row;
+};
+std::vector<CoarseDrop> coarse_dropped;
 #endif
 
 
@@ -430,7 +469,16 @@ __device__ __forceinline__ void WaveMinMax(float lo_value, float hi_value, uint3
 }
 
 // kPlain (X pass only): no virtual border and a resolution inside the fast conversion's range.
-template <typename InT, typename OutT, bool kFinal, bool kPacked, bool kPlain>
+// kCoarse (the plain X pass with 32-bit entries; an instantiation of its own, which only sparse scenes in launches of
+// several rounds run): a COARSE HULL in front of the sweep.  On a sparse scene the X pass pushes 6.7 sites per lane and 16
+// rows of which 2 stay -- the others are popped by sites far away, which no local test sees coming.  So the line is swept
+// twice: first every kCoarseStride-th row alone, through the same stack code; the hull of that subsample (a dozen vertices
+// per line on average) goes to the slot's scratch, the stack starts again, and in the sweep proper a row strictly above the
+// chord between the two subsample vertices around it never touches the stack -- it lies above a segment between two real
+// sites, so it is no vertex of the line's hull, whatever else the line holds.  Sweep 2 is the same code.  On a dense scene
+// the subsample is convex, the filter removes nothing and the first sweep is pure cost: LaunchSweep enqueues both kernels and
+// each leaves at once unless pass 1's count of one-class lines says the scene is its own (g.by_scene).
+template <typename InT, typename OutT, bool kFinal, bool kPacked, bool kPlain, bool kCoarse = false>
 __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(const InT* __restrict__ in,
                                                                             OutT* __restrict__ out,
                                                                             unsigned char* __restrict__ spill,
@@ -449,6 +497,23 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   constexpr bool kSignBlocks = !kFinal;
   constexpr bool kTakeSignWords = !kSignBlocks;
   static_assert(!(kRecords && kFinal), "records feed the Y pass");
+  static_assert(!kCoarse || (kFinal && kPacked && kPlain), "the coarse hull is built for the plain X pass with 32-bit entries");
+  // The two kernels a launch by scene is made of: the scene's share of one-class lines decides which of them works, and the
+  // other returns before it touches the LDS or a work counter.  Nobody waits for anybody.
+  if constexpr (kFinal && kPacked && kPlain)
+  {
+    if (g.by_scene)
+    {
+      // (a sample of at most 2^23 lines: the products stay inside 32 bits)
+      const uint32_t one_class = __builtin_amdgcn_readfirstlane(minmax_enc[kOneClassWord]) * kCoarseShareDen;
+      const uint32_t counted = __builtin_amdgcn_readfirstlane(minmax_enc[kOneClassWord + 1]);
+      const bool coarse_scene = static_cast<int>(one_class >= counted * kCoarseShareLow) &
+                                static_cast<int>(one_class < counted * kCoarseShareHigh);
+      if (coarse_scene != kCoarse) return;
+    }
+    // (read by the testing library alone, vgt_hip_testing_x_pass_choice: one store by one lane of workgroup 0 per launch)
+    if (blockIdx.x == 0 && threadIdx.x == 0) work_counter[kChoiceWord] = (kCoarse ? 2 : 1) + (g.by_scene ? 4 : 0);
+  }
   constexpr int kRing = RingShape<kPacked>::kRing;
   constexpr int kChunk = RingShape<kPacked>::kChunk;
   constexpr int32_t kLimit = C::kSentinelG;  // values at or above: no site
@@ -468,6 +533,9 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
   // the lines it works on, so the scratch is sized by the number of workgroups in flight, not by the grid.
   unsigned char* const own_spill = spill + static_cast<int64_t>(blockIdx.x) * g.chunks * (kWaveSize * kChunkBytes);
   uint2* const own_info = word_info + static_cast<int64_t>(blockIdx.x) * (g.nwords + 1) * kWaveSize;
+  // (kCoarse: the slot's coarse area, the last CoarseChunks(n) chunks of its spill area, laid out like the rest of it)
+  [[maybe_unused]] unsigned char* const own_coarse =
+      kCoarse ? own_spill + static_cast<int64_t>(g.chunks - CoarseChunks(g.n)) * (kWaveSize * kChunkBytes) : nullptr;
   const uint32_t lane_entry = static_cast<uint32_t>(lane) * kEntryBytes;  // byte offset of this lane inside a ring slot
   const uint32_t lane_chunk = static_cast<uint32_t>(lane) * kChunkBytes;  // ... inside a row of spill chunks
   float lo_value = INFINITY, hi_value = -INFINITY;
@@ -633,11 +701,13 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
     auto check_ring = [&]() {
       // Two separate things.  Rare: a ring that pops have nearly emptied, and the chunk requested for it at the last check
       // (kept apart and hinted cold, so that what it does to pf0's registers stays off the common path).
+      // (kCoarse: not there.  Behind the coarse hull a pop is rare and a pop that reaches a spilled chunk rarer still --
+      // it then waits for its chunk, refill_now -- and the eight registers of pf0 are what that kernel's chord state lives in.)
       const uint32_t resident = D - L;
       // (bitwise, not short-circuit: the compiler turns `||` / `&&` of these comparisons into nested exec-mask regions)
-      const bool refilling = static_cast<int>(pf_count != 0) |
-                             (static_cast<int>(L != 0) & static_cast<int>(resident <= kChunkSlots));
-      if (__builtin_expect(__builtin_amdgcn_ballot_w64(refilling) != 0ull, 0))
+      const bool refilling = !kCoarse && (static_cast<int>(pf_count != 0) |
+                                          (static_cast<int>(L != 0) & static_cast<int>(resident <= kChunkSlots)));
+      if (!kCoarse && __builtin_expect(__builtin_amdgcn_ballot_w64(refilling) != 0ull, 0))
       {
         VGT_COLD_PATH();
         // a chunk requested at the last check goes into the ring (the ring had at most kChunk entries then and
@@ -919,7 +989,8 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
         }
       };
       int32_t nxt[kBand];
-      load_band(nxt, 0);
+      // (kCoarse: the first band is requested behind the first sweep, whose subsample rows need the registers)
+      if constexpr (!kCoarse) load_band(nxt, 0);
       // Hull point of a row.  A row that is no site gets G = kNoSiteG + q^2: above every real hull point by more than any
       // site can make up before the last row (site()'s first test rejects it: kNoSiteG - G > 2 (n - 1)^2 for every real G of
       // either entry kind) and small enough that differences of two hull points never overflow.  So no row needs a "valid"
@@ -937,11 +1008,140 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
       // successor -- that is every row but the ends.
       // (with "no site" as a huge hull point the test needs no flags: next to such a neighbour the site is kept, and a row
       // that is no site itself is dropped here or rejected by site())
+      // ---- kCoarse: the first sweep, over every kCoarseStride-th row, and what the sweep proper keeps of it ----
+      // The subsample hull's vertices around the band at work: (low_G, low_row) the one at or below the band's first row
+      // (row -1: none yet), chb the next one ahead as it lies in the scratch ("unknown" = none), chc the one after chb,
+      // fetched a band or more before it is needed, ch_next its index.  Two ahead: the chord needs chb's successor the moment
+      // chb is reached.  (A lane reads back what it stored itself, like the spill chunks: no wait between the two.)
+      [[maybe_unused]] Entry chb = C::Unknown(), chc = C::Unknown();
+      [[maybe_unused]] int32_t low_G = 0;
+      [[maybe_unused]] int low_row = -1, ch_next = 0;
+      [[maybe_unused]] auto coarse_entry = [&](int index) -> Entry {
+        const uint32_t chunk_first = static_cast<uint32_t>(index / kChunk) * kChunkSlots;
+        return reinterpret_cast<const Entry*>(own_coarse + (chunk_first + lane_chunk))[index % kChunk];
+      };
+      if constexpr (kCoarse)
+      {
+        static_assert(kCoarseStride % kBand == 0, "a band never holds two vertices of the subsample's hull");
+        static_assert(kChunk == 8, "CoarseChunks counts chunks of eight entries");
+        // (the first sweep spills into the coarse area, where its result is to lie anyway)
+        wave_spill = own_coarse;
+        constexpr int kBatch = 2 * kBand;  // subsample rows in flight at a time: one memory latency for a 1024-row line
+        for (int s0 = 0; s0 < n; s0 += kBatch * kCoarseStride)
+        {
+          int32_t sub[kBatch];
+          {
+            // (rows past the line's end repeat the last subsample row and are not used)
+            const int last_sub = (n - 1) / kCoarseStride * kCoarseStride;
+#pragma unroll
+            for (int k = 0; k < kBatch; k++)
+            {
+              const int q = min(s0 + k * kCoarseStride, last_sub);
+              const VGT_GLOBAL InT* row_in = UniformPointer(GlobalPointer(wave_in + static_cast<int64_t>(q) * rstride));
+              sub[k] = static_cast<int32_t>(*LaneAddress(row_in, lane_bytes));
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < kBatch; k++)
+          {
+            const int q = s0 + k * kCoarseStride;
+            if (q < n)
+            {
+              if (k % kChunk == 0) check_ring();
+              int32_t G_sub;
+              decode(sub[k], q, G_sub);
+              site(q, G_sub, true);
+            }
+          }
+        }
+        // The subsample hull's first two vertices (entries 4 and 5: behind the sentinels) straight from the ring, where they
+        // still are unless the first sweep spilled (33 rows and the sentinels: rare) -- no round trip through memory at
+        // the start of the sweep proper.
+        const bool in_ring = L == 0u;
+        // The whole stack into the coarse area (the ring's entries join the chunks spilled on the way), "unknown" behind its
+        // last entry -- in the same chunk, or in one more that holds nothing else: the walk ends there.
+        for (uint32_t first = L; __builtin_amdgcn_ballot_w64(first <= D) != 0ull;)
+        {
+          if (first <= D)
+          {
+            Entry buf[kChunk];
+            Entry* const slots = chunk_in_ring(first);
+#pragma unroll
+            for (int j = 0; j < kChunk; j++)
+            {
+              buf[j] = chunk_slot(slots, first, j);
+              if (first + (static_cast<uint32_t>(j) << kShift) >= D) buf[j] = C::Unknown();
+            }
+            StoreChunk(spill_ptr(first), buf);
+            first += kChunkSlots;
+          }
+        }
+        // (a stack of depth 4 holds the sentinels alone: "unknown" in both)
+        if (in_ring)
+        {
+          if (D > (4u << kShift)) chb = ring_ref(4u << kShift);
+          if (D > (5u << kShift)) chc = ring_ref(5u << kShift);
+        }
+        ch_next = 5;
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!in_ring) != 0ull, 0))
+        {
+          VGT_COLD_PATH();
+          if (!in_ring)
+          {
+            chb = coarse_entry(4);
+            if (!C::IsUnknown(chb)) chc = coarse_entry(5);
+          }
+        }
+        // the stack starts again
+        wave_spill = own_spill;
+        D = 4u << kShift;
+        L = 0;
+        Gt = C::kSentinelG;
+        nB = 1;
+        rt = 0;
+        A = 0;
+        e3 = C::Pack(C::kSentinelG + 2, 0);
+        pf_count = 0;
+        ring_ref(0u << kShift) = C::Pack(0, 0);
+        ring_ref(1u << kShift) = C::Pack(C::kSentinelG + 2, 0);
+        ring_ref(2u << kShift) = C::Pack(C::kSentinelG + 1, 0);
+        ring_ref(3u << kShift) = C::Pack(C::kSentinelG, 0);
+        load_band(nxt, 0);
+      }
       int32_t G_prev = kNoSiteG, G_cur = 0;
       decode(nxt[0], 0, G_cur);
       for (int r0 = 0; r0 < n; r0 += kBand)
       {
         __builtin_assume(r0 >= 0 && r0 < 16384);
+        // (kCoarse) the chord over this band: from the vertex at or below its first row to the next one, which lies beyond
+        // its last row; no chord (width 0: the test below then never fires) before the first and behind the last vertex
+        [[maybe_unused]] int32_t chord_G = 0, chord_dG = 0;
+        [[maybe_unused]] int chord_row = 0, chord_width = 0;
+        if constexpr (kCoarse)
+        {
+          const bool arrived = static_cast<int>(!C::IsUnknown(chb)) & static_cast<int>(r0 >= C::Row(chb));
+          if (__builtin_amdgcn_ballot_w64(arrived) != 0ull)
+          {
+            if (arrived)
+            {
+              low_G = C::G(chb);
+              low_row = C::Row(chb);
+              chb = chc;
+              if (!C::IsUnknown(chc))
+              {
+                ch_next++;
+                chc = coarse_entry(ch_next);
+              }
+            }
+          }
+          chord_G = low_G;
+          chord_row = low_row;
+          if (static_cast<int>(low_row >= 0) & static_cast<int>(!C::IsUnknown(chb)))
+          {
+            chord_dG = C::G(chb) - low_G;
+            chord_width = C::Row(chb) - low_row;
+          }
+        }
         int32_t cur[kBand];
 #pragma unroll
         for (int k = 0; k < kBand; k++) cur[k] = nxt[k];
@@ -972,7 +1172,18 @@ __global__ __launch_bounds__(kWaveSize, VGT_SWEEP_WAVES) void SweepPassKernel(co
               int32_t G_next = kNoSiteG + (q + 1) * (q + 1);  // (past the last row: no site)
               // (every row of a full band but its last has a successor: no test)
               if ((!kGuard && k + 1 < kBand) || q + 1 < n) decode(k + 1 < kBand ? cur[k + 1] : nxt[0], q + 1, G_next);
-              site(q, G_cur, G_cur - G_prev < G_next - G_cur);
+              if constexpr (kCoarse)
+              {
+                // strictly above the chord of the subsample's hull over this row: no vertex of the line's hull
+                const bool above = static_cast<int64_t>(G_cur - chord_G) * chord_width -
+                                       static_cast<int64_t>(chord_dG) * (q - chord_row) > 0;
+#ifdef VGT_HOST_EMULATION
+                if (above && G_cur < kNoSiteG) coarse_dropped.push_back(CoarseDrop{item, lane, q});
+#endif
+                site(q, G_cur, static_cast<int>(G_cur - G_prev < G_next - G_cur) & static_cast<int>(!above));
+              }
+              else
+                site(q, G_cur, G_cur - G_prev < G_next - G_cur);
               G_prev = G_cur;
               G_cur = G_next;
             }
@@ -1523,12 +1734,20 @@ bool PackedEntries(int64_t n, int64_t max_input)
   return n <= 1024 && max_input + (n - 1) * (n - 1) < Codec<true>::kSentinelG;
 }
 
-// Scratch of one slot: the spill chunks of its 64 lines (every entry of a full-depth stack) and one (sign word, carry) pair
-// per 32 rows and lane.
+// Chunks per lane of a slot's coarse area (the coarse-hull X kernel: 32-bit entries, lines of kCoarseShortest rows and more;
+// reserved whichever kernel runs, so that a launch uses the same slots either way).
+int64_t CoarseAreaChunks(int64_t n, bool packed)
+{
+  return (kCoarseBuilt && packed && n >= kCoarseShortest) ? CoarseChunks(static_cast<int>(n)) : 0;
+}
+
+// Scratch of one slot: the spill chunks of its 64 lines (every entry of a full-depth stack), the coarse area, and one (sign
+// word, carry) pair per 32 rows and lane.
 size_t SlotScratchBytes(int64_t n, bool packed)
 {
   const int64_t nwords = (n + kWord - 1) / kWord;
-  const size_t spill = packed ? SpillChunks(n, RingShape<true>::kChunk) * kWaveSize * RingShape<true>::kChunk * sizeof(uint32_t)
+  const size_t spill = packed ? (SpillChunks(n, RingShape<true>::kChunk) + CoarseAreaChunks(n, packed)) * kWaveSize *
+                                    RingShape<true>::kChunk * sizeof(uint32_t)
                               : SpillChunks(n, RingShape<false>::kChunk) * kWaveSize * RingShape<false>::kChunk * sizeof(uint2);
   return spill + static_cast<size_t>(nwords + 1) * kWaveSize * sizeof(uint2);
 }
@@ -1546,7 +1765,7 @@ size_t PassScratchBytes(int64_t n, int64_t items, int64_t max_input)
 
 template <typename InT, typename OutT, bool kFinal>
 hipError_t LaunchSweep(const InT* in, OutT* out, void* scratch, size_t scratch_bytes, uint32_t* minmax_enc, SweepGeom g,
-                       int64_t outer_count, int64_t max_input, hipStream_t stream)
+                       int64_t outer_count, int64_t max_input, hipStream_t stream, int x_kernel = kXKernelPlain)
 {
   g.zsegs = (g.nz + kWaveSize - 1) / kWaveSize;
   g.nwords = (g.n + kWord - 1) / kWord;
@@ -1562,6 +1781,9 @@ hipError_t LaunchSweep(const InT* in, OutT* out, void* scratch, size_t scratch_b
   }
   const bool packed = PackedEntries(g.n, max_input);
   int64_t slots = items < kSweepSlots ? items : kSweepSlots;
+#ifndef VGT_HOST_EMULATION
+  if (const int told = SweepSlotsOverride(); told > 0 && told < slots) slots = told;  // (testing builds: launches of many rounds on small grids)
+#endif
   {
     // as many slots as the scratch holds (see PassScratchBytes)
     const size_t per_slot = SlotScratchBytes(g.n, packed);
@@ -1573,6 +1795,14 @@ hipError_t LaunchSweep(const InT* in, OutT* out, void* scratch, size_t scratch_b
   g.groups = static_cast<int>(slots < kSweepGroups ? slots : kSweepGroups);
   const int chunk = packed ? RingShape<true>::kChunk : RingShape<false>::kChunk;
   g.chunks = static_cast<int>(SpillChunks(g.n, chunk));
+  // the plain X pass: no virtual border, resolution inside the range of the fast final conversion
+  const bool general = kFinal && (g.add_virtual_border || !(g.resolution > 1.0e-30 && g.resolution < 1.0e30));
+  // The coarse-hull kernel: where the caller allows it (a whole single grid) and the kernel applies; by scene, only where
+  // it has been measured to pay as well: lines of kCoarseMinRows rows in launches of kCoarseMinRounds rounds of items.
+  bool coarse = kFinal && kCoarseBuilt && x_kernel != kXKernelPlain && packed && !general && g.batch_outers == g.outers && g.n >= kCoarseShortest;
+  if (x_kernel == kXKernelByScene) coarse = coarse && g.n >= kCoarseMinRows && items >= kCoarseMinRounds * slots;
+  if (coarse) g.chunks += CoarseChunks(g.n);  // (the slots were sized for it: SlotScratchBytes)
+  if (coarse && x_kernel == kXKernelByScene) g.by_scene = 1;
   // scratch: work counter | spill chunks of every slot | one (sign word, carry) pair per 32 rows, lane and slot
   char* bytes = static_cast<char*>(scratch);
   int* counter = reinterpret_cast<int*>(bytes);
@@ -1584,8 +1814,6 @@ hipError_t LaunchSweep(const InT* in, OutT* out, void* scratch, size_t scratch_b
   *counter = 0;
 #endif
   const dim3 grid(static_cast<unsigned>(slots)), block(kWaveSize);
-  // the plain X pass: no virtual border, resolution inside the range of the fast final conversion
-  const bool general = kFinal && (g.add_virtual_border || !(g.resolution > 1.0e-30 && g.resolution < 1.0e30));
 #ifndef VGT_HOST_EMULATION
   {
     // the work counters start at zero
@@ -1596,6 +1824,17 @@ hipError_t LaunchSweep(const InT* in, OutT* out, void* scratch, size_t scratch_b
 #define VGT_LAUNCH_SWEEP(PACKED, PLAIN)                                                                             \
   hipLaunchKernelGGL((SweepPassKernel<InT, OutT, kFinal, PACKED, PLAIN>), grid, block, 0, stream, in, out, spill, info, \
                      minmax_enc, counter, g)
+  if constexpr (kFinal && kCoarseBuilt)
+  {
+    if (coarse)
+    {
+      // By scene: both kernels behind the one clearing of the counters; the one whose scene it is not returns at once.
+      if (g.by_scene) VGT_LAUNCH_SWEEP(true, true);
+      hipLaunchKernelGGL((SweepPassKernel<InT, OutT, true, true, true, true>), grid, block, 0, stream, in, out, spill, info,
+                         minmax_enc, counter, g);
+      return hipGetLastError();
+    }
+  }
   if (packed && general)
     VGT_LAUNCH_SWEEP(true, !kFinal);
   else if (packed)
@@ -1667,8 +1906,12 @@ hipError_t LaunchPassXSweepFinalizeRange(const int32_t* in32, float* sdf, uint32
     g.outer_begin = static_cast<int>(outer_begin);
     outer_count = outer_count_or_all;
   }
+  // (the kernel by scene: a whole single grid whose pass 1 has counted its one-class lines next to these extrema)
+  int x_kernel = p.x_kernel;
+  if (outer_count_or_all >= 0 || p.batch > 1) x_kernel = kXKernelPlain;
+  if (x_kernel == kXKernelByScene && p.one_class_lines != minmax_enc + kOneClassWord) x_kernel = kXKernelPlain;
   return LaunchSweep<int32_t, float, true>(in32, sdf, scratch.ptr, scratch.bytes, minmax_enc, g, outer_count,
-                                           MaxInputX(p), stream);
+                                           MaxInputX(p), stream, x_kernel);
 }
 
 hipError_t LaunchPassXSweepFinalize(const int32_t* in32, float* sdf, uint32_t* minmax_enc, SweepScratch scratch,

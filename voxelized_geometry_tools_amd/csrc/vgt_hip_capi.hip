@@ -169,6 +169,11 @@ thread_local std::string g_last_error;
 // What vgt_hip_testing_set_short_line_rows told the line passes (vgt::ShortLineOverride), -1 = nothing.  Only that hook
 // stores to it, and only the testing library has the hook.
 std::atomic<int> g_short_line_override{-1};
+// What vgt_hip_testing_set_sweep_slots told the sweep launches (vgt::SweepSlotsOverride), 0 = nothing.
+std::atomic<int> g_sweep_slots_override{0};
+// What vgt_hip_testing_set_coarse_hull told the X pass: vgt::kXKernelByScene (the product's only mode), kXKernelCoarse or
+// kXKernelPlain.  Only that hook stores to it.
+std::atomic<int> g_coarse_hull_mode{vgt::kXKernelByScene};
 // What vgt_hip_testing_set_check_spheres_workgroups told the sphere-model check, 0 = nothing (the launcher's own limit).
 std::atomic<int> g_check_spheres_workgroups{0};
 // The same from vgt_hip_testing_set_align_workgroups, for the evaluation launches of the cloud alignment.
@@ -201,6 +206,7 @@ namespace vgt
 void SetLastError(const std::string& message) { g_last_error = message; }
 hipStream_t ContextStream(const vgt_hip_ctx* ctx) { return ctx->stream; }
 int ShortLineOverride() { return g_short_line_override.load(); }
+int SweepSlotsOverride() { return g_sweep_slots_override.load(); }
 }  // namespace vgt
 namespace
 {
@@ -465,6 +471,18 @@ hipError_t LaunchPassTwo(const SdfWorkspace& ws, const vgt::SdfParams& part, int
   }
   return vgt::LaunchPassYSweepRecords(ws.records + first_slice * vgt::RecordWords(part.nz) * part.ny,
                                       ws.t32 + voxel_offset, ws.sweep_scratch, part, s);
+}
+// A whole single grid on the default pipeline: pass 1 counts the grid's one-class lines into the word next to the extrema
+// and the X pass chooses its kernel by that count, on the device (edt_sweep_kernels.hip: plain or coarse hull; both are
+// enqueued where the launch qualifies and one returns at once).  Every other caller keeps the plain kernel.
+vgt::SdfParams WithKernelByScene(const SdfWorkspace& ws, vgt::SdfParams p)
+{
+  if (p.batch == 1 && ws.records)
+  {
+    p.one_class_lines = ws.minmax_enc + vgt::kOneClassWord;
+    p.x_kernel = g_coarse_hull_mode.load();
+  }
+  return p;
 }
 // The X pass and the final conversion of the whole grid `p`, into sdf_dev and the workspace's extrema.
 hipError_t LaunchPassThree(const SdfWorkspace& ws, const vgt::SdfParams& p, float* sdf_dev, hipStream_t s)
@@ -821,16 +839,17 @@ hipEvent_t* TimingSlot(vgt_hip_ctx* ctx)
 
 // Enqueues the three passes.  events (optional) = 4 recorded events bracketing the kernels.
 template <typename InT>
-int RunSdfPipeline(vgt_hip_ctx* ctx, const InT* input_dev, const vgt::SdfParams& p, float* sdf_dev,
+int RunSdfPipeline(vgt_hip_ctx* ctx, const InT* input_dev, const vgt::SdfParams& given, float* sdf_dev,
                    void* workspace_dev, size_t workspace_bytes, float* minmax_dev,
                    hipEvent_t* events)
 {
-  if (p.batch > 1 && ctx->variant != 0)
+  if (given.batch > 1 && ctx->variant != 0)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "batches run on the default EDT pipeline only");
-  const SdfWorkspace ws = CarveWorkspace(workspace_dev, p.nx, p.ny, p.nz, ctx->variant, p.batch);
+  const SdfWorkspace ws = CarveWorkspace(workspace_dev, given.nx, given.ny, given.nz, ctx->variant, given.batch);
   if (workspace_dev == nullptr || workspace_bytes < ws.bytes)
     return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "SDF workspace too small");
   hipStream_t s = ctx->stream;
+  const vgt::SdfParams p = WithKernelByScene(ws, given);
   // A batch of grids (one after the other in every buffer) is ONE grid of batch * nx slices to pass 1 and to the Y
   // pass -- their lines never leave a slice -- and p.batch grids to the X pass, whose lines run along x.
   vgt::SdfParams slices = p;
@@ -1639,6 +1658,51 @@ int vgt_hip_testing_set_short_line_rows(int rows)
 {
   // 0 ... kShortLineRowsFewItems; negative: back to the defaults
   g_short_line_override.store(rows < 0 ? -1 : (rows > vgt::kShortLineRowsFewItems ? vgt::kShortLineRowsFewItems : rows));
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_sweep_slots(int slots)
+{
+  g_sweep_slots_override.store(slots > 0 ? slots : 0);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_set_coarse_hull(int mode)
+{
+  if (mode != vgt::kXKernelByScene && mode != vgt::kXKernelCoarse && mode != vgt::kXKernelPlain)
+    return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "coarse-hull mode must be 0 (by scene), 1 (always) or 2 (never)");
+  g_coarse_hull_mode.store(mode);
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_x_pass_choice(vgt_hip_ctx* ctx, const void* workspace_dev, int64_t nx, int64_t ny, int64_t nz,
+                                  int32_t* choice)
+{
+  if (!ctx || !workspace_dev || !choice) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckSdfShape(nx, ny, nz, 1.0);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const SdfWorkspace ws = CarveWorkspace(const_cast<void*>(workspace_dev), nx, ny, nz, ctx->variant);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "synchronize");
+  // (the second int of the sweeps' scratch head: edt_sweep_kernels.hip, kChoiceWord)
+  VGT_TRY_HIP(hipMemcpy(choice, static_cast<const char*>(ws.sweep_scratch.ptr) + sizeof(int32_t), sizeof(int32_t),
+                        hipMemcpyDeviceToHost),
+              "copy");
+  return VGT_HIP_OK;
+}
+
+int vgt_hip_testing_one_class_counts(vgt_hip_ctx* ctx, const void* workspace_dev, int64_t nx, int64_t ny, int64_t nz,
+                                     uint32_t* counts)
+{
+  if (!ctx || !workspace_dev || !counts) return Fail(VGT_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int rc = CheckSdfShape(nx, ny, nz, 1.0);
+  if (rc != VGT_HIP_OK) return rc;
+  VGT_TRY_HIP(hipSetDevice(ctx->device), "set device");
+  const SdfWorkspace ws = CarveWorkspace(const_cast<void*>(workspace_dev), nx, ny, nz, ctx->variant);
+  std::lock_guard<std::mutex> lock(ctx->mutex);
+  VGT_TRY_HIP(hipStreamSynchronize(ctx->stream), "synchronize");
+  VGT_TRY_HIP(hipMemcpy(counts, ws.minmax_enc + vgt::kOneClassWord, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy");
   return VGT_HIP_OK;
 }
 

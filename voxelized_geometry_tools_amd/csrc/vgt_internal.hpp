@@ -36,6 +36,9 @@ constexpr int32_t kInf32 = 0x7fffffff;
 // and every parabola value below 2^31.
 constexpr int64_t kMaxExtent = 16384;
 
+// Which kernel the plain X pass with 32-bit entries runs (SdfParams::x_kernel): chosen on the device by scene, the coarse-hull
+// kernel wherever it applies (whatever it costs), or the plain kernel alone.
+constexpr int kXKernelByScene = 0, kXKernelCoarse = 1, kXKernelPlain = 2;
 struct SdfParams
 {
   int64_t nx, ny, nz;  // extents of the grid held by this device (a Z slab when partitioned)
@@ -50,7 +53,17 @@ struct SdfParams
   // see it as one grid of batch * nx slices (their lines never leave a slice), only the X pass -- whose lines run along
   // x -- and the extrema need to know.
   int64_t batch = 1;
+  // The X pass's kernel by scene (edt_sweep_kernels.hip: the coarse-hull form of the plain X sweep wins on sparse scenes and
+  // loses on dense ones).  Pass 1 adds the number of Z lines that hold one class into one_class_lines[0] and the number of
+  // lines counted into one_class_lines[1] when it is given (cleared by LaunchInitMinMax: the words kOneClassWord and the
+  // next of a single grid's minmax_enc), and the X pass, given the same words, enqueues both kernels and lets the device
+  // choose (kXKernelByScene).  The default is the plain kernel alone.
+  uint32_t* one_class_lines = nullptr;
+  int x_kernel = kXKernelPlain;
 };
+// minmax_enc of ONE grid: [0] / [1] the extrema, [kOneClassWord] pass 1's count of one-class Z lines among the
+// [kOneClassWord + 1] lines that its counting workgroups saw (a sample spread over the grid).
+constexpr int kOneClassWord = 2;
 
 // Pass 1 of the default pipeline (edt_record_kernels.hip): the binarised grid as CLASS RECORDS, one 16-byte record per
 // 64-voxel word of a Z line, laid out [x][word][y] so that the records a Y-pass wave walks through (one x, one word,
@@ -156,6 +169,9 @@ constexpr int64_t kFewLineItems = 1024;
 // What a testing build was told (vgt_hip_testing_set_short_line_rows), -1 = nothing (the product library: always).
 // Defined next to that hook, in vgt_hip_capi.hip.
 int ShortLineOverride();
+// Workgroups (= scratch slots) per sweep launch a testing build was told to stop at (vgt_hip_testing_set_sweep_slots), 0 =
+// nothing (the product library: always).  Defined next to that hook, in vgt_hip_capi.hip.
+int SweepSlotsOverride();
 inline int ShortLineRows()
 {
   const int told = ShortLineOverride();
@@ -184,7 +200,7 @@ hipError_t LaunchPassXSweepFinalize(const int32_t* in32, float* sdf, uint32_t* m
 // Scratch for the lane-per-line sweep passes (edt_sweep_kernels.hip): work counter, spilled stack entries and sign
 // words of the workgroups in flight.
 size_t SweepPassScratchBytes(int64_t nx, int64_t ny, int64_t nz, int64_t batch = 1);
-// `count` pairs of ordered encodings (one per grid of a batch)
+// `count` pairs of ordered encodings (one per grid of a batch); one grid: the word kOneClassWord is cleared as well
 hipError_t LaunchInitMinMax(uint32_t* minmax_enc, hipStream_t stream, int64_t count = 1);
 hipError_t LaunchDecodeMinMax(const uint32_t* minmax_enc, float* minmax_out, hipStream_t stream, int64_t count = 1);
 
